@@ -17,13 +17,17 @@ host" (§8d) is part of every step.  Inputs are synthetic int16 depth
 each step aligns every (k, k+1) pair (each frame prepared once), gathers the
 relative poses and composes the trajectory on rank 0 (strong scaling).
 
-At N = 1, rank 0 also runs, after the timed region and beside the headline
-value: the C2 (one pair per call), C3 (1280x960, 20 iterations) and C5
-(1000-frame sequence: batch and streamed) legs, each with its pose error
-against the C oracle; the PCIe-inclusive host-buffer API; the viewer point
-list (§8 f4); and the CPU baseline (the C oracle on the host cores).
+A plain run sets up, warms up, times the K steps, writes the last step's
+outputs (`--dump-outputs DIR`) and prints the line.  With `--full`, after the
+timed region and beside the headline value: spread windows, the k_prep
+timing pass, every rank's parity sample against the C oracle and its
+self-report; and at N = 1 rank 0 also runs the C2 (one pair per call), C3
+(1280x960, 20 iterations) and C5 (1000-frame sequence: batch and streamed)
+legs, each with its pose error against the C oracle; the PCIe-inclusive
+host-buffer API; the viewer point list (§8 f4); spec parity; and the CPU
+baseline (the C oracle on the host cores).
 
-Launch: python bench.py [--gpus N] [--steps K] [--warmup W]   (N > 1: bench.py starts
+Launch: python bench.py [--gpus N] [--steps K] [--warmup W] [--full]   (N > 1: bench.py starts
         torch.distributed.run with N ranks as a child process and exits with its code)
         python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 Rank 0 prints ONE JSON line.
@@ -134,8 +138,21 @@ def parse():
                     help="after the --warmup steps, run more untimed steps until the warm-up has "
                          "lasted this long (the GPU's clock ramps over ~10-20 ms from idle; "
                          "reported as warmup_steps_run); 0 = exactly --warmup steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beside the headline value: "
+                         "the spread windows, the k_prep timing pass, every rank's parity sample "
+                         "against the C oracle and its self-report, and at N = 1 the CPU baseline, "
+                         "the C2 / C3 / C5 legs, host I/O, the viewer and spec parity (each leg "
+                         "has its own --no-* switch).  Without it the run sets up, warms up, "
+                         "times the --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the last timed step delivered "
+                         "to its caller as DIR/<name>.npy (float32 / float64): pairs: poses (the "
+                         "gathered fp32 poses in host memory), poses_fp64 and status (rank 0's "
+                         "shard); sequence: relative_poses and trajectory")
     ap.add_argument("--windows", type=int, default=3,
-                    help="extra timed windows of --steps steps after the timed region (spread)")
+                    help="--full: extra timed windows of --steps steps after the timed region "
+                         "(spread)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-legs", action="store_true",
                     help="skip the C2 / C3 / C5 legs (rank 0, N=1)")
@@ -165,7 +182,10 @@ def parse():
                          "them with the N = 1 run's)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic.json"),
                     help="PMC-derived HBM bytes and VALU figures of k_icp (tools/pmc_traffic.py)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
+    return a
 
 
 def oracle_mod():
@@ -225,9 +245,9 @@ class Run:
 
     def timed(self, ctx, step):
         """W warm-up steps, then EXACTLY K timed steps between barrier + sync
-        (max over ranks), HIP events around the iteration kernel only; then
-        `windows` more K-step windows (spread) and a short pass timing every
-        kernel kind (k_prep)."""
+        (max over ranks), HIP events around the iteration kernel only; with
+        --full, then `windows` more K-step windows (spread) and a short pass
+        timing every kernel kind (k_prep)."""
         a = self.a
         t0 = time.perf_counter()
         for _ in range(a.warmup):
@@ -255,6 +275,8 @@ class Run:
         elapsed = self.window(step, a.steps)
         kt = {"k_icp": ctx.get_timing(0)}
         ctx.set_timing(False)
+        if not a.full:
+            return elapsed, kt, []
         spread = [self.window(step, a.steps) for _ in range(a.windows)]
         ctx.set_timing(True)
         extra = min(a.steps, 5)
@@ -452,6 +474,17 @@ def parity_gate(result):
     return ok
 
 
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy.  float32 and float64 stay
+    as they are; anything else (the status words) is stored as float64."""
+    os.makedirs(d, exist_ok=True)
+    for name, x in arrays.items():
+        x = np.asarray(x)
+        if x.dtype not in (np.float32, np.float64):
+            x = x.astype(np.float64)
+        np.save(os.path.join(d, name + ".npy"), x)
+
+
 def pose_err(Ta, Tb):
     """max |Ta - Tb| over the 3x4 entries (any leading shape)."""
     Ta = np.asarray(Ta, np.float64).reshape(-1, 4, 4)
@@ -544,15 +577,24 @@ def run_pairs(R):
         "parallelism": f"dp{world} (contiguous pair shards, RCCL pose all-gather)",
         "steps_in_flight": depth, "k_icp_slot_share": f"1/{share}",
     }
-    result["window_rates"] = [n_glob * a.steps / s for s in spread]
+    # k_icp's events sat inside the timed window: its roofline needs no run of its own
     result["roofline"] = roofline_icp(a, kt, n, W, H, share)
-    result["roofline_prep"] = roofline_prep(a, kt, n, W, H)
-    result["kernel_ms_per_step"] = {"k_icp": kt["k_icp"][0] / max(kt["k_icp"][1], 1),
-                                    "k_prep": kt["k_prep"][0] / max(kt["prep_pass_steps"], 1)}
+    result["kernel_ms_per_step"] = {"k_icp": kt["k_icp"][0] / max(kt["k_icp"][1], 1)}
     spins, waited = ctx.get_sched_stats()   # last align: persistent-kernel pose waits
     result["sched_last_step"] = {"epoch_polls": spins, "items_waited": waited}
     result["kernel_path"] = ctx.get_plan()
     result["status_nonzero"] = int((st_gpu != 0).sum())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"poses": last_host, "poses_fp64": T_gpu, "status": st_gpu})
+    if a.dump_poses:
+        np.save(f"{a.dump_poses}.rank{rank}.npy", np.asarray(T_gpu, np.float64).reshape(-1, 4, 4))
+    if not a.full:
+        for c in ctxs:
+            c.close()
+        return result
+    result["window_rates"] = [n_glob * a.steps / s for s in spread]
+    result["roofline_prep"] = roofline_prep(a, kt, n, W, H)
+    result["kernel_ms_per_step"]["k_prep"] = kt["k_prep"][0] / max(kt["prep_pass_steps"], 1)
     # every rank's own k_icp / k_prep / gather times and the group's size
     # (collective: all ranks), so an N > 1 line shows that N ranks ran and
     # splits compute from the collective
@@ -561,8 +603,6 @@ def run_pairs(R):
     # oracle (these pairs sit at the shard's own launch geometry)
     idx = parity_sample(n)
     perr = shard_parity(a, src, dst, T_gpu, idx)
-    if a.dump_poses:
-        np.save(f"{a.dump_poses}.rank{rank}.npy", np.asarray(T_gpu, np.float64).reshape(-1, 4, 4))
     result["ranks"] = youth_dist.rank_report({
         "k_icp_ms": result["kernel_ms_per_step"]["k_icp"],
         "k_prep_ms": result["kernel_ms_per_step"]["k_prep"],
@@ -1193,8 +1233,23 @@ def run_sequence(R):
         "frames": F, "pairs": F - 1, "width": W, "height": H, "iters": a.iters,
         "parallelism": f"dp{world} (contiguous pair ranges, RCCL pose gather)",
     }
-    result["window_rates"] = [(F - 1) * a.steps / s for s in spread]
     result["roofline"] = roofline_icp(a, kt, max(npairs, 1), W, H)
+    T_rel = ctx.get_poses(npairs)[0] if npairs else None
+    if a.dump_poses:
+        np.save(f"{a.dump_poses}.rank{rank}.npy",
+                np.asarray(T_rel if npairs else np.zeros((0, 4, 4)), np.float64).reshape(-1, 4, 4))
+    if rank == 0:
+        rows = traj["T"].cpu().numpy().reshape(-1, 4, 4)
+        T = youth_dist.compose_trajectory(rows)
+        result["trajectory_frames"] = int(T.shape[0])
+        if a.dump_poses:
+            np.save(f"{a.dump_poses}.traj.npy", np.asarray(T, np.float64))
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, {"relative_poses": rows, "trajectory": T})
+    if not a.full:
+        ctx.close()
+        return result
+    result["window_rates"] = [(F - 1) * a.steps / s for s in spread]
     g_ms = None
     if R.dist_on:
         ts = []
@@ -1208,11 +1263,7 @@ def run_sequence(R):
     # every rank checks its first pair and its halo pair (the last, whose
     # source frame is the next shard's first) against the CPU oracle
     idx = sorted({0, npairs - 1}) if npairs else []
-    T_rel = ctx.get_poses(npairs)[0] if npairs else None
     perr = shard_parity(a, frames[1:], frames[:-1], T_rel, idx)
-    if a.dump_poses:
-        np.save(f"{a.dump_poses}.rank{rank}.npy",
-                np.asarray(T_rel if npairs else np.zeros((0, 4, 4)), np.float64).reshape(-1, 4, 4))
     result["ranks"] = youth_dist.rank_report({
         "k_icp_ms": kt["k_icp"][0] / max(kt["k_icp"][1], 1),
         "k_prep_ms": kt["k_prep"][0] / max(kt["prep_pass_steps"], 1),
@@ -1221,11 +1272,6 @@ def run_sequence(R):
     result["ranks"]["gather_timed"] = g_ms is not None
     result["ranks"]["parity_sample"] = "each rank: its first pair and its halo pair vs the C oracle"
     parity_gate(result)
-    if rank == 0:
-        T = youth_dist.compose_trajectory(traj["T"].cpu().numpy().reshape(-1, 4, 4))
-        result["trajectory_frames"] = int(T.shape[0])
-        if a.dump_poses:
-            np.save(f"{a.dump_poses}.traj.npy", np.asarray(T, np.float64))
     ctx.close()
     return result
 
@@ -1391,7 +1437,8 @@ def main():
     with torch.cuda.stream(torch.cuda.Stream()):
         result = run_pairs(R) if a.workload == "pairs" else run_sequence(R)
     if R.rank == 0:
-        result["legs"] = legs_summary(result)   # last key: survives a truncated tail
+        if a.full:
+            result["legs"] = legs_summary(result)   # last key: survives a truncated tail
         print(json.dumps(result), flush=True)
     R.finish()
     if R.rank == 0 and not result.get("parity_all_ranks_ok", True):

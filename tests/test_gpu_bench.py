@@ -41,7 +41,7 @@ def _port():
 
 
 def test_bench_single_gpu_contract():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1",
                         "--global-pairs", "64", "--windows", "1", "--c3-pairs", "2",
                         "--c5-frames", "41"], cwd=ROOT, capture_output=True, text=True,
                        timeout=600)
@@ -122,12 +122,49 @@ def test_bench_single_gpu_contract():
     _assert_rank_parity(d, 1, 4)
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the run times its steps and prints the headline line
+    with nothing that takes a run of its own (windows, k_prep pass, oracle
+    checks, legs); --dump-outputs writes the last timed step's poses: the
+    fp32 rows delivered to host memory, the fp64 poses and the status words.
+    The fp32 rows are the fp64 poses rounded (entries below 8 in magnitude:
+    half an fp32 ulp is < 4.8e-7), and the first four pairs sit within 1e-5
+    of the C oracle's poses of the same synthetic pairs."""
+    import numpy as np
+
+    import oracle
+    import youth_synth
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--global-pairs", "32", "--dump-outputs", str(out)], cwd=ROOT,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _json_line(r.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["unit"] == "aligns/s" and d["dtype"] == "fp32"
+    assert d["ms_per_step"] > 0
+    assert abs(d["value"] - 32 * 1e3 / d["ms_per_step"]) <= 1e-9 * d["value"]
+    assert d["status_nonzero"] == 0 and d["roofline"]["launches"] > 0
+    for k in ("window_rates", "roofline_prep", "ranks", "parity_all_ranks_ok", "cpu_baseline",
+              "parity", "host_io", "c2", "c3", "c5", "viewer_cloud", "spec_parity", "legs"):
+        assert k not in d, k
+    assert sorted(p.name for p in out.iterdir()) == ["poses.npy", "poses_fp64.npy", "status.npy"]
+    P, P64, st = (np.load(out / f"{n}.npy") for n in ("poses", "poses_fp64", "status"))
+    assert P.dtype == np.float32 and P64.dtype == np.float64 and st.dtype == np.float64
+    assert P.shape == P64.shape == (32, 4, 4) and st.shape == (32,) and not st.any()
+    assert float(np.abs(P - P64).max()) <= 4.8e-7
+    src, dst, _ = youth_synth.pairs(0, 4)
+    T_cpu, _ = oracle.align_batch(src, dst, iters=10, n_threads=4)
+    assert float(np.abs(P64[:4, :3] - T_cpu[:, :3]).max()) <= 1e-5
+
+
 @pytest.mark.parametrize("workload", ["pairs", "sequence"])
 def test_bench_two_ranks_rehearsal(workload):
     env = dict(os.environ, YOUTH_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus",
-           "2", "--steps", "3", "--warmup", "1", "--windows", "1", "--workload", workload,
+           "2", "--full", "--steps", "3", "--warmup", "1", "--windows", "1", "--workload", workload,
            "--global-pairs", "128"]
     if workload == "sequence":
         cmd += ["--frames", "41"]
@@ -160,7 +197,7 @@ def test_bench_three_ranks_uneven_shards(workload):
     env = dict(os.environ, YOUTH_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus",
-           "3", "--steps", "3", "--warmup", "1", "--windows", "1", "--workload", workload,
+           "3", "--full", "--steps", "3", "--warmup", "1", "--windows", "1", "--workload", workload,
            "--global-pairs", "100", "--frames", "61"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -189,7 +226,7 @@ def test_bench_rccl_gather_one_gpu(workload):
     env.pop("YOUTH_BENCH_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus",
-           "1", "--steps", "3", "--warmup", "1", "--windows", "1", "--workload", workload,
+           "1", "--full", "--steps", "3", "--warmup", "1", "--windows", "1", "--workload", workload,
            "--global-pairs", "32", "--frames", "21", "--no-legs", "--no-cpu-baseline",
            "--no-host-io", "--no-viewer"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
@@ -206,8 +243,8 @@ def test_bench_gpus_flag_self_launches_ranks():
     env = dict(os.environ, YOUTH_BENCH_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup",
-                        "1", "--windows", "1", "--global-pairs", "64"], cwd=ROOT, env=env,
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--full", "--steps", "3",
+                        "--warmup", "1", "--windows", "1", "--global-pairs", "64"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
@@ -240,8 +277,8 @@ def test_bench_eight_ranks_rehearsal(workload, tmp_path):
     solo = ["--no-legs", "--no-cpu-baseline", "--no-host-io", "--no-viewer", "--no-spec-parity"]
     p8, p1 = str(tmp_path / "n8"), str(tmp_path / "n1")
     t0 = time.perf_counter()
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--dump-poses", p8] + common,
-                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--full", "--dump-poses", p8]
+                       + common, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     wall8 = time.perf_counter() - t0
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)

@@ -14,7 +14,7 @@ for r in $(seq 1 $R); do
     envargs=()
     if [ -n "${envs:-}" ]; then IFS=, read -ra envargs <<< "$envs"; fi
     env "${envargs[@]}" YOUTH_ICP_LIB=tools/ab/$lib/libyouth_icp.so timeout -k 10 240 python3 bench.py \
-        --steps 30 --warmup 5 --no-cpu-baseline --no-host-io ${EXTRA:-} \
+        --full --steps 30 --warmup 5 --no-cpu-baseline --no-host-io ${EXTRA:-} \
         > gpurun_out/ab/$label.$r.json 2> gpurun_out/ab/$label.$r.err
     python3 - "$label" "$r" <<'PY'
 import json,sys

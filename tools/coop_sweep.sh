@@ -9,7 +9,7 @@ one() {  # label env... -- bench args
     local label=$1; shift
     local envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
     local out
-    out=$(env "${envs[@]}" timeout -k 10 120 python3 bench.py --no-cpu-baseline --no-host-io "$@") || { echo "$label FAILED"; return 1; }
+    out=$(env "${envs[@]}" timeout -k 10 120 python3 bench.py --full --no-cpu-baseline --no-host-io "$@") || { echo "$label FAILED"; return 1; }
     python3 -c "import json,sys; d=json.loads(sys.argv[1]); k=d['kernel_ms_per_step']; print(f\"{sys.argv[2]:34s} {d['value']:9.0f} aligns/s  ms/step {d['ms_per_step']*1e3:7.1f} us  icp {k['k_reduce']*1e3:7.1f} us  prep {k['k_prep']*1e3:5.1f} us\")" "$out" "$label"
 }
 for r in $(seq 1 $R); do

@@ -6,7 +6,7 @@ for r in 1 2; do
   for n in 64 128; do
     for cfg in "1 1" "2 2" "3 3" "4 4" "2 1"; do
       set -- $cfg
-      timeout -k 10 200 python3 bench.py --global-pairs $n --pipeline $1 --share $2 --steps 40 --warmup 5 \
+      timeout -k 10 200 python3 bench.py --full --global-pairs $n --pipeline $1 --share $2 --steps 40 --warmup 5 \
           --windows 2 --no-legs --no-viewer --no-spec-parity --no-host-io --no-cpu-baseline > gpurun_out/sp.json
       python3 -c "
 import json; d=json.loads(open('gpurun_out/sp.json').read().strip().splitlines()[-1])

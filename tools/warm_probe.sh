@@ -5,7 +5,7 @@ set -euo pipefail
 mkdir -p gpurun_out/warm
 for gp in 64 128; do
   for w in ${WARMS:-5 50 400}; do
-    timeout -k 10 120 python3 bench.py --global-pairs $gp --steps 20 --warmup $w --no-cpu-baseline \
+    timeout -k 10 120 python3 bench.py --full --global-pairs $gp --steps 20 --warmup $w --no-cpu-baseline \
         --no-host-io --no-legs --no-viewer > gpurun_out/warm/g${gp}_w$w.json 2> gpurun_out/warm/g${gp}_w$w.err
     python3 - gpurun_out/warm/g${gp}_w$w.json $gp $w <<'PY'
 import json, sys
