@@ -316,8 +316,9 @@ int youth_icp_get_sched_stats(youth_icp_ctx* ctx, unsigned* spins,
 
 /* Kernel path of the last align on this context (build-only, reporting):
  * returns 1 when it ran the small-batch cooperative kernel (k_icp_coop:
- * *workgroups_per_pair x 512 threads, *px_per_lane source pixels per lane,
- * target prep fused), 0 for the persistent batch kernel (k_prep + k_icp),
+ * *workgroups_per_pair workgroups of 512 threads, or of 256 under
+ * YOUTH_ICP_COOP_THREADS=256 (youth_icp_get_lanes reports the size that
+ * ran), *px_per_lane source pixels per lane, target prep fused), 0 for the persistent batch kernel (k_prep + k_icp),
  * 2 for the per-iteration fallback (YOUTH_ICP_NO_PERSISTENT=1: k_prep, k_init,
  * then one k_reduce with the fused last-workgroup solve per iteration),
  * negative on error.  Either pointer may be NULL. */

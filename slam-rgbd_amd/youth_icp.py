@@ -411,7 +411,10 @@ class IcpContext:
         self.W, self.H, self.max_frames = width, height, max_frames
         self.K = K if K is not None else default_intrinsics(width, height)
         self.params = Params(iters, dist_thresh)
-        self._ctx = self._lib.youth_icp_create(device, width, height, max_frames,
+        # youth_icp_create's reading of YOUTH_ICP_COOP_THREADS (atoi == 256)
+        m = re.match(r"\s*[+-]?\d+", os.environ.get("YOUTH_ICP_COOP_THREADS", ""))
+        self._coop_threads = 256 if m and int(m.group()) == 256 else 512
+        self._ctx =self._lib.youth_icp_create(device, width, height, max_frames,
                                                ctypes.byref(self.K), ctypes.byref(self.params))
         if not self._ctx:
             msg = (self._lib.youth_icp_last_error() or b"").decode()
@@ -531,12 +534,22 @@ class IcpContext:
 
     def get_plan(self) -> dict:
         """Kernel path of the last align: the small-batch cooperative kernel
-        (workgroups per pair, source pixels per lane) or the persistent one."""
+        (workgroups per pair, threads per workgroup, source pixels per lane)
+        or the persistent one."""
         g, px = c_int(0), c_int(0)
         r = self._lib.youth_icp_get_plan(self._ctx, ctypes.byref(g), ctypes.byref(px))
         _check(min(r, 0))
         if r == 1:
-            return {"kernel": "k_icp_coop", "workgroups_per_pair": g.value, "threads": 512,
+            # the workgroup size follows YOUTH_ICP_COOP_THREADS: the launch's own
+            # record, unless a stage call or a mixed host batch has replaced it
+            threads = self._coop_threads
+            try:
+                kind, _, lane_threads, _ = self.lanes()
+                if kind in (LANES_COOP, LANES_COOP_TILE):
+                    threads = lane_threads
+            except IcpError:
+                pass
+            return {"kernel": "k_icp_coop", "workgroups_per_pair": g.value, "threads": threads,
                     "px_per_lane": px.value}
         if r == 2:
             return {"kernel": "k_prep + k_init + k_reduce x iters (per-iteration)"}
