@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "host_copy.h"
+#include "slam_map_hooks.h"
 #include "youth_icp.h"
 
 // ----------------------------------------------------------- event trace --
@@ -480,6 +481,10 @@ bool g_cfg_has_yaml = false;
 
 // tracker state (worker thread owns ctx; trajectory guarded by g_slam_mu)
 std::vector<PoseRec> g_traj;
+// the voxel map's hook table (slam_map_hooks.h): null unless slam_map.cpp is
+// linked in; its integrate / clear run under g_slam_mu, next to the
+// trajectory change they belong to
+std::atomic<const youth_slam_map_hooks*> g_map_hooks{nullptr};
 // g_traj.size(), stored under g_slam_mu after every change: a host polling
 // for its pose (youth_slam_trajectory_length) does not take the lock the
 // worker records every pose under
@@ -619,6 +624,7 @@ void worker_main(int device)
             memcpy(T_w_ref, I, sizeof(I));
             g_traj.clear();
             g_traj_len.store(0, std::memory_order_release);
+            if (const youth_slam_map_hooks* mh = g_map_hooks.load()) mh->clear();
         } else {
             // P_ref = T_rel P_new  =>  T_w_new = T_w_ref * T_rel
             mat_mul4(T_w_ref, T_rel, T_w_ref);
@@ -635,6 +641,12 @@ void worker_main(int device)
         g_traj.push_back(pr);
         g_traj_len.store((int)g_traj.size(), std::memory_order_release);
         if (pr0.npts >= 0) g_last_points = pr0.npts;
+        // the map takes every recorded frame with the pose just recorded; the
+        // frame's buffer (now ref_hold) is read before this returns
+        if (const youth_slam_map_hooks* mh = g_map_hooks.load()) {
+            const youth_intrinsics K = intrinsics_for(pr0.item.w, pr0.item.h);
+            mh->integrate(pr0.item.buf, pr0.item.w, pr0.item.h, &K, T_w_ref);
+        }
     };
     while (g_process.load()) {
         Item items[YOUTH_TRACK_MAX_BATCH];
@@ -868,6 +880,7 @@ void initSlamModule(const char* config_file, const char* vocabulary_file)
     g_traj.clear();
     g_traj_len.store(0, std::memory_order_release);
     g_last_points = 0;
+    if (const youth_slam_map_hooks* mh = g_map_hooks.load()) mh->start(device);
     g_process.store(true);
     g_batched.store(0);
     for (auto& r : g_realigned) r.store(0);
@@ -895,6 +908,7 @@ void stopSlamModule(void)
     g_process.store(false);
     if (g_worker.joinable()) g_worker.join();
     if (g_queue) youth_queue_clear(g_queue);
+    if (const youth_slam_map_hooks* mh = g_map_hooks.load()) mh->stop();
     {
         std::lock_guard<std::mutex> sl(g_state_mu);
         g_running.store(false);
@@ -940,8 +954,10 @@ int saveSlamMap(const char* map_file)
     const std::string base(map_file);
     // every frame is tracked frame-to-frame, so the keyframe file equals the
     // trajectory (SLAM.cpp:188 writes both)
-    const int ok = write_tum(base + "_trajectory.txt", traj) &&
-                   write_tum(base + "_keyframes.txt", traj);
+    int ok = write_tum(base + "_trajectory.txt", traj) &&
+             write_tum(base + "_keyframes.txt", traj);
+    // <map_file>_map.ply when the voxel map is on (youth_map.h)
+    if (const youth_slam_map_hooks* mh = g_map_hooks.load()) ok = mh->save(map_file) && ok;
     if (ok)
         fprintf(stderr, "youth_icp: map saved to %s\n", map_file);
     else
@@ -970,6 +986,7 @@ void resetSlam(void)
         g_traj.clear();
         g_traj_len.store(0, std::memory_order_release);
         g_last_points = 0;
+        if (const youth_slam_map_hooks* mh = g_map_hooks.load()) mh->clear();
     }
     fprintf(stderr, "youth_icp: SLAM system reset\n");
 }
@@ -1034,6 +1051,8 @@ int youth_slam_wait_idle(int timeout_ms)
     }
     return 0;
 }
+
+void youth_slam_set_map_hooks(const youth_slam_map_hooks* hooks) { g_map_hooks.store(hooks); }
 
 // recorded from inside the tracker (icp_kernels.hip: a submission's steps)
 void youth_slam_trace_hook(int kind, int arg) { trace(kind, arg); }

@@ -1,0 +1,29 @@
+// The SLAM module's door to the voxel map (include/youth_map.h).  slam_api.cpp
+// knows the map only through this table, which slam_map.cpp registers from a
+// static initialiser: a build of slam_api.cpp without that unit (the host-only
+// sanitizer drivers) links as before and finds the table null.
+#ifndef YOUTH_SLAM_MAP_HOOKS_H
+#define YOUTH_SLAM_MAP_HOOKS_H
+
+#include <stdint.h>
+
+#include "youth_icp.h"
+
+struct youth_slam_map_hooks {
+    // initSlamModule: read YOUTH_SLAM_MAP_* and create the map (or leave it off)
+    void (*start)(int device);
+    // stopSlamModule, after the worker has been joined
+    void (*stop)(void);
+    // a recorded frame and its camera -> world pose (fp64 4x4); returns when
+    // the frame's buffer has been read
+    void (*integrate)(const int16_t* depth, int w, int h, const youth_intrinsics* K,
+                      const double* T_world);
+    // resetSlam / a new sequence's origin
+    void (*clear)(void);
+    // saveSlamMap: <base>_map.ply; 1 written or map off, 0 failed
+    int (*save)(const char* base);
+};
+
+extern "C" void youth_slam_set_map_hooks(const youth_slam_map_hooks* hooks);
+
+#endif  // YOUTH_SLAM_MAP_HOOKS_H

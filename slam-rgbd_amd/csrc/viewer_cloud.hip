@@ -28,77 +28,17 @@
 #include <cstring>
 #include <string>
 
+#include "cloud_backproject.h"
 #include "youth_viewer.h"
 
 namespace {
 
+using youth_cloud::CloudK;
+using youth_cloud::load_depth;
+using youth_cloud::load_rgb;
+
 constexpr int kCloudThreads = 256;
 constexpr int kVF = YOUTH_CLOUD_FLOATS_PER_VERTEX;      // 6 floats per vertex
-
-struct CloudK {
-    float fx, fy, cx, cy, ds;
-};
-
-// kPx depth values of pixels [i, i+kPx) of one frame.  kVec: one 8-/16-byte
-// load (frame base aligned, N % kPx == 0, so i + kPx <= N whenever i < N).
-template <bool kVec, int kPx>
-__device__ __forceinline__ void load_depth(const int16_t* __restrict__ d, int i, int N, int* dd)
-{
-    if (kVec) {
-        int v[kPx / 2];
-        if (i < N) {
-            if constexpr (kPx == 8) {
-                const int4 w = *reinterpret_cast<const int4*>(d + i);
-                v[0] = w.x;
-                v[1] = w.y;
-                v[2] = w.z;
-                v[3] = w.w;
-            } else {
-                const int2 w = *reinterpret_cast<const int2*>(d + i);
-                v[0] = w.x; v[1] = w.y;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < kPx / 2; ++k) v[k] = 0;
-        }
-#pragma unroll
-        for (int k = 0; k < kPx / 2; ++k) {
-            dd[2 * k] = (int)(short)(v[k] & 0xffff);   // little-endian: low half first
-            dd[2 * k + 1] = v[k] >> 16;                // arithmetic shift: sign kept
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kPx; ++k) dd[k] = (i + k) < N ? (int)d[i + k] : 0;
-    }
-}
-
-// kPx * 3 colour bytes of pixels [i, i+kPx) (viewerModule.c:348-352): kVec
-// loads 8-byte (kPx 8) or 4-byte (kPx 4) words, the offset (fN + i) * 3
-// being a multiple of 24 / 12.
-template <bool kVec, int kPx>
-__device__ __forceinline__ void load_rgb(const uint8_t* __restrict__ c, int i, int N,
-                                         unsigned char* cc)
-{
-    if (kVec && i < N) {
-        unsigned wds[kPx * 3 / 4];
-        if constexpr (kPx == 8) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const uint2 w = *reinterpret_cast<const uint2*>(c + 8 * k);
-                wds[2 * k] = w.x;
-                wds[2 * k + 1] = w.y;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) wds[k] = *reinterpret_cast<const unsigned*>(c + 4 * k);
-        }
-#pragma unroll
-        for (int k = 0; k < kPx * 3; ++k) cc[k] = (unsigned char)(wds[k >> 2] >> (8 * (k & 3)));
-    } else {
-#pragma unroll
-        for (int k = 0; k < kPx * 3; ++k) cc[k] = (i + k / 3) < N ? c[k] : (unsigned char)0;
-    }
-}
 
 __device__ __forceinline__ int wave_sum_i32(int x)
 {
@@ -227,15 +167,13 @@ __global__ __launch_bounds__(kCloudThreads) void k_cloud_emit(
 #pragma unroll
     for (int k = 0; k < kPx; ++k) {
         if (dd[k] > 0) {
-            // viewerModule.c:343-345, evaluated as written (IEEE quotients)
-            const float z = (float)dd[k] / K.ds;
-            const float x = (((float)u - K.cx) * z) / K.fx;
-            const float y = (((float)v - K.cy) * z) / K.fy;
-            // world frame (youth_cloud_build_device_posed): P_w = R P + t as
-            // three fma chains, the ICP transform's order (spec a7)
-            const float px = T_world ? fmaf(Tw[2], z, fmaf(Tw[1], y, fmaf(Tw[0], x, Tw[3]))) : x;
-            const float py = T_world ? fmaf(Tw[6], z, fmaf(Tw[5], y, fmaf(Tw[4], x, Tw[7]))) : y;
-            const float pz = T_world ? fmaf(Tw[10], z, fmaf(Tw[9], y, fmaf(Tw[8], x, Tw[11]))) : z;
+            // viewerModule.c:343-345 and, posed, the camera -> world fma
+            // chains (cloud_backproject.h)
+            float x, y, z;
+            youth_cloud::camera_point(dd[k], u, v, K, x, y, z);
+            const float px = T_world ? youth_cloud::world_axis(Tw, x, y, z) : x;
+            const float py = T_world ? youth_cloud::world_axis(Tw + 4, x, y, z) : y;
+            const float pz = T_world ? youth_cloud::world_axis(Tw + 8, x, y, z) : z;
             // glVertex3f(-x_pos, -y_pos, -z_pos) (:354), glColor3f(r, g, b) (:349-351)
             const float o[kVF] = {-px, -py, -pz, (float)cc[3 * k + 0] / 255.0f,
                                   (float)cc[3 * k + 1] / 255.0f, (float)cc[3 * k + 2] / 255.0f};

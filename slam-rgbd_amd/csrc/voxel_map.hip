@@ -1,0 +1,642 @@
+// Voxel map on gfx950 (C-ABI: include/youth_map.h; spec: DESIGN.md §10).
+//
+// World-frame point fusion: every contributing pixel of every integrated
+// frame lands in one voxel of a sparse grid kept as an open-addressing hash
+// table in HBM.  A record is integers only (count, sum of the in-voxel
+// position q per axis, sum of R, G, B) and every accumulation is an unsigned
+// integer atomic add, so the table's CONTENT does not depend on the launch
+// shape, the frame order or thread timing; only the slot a voxel sits in
+// does, and extraction sorts that away.
+//
+//   k_map_integrate  one 2048-pixel raster tile per workgroup (the viewer's
+//                    tiling: 8 consecutive pixels per thread, 16-B depth and
+//                    8-B colour loads).  A thread first merges runs of equal
+//                    keys among its own 8 pixels in registers, then adds each
+//                    run to the workgroup's LDS hash table (64-bit LDS CAS on
+//                    the key, LDS integer adds).  After a barrier each occupied
+//                    LDS slot goes to the global table as ONE insert (64-bit
+//                    CAS on the key, only when a relaxed load does not find
+//                    the key already) and one set of integer atomic adds.
+//                    A run that finds no room in the LDS table within its
+//                    probe bound goes straight to the global table; with
+//                    YOUTH_MAP_LDS=0 every run does (no LDS is allocated).
+//   k_map_extract    compacts the occupied slots into youth_voxel records
+//                    (slot order; the host sorts).
+//
+// Atomics execute at the memory side and a hashed scatter is the one-lane-
+// per-row shape, the slowest there is; the rate known for this chip was
+// measured for float adds, the integer rate is not known.  The LDS table is
+// there to send one insert per (tile, voxel) instead of one per pixel; what it
+// buys is measured by tools/map_bench.py, not assumed.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "cloud_backproject.h"
+#include "youth_map.h"
+
+namespace {
+
+using youth_cloud::CloudK;
+
+constexpr int kMapThreads = 256;
+constexpr int kMapPx = 8;                       // pixels per thread
+constexpr int kLdsSlots = kMapThreads * kMapPx / 2;   // per-workgroup table: half the tile
+constexpr int kLdsProbe = 8;                    // LDS probe bound
+constexpr int kProbe = 128;                     // global probe bound
+constexpr unsigned long long kEmpty = ~0ull;    // a key is 63 bits: never all ones
+constexpr int kValWords = 8;                    // count, q[3], c[3], pad: 32 B per slot
+enum { kStIntegrated, kStOutOfRange, kStDropped, kStOccupied, kStDirect, kStExtracted, kStN };
+
+struct MapTable {
+    unsigned long long* keys;   // [cap]
+    uint32_t* vals;             // [cap][kValWords]
+    unsigned long long* stats;  // [kStN]
+    uint32_t mask;              // cap - 1
+};
+
+struct Acc {
+    unsigned long long key;
+    uint32_t cnt, q[3], c[3];
+};
+
+__device__ __forceinline__ unsigned long long mix64(unsigned long long h)
+{
+    h ^= h >> 33;
+    h *= 0xff51afd7ed558ccdull;
+    h ^= h >> 33;
+    h *= 0xc4ceb9fe1a85ec53ull;
+    h ^= h >> 33;
+    return h;
+}
+
+// One axis of the key: false = out of range.
+__device__ __forceinline__ bool axis_key(float a, float vpm, uint32_t& cell, uint32_t& q)
+{
+    const float s = a * vpm;
+    const float fl = floorf(s);
+    if (!(-1048576.0f <= fl && fl < 1048576.0f)) return false;   // NaN fails too
+    const int i = (int)fl;
+    const float f = s - fl;   // may round up to 1.0f for tiny negative s
+    q = min(255u, (uint32_t)(f * 256.0f));
+    cell = (uint32_t)(i + (1 << 20));
+    return true;
+}
+
+// The slot of `key` in the global table, claiming an empty one if it is new;
+// false when the probe bound is exhausted (the caller drops the point).  A
+// stale relaxed load can only show "empty" for a slot that is taken, and the
+// CAS then returns the slot's real key.
+__device__ __forceinline__ bool global_slot(const MapTable& t, unsigned long long key,
+                                            uint32_t& slot, uint32_t& claimed)
+{
+    const uint32_t h = (uint32_t)mix64(key);
+    for (int p = 0; p < kProbe; ++p) {
+        const uint32_t s = (h + (uint32_t)p) & t.mask;
+        unsigned long long k =
+            __hip_atomic_load(&t.keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == kEmpty) {
+            k = atomicCAS(&t.keys[s], kEmpty, key);
+            if (k == kEmpty) {
+                ++claimed;
+                slot = s;
+                return true;
+            }
+        }
+        if (k == key) {
+            slot = s;
+            return true;
+        }
+    }
+    return false;
+}
+
+struct Tally {
+    uint32_t integrated = 0, out_of_range = 0, dropped = 0, occupied = 0, direct = 0;
+};
+
+// A run (or an LDS slot's sum) into the global table.
+template <bool kRgb>
+__device__ __forceinline__ void global_add(const MapTable& t, const Acc& a, Tally& n)
+{
+    uint32_t slot;
+    if (!global_slot(t, a.key, slot, n.occupied)) {
+        n.dropped += a.cnt;
+        return;
+    }
+    uint32_t* v = t.vals + (size_t)slot * kValWords;
+    atomicAdd(v + 0, a.cnt);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) atomicAdd(v + 1 + j, a.q[j]);
+    if (kRgb) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) atomicAdd(v + 4 + j, a.c[j]);
+    }
+    n.integrated += a.cnt;
+}
+
+struct LdsTable {
+    unsigned long long keys[kLdsSlots];
+    uint32_t vals[7][kLdsSlots];   // [word][slot]: a flush reads consecutive banks
+};
+
+template <bool kLds, bool kRgb>
+__device__ __forceinline__ void emit_run(const MapTable& t, LdsTable* lt, const Acc& a, Tally& n)
+{
+    if (kLds) {
+        const uint32_t h = (uint32_t)(mix64(a.key) >> 32);
+        for (int p = 0; p < kLdsProbe; ++p) {
+            const uint32_t s = (h + (uint32_t)p) & (kLdsSlots - 1);
+            const unsigned long long k = atomicCAS(&lt->keys[s], kEmpty, a.key);
+            if (k == kEmpty || k == a.key) {
+                atomicAdd(&lt->vals[0][s], a.cnt);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) atomicAdd(&lt->vals[1 + j][s], a.q[j]);
+                if (kRgb) {
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) atomicAdd(&lt->vals[4 + j][s], a.c[j]);
+                }
+                return;
+            }
+        }
+    }
+    n.direct += a.cnt;   // the LDS table has no room for this key (or there is none)
+    global_add<kRgb>(t, a, n);
+}
+
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
+    return x;
+}
+
+template <bool kVec, bool kLds, bool kRgb>
+__global__ __launch_bounds__(kMapThreads) void k_map_integrate(
+    const int16_t* __restrict__ depth, const uint8_t* __restrict__ rgb, int W, int N, CloudK K,
+    const float* __restrict__ T_world, float vpm, int max_depth, MapTable t)
+{
+    __shared__ __align__(8) unsigned char lds_raw[kLds ? sizeof(LdsTable) : 8];
+    LdsTable* lt = reinterpret_cast<LdsTable*>(lds_raw);   // unused without kLds
+    if (kLds) {
+        for (int s = threadIdx.x; s < kLdsSlots; s += kMapThreads) {
+            lt->keys[s] = kEmpty;
+#pragma unroll
+            for (int j = 0; j < 7; ++j) lt->vals[j][s] = 0;
+        }
+        __syncthreads();
+    }
+    const int f = blockIdx.y, tile = blockIdx.x;
+    const int i = (tile * kMapThreads + threadIdx.x) * kMapPx;
+    int dd[kMapPx];
+    youth_cloud::load_depth<kVec, kMapPx>(depth + (size_t)f * N, i, N, dd);
+    unsigned char cc[kMapPx * 3];
+    if (kRgb) {
+        youth_cloud::load_rgb<kVec, kMapPx>(rgb + ((size_t)f * N + i) * 3, i, N, cc);
+    } else {
+#pragma unroll
+        for (int k = 0; k < kMapPx * 3; ++k) cc[k] = 0;
+    }
+    // frame f's camera -> world pose, or the identity: one path, the same fma chains
+    float Tw[12] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f};
+    if (T_world) {
+#pragma unroll
+        for (int q = 0; q < 12; ++q) Tw[q] = T_world[(size_t)f * 12 + q];
+    }
+    Tally n;
+    Acc cur;
+    bool have = false;
+    // (u, v) of pixel i; a thread's pixels may wrap rows (any W >= 1)
+    int v = i / W;
+    int u = i - v * W;
+#pragma unroll
+    for (int k = 0; k < kMapPx; ++k) {
+        const int d = dd[k];
+        if (d > 0 && (max_depth == 0 || d <= max_depth)) {
+            float x, y, z;
+            youth_cloud::camera_point(d, u, v, K, x, y, z);
+            const float X = youth_cloud::world_axis(Tw, x, y, z);
+            const float Y = youth_cloud::world_axis(Tw + 4, x, y, z);
+            const float Z = youth_cloud::world_axis(Tw + 8, x, y, z);
+            uint32_t cx, cy, cz, qx, qy, qz;
+            const bool in = axis_key(X, vpm, cx, qx) && axis_key(Y, vpm, cy, qy) &&
+                            axis_key(Z, vpm, cz, qz);
+            if (in) {
+                const unsigned long long key =
+                    ((unsigned long long)cz << 42) | ((unsigned long long)cy << 21) | cx;
+                if (have && key != cur.key) {
+                    emit_run<kLds, kRgb>(t, lt, cur, n);
+                    have = false;
+                }
+                if (!have) {
+                    cur.key = key;
+                    cur.cnt = 0;
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) cur.q[j] = cur.c[j] = 0;
+                    have = true;
+                }
+                ++cur.cnt;
+                cur.q[0] += qx;
+                cur.q[1] += qy;
+                cur.q[2] += qz;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) cur.c[j] += cc[3 * k + j];
+            } else {
+                ++n.out_of_range;
+            }
+        }
+        ++u;
+        while (u >= W) {
+            u -= W;
+            ++v;
+        }
+    }
+    if (have) emit_run<kLds, kRgb>(t, lt, cur, n);
+    if (kLds) {
+        __syncthreads();
+        for (int s = threadIdx.x; s < kLdsSlots; s += kMapThreads) {
+            Acc a;
+            a.key = lt->keys[s];
+            if (a.key == kEmpty) continue;
+            a.cnt = lt->vals[0][s];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                a.q[j] = lt->vals[1 + j][s];
+                a.c[j] = lt->vals[4 + j][s];
+            }
+            global_add<kRgb>(t, a, n);
+        }
+    }
+    // the counters: one add per wave and counter that has something to add
+    const uint32_t sums[5] = {wave_sum_u32(n.integrated), wave_sum_u32(n.out_of_range),
+                              wave_sum_u32(n.dropped), wave_sum_u32(n.occupied),
+                              wave_sum_u32(n.direct)};
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < 5; ++j)
+            if (sums[j]) atomicAdd(&t.stats[j], (unsigned long long)sums[j]);
+    }
+}
+
+// Occupied slots -> records, in slot order of arrival (the host sorts).
+__global__ __launch_bounds__(kMapThreads) void k_map_extract(MapTable t, youth_voxel* __restrict__ out,
+                                                             uint32_t cap)
+{
+    const uint32_t s = blockIdx.x * kMapThreads + threadIdx.x;
+    if (s > t.mask) return;
+    const unsigned long long key = t.keys[s];
+    if (key == kEmpty) return;
+    const uint32_t at = (uint32_t)atomicAdd(&t.stats[kStExtracted], 1ull);
+    if (at >= cap) return;
+    const uint32_t* v = t.vals + (size_t)s * kValWords;
+    youth_voxel r;
+    r.ix = (int32_t)(key & 0x1fffff) - (1 << 20);
+    r.iy = (int32_t)((key >> 21) & 0x1fffff) - (1 << 20);
+    r.iz = (int32_t)((key >> 42) & 0x1fffff) - (1 << 20);
+    r.count = v[0];
+    for (int j = 0; j < 3; ++j) {
+        r.sum_q[j] = v[1 + j];
+        r.sum_c[j] = v[4 + j];
+    }
+    out[at] = r;
+}
+
+}  // namespace
+
+// =============================================================== host side ==
+
+static thread_local std::string g_map_error;
+
+__attribute__((format(printf, 2, 3))) static int map_error(int code, const char* fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    g_map_error = buf;
+    return code;
+}
+
+#define MAP_TRY(expr)                                                                    \
+    do {                                                                                 \
+        hipError_t e_ = (expr);                                                          \
+        if (e_ != hipSuccess)                                                            \
+            return map_error(YOUTH_EHIP, "%s (line %d)", hipGetErrorString(e_), __LINE__); \
+    } while (0)
+
+struct youth_map {
+    int device = 0;
+    float vpm = 0.0f;
+    long long cap = 0;
+    bool lds = true;      // YOUTH_MAP_LDS
+    int max_depth = 0;
+    hipStream_t stream = nullptr;
+    MapTable t{};
+    // host API staging (one frame) and the extraction buffer, grown on demand
+    int16_t* d_depth = nullptr;
+    uint8_t* d_rgb = nullptr;
+    size_t depth_cap = 0, rgb_cap = 0;
+    float* d_T = nullptr;   // [12]
+    youth_voxel* d_rec = nullptr;
+    size_t rec_cap = 0;
+};
+
+static void map_free(youth_map* m)
+{
+    if (!m) return;
+    if (hipSetDevice(m->device) == hipSuccess) {
+        if (m->stream) (void)hipStreamSynchronize(m->stream);
+        (void)hipFree(m->t.keys);
+        (void)hipFree(m->t.vals);
+        (void)hipFree(m->t.stats);
+        (void)hipFree(m->d_depth);
+        (void)hipFree(m->d_rgb);
+        (void)hipFree(m->d_T);
+        (void)hipFree(m->d_rec);
+        if (m->stream) (void)hipStreamDestroy(m->stream);
+    }
+    delete m;
+}
+
+// stats (host order) after the map's stream has drained
+static int map_read_stats(youth_map* m, unsigned long long* st)
+{
+    MAP_TRY(hipSetDevice(m->device));
+    MAP_TRY(hipMemcpyAsync(st, m->t.stats, kStN * sizeof(unsigned long long),
+                           hipMemcpyDeviceToHost, m->stream));
+    MAP_TRY(hipStreamSynchronize(m->stream));
+    return YOUTH_OK;
+}
+
+static double voxel_axis(int32_t i, uint32_t sum_q, uint32_t count, float vpm)
+{
+    return ((double)i + ((double)sum_q / (double)count + 0.5) / 256.0) / (double)vpm;
+}
+
+extern "C" {
+
+const char* youth_map_last_error(void) { return g_map_error.c_str(); }
+
+youth_map* youth_map_create(int device, float vpm, long long capacity_slots)
+{
+    if (!std::isfinite(vpm) || !(vpm > 0.0f) || capacity_slots < 1 ||
+        capacity_slots > (1LL << 28)) {
+        map_error(YOUTH_EINVAL,
+                  "youth_map_create: vpm %g, %lld slots (need finite vpm > 0, 1 <= slots <= 2^28)",
+                  (double)vpm, capacity_slots);
+        return nullptr;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        map_error(YOUTH_ENODEV, "youth_map_create: no HIP device visible");
+        return nullptr;
+    }
+    if (device < 0 || device >= ndev) {
+        map_error(YOUTH_EINVAL, "youth_map_create: device %d of %d", device, ndev);
+        return nullptr;
+    }
+    auto* m = new youth_map;
+    m->device = device;
+    m->vpm = vpm;
+    m->cap = 64;
+    while (m->cap < capacity_slots) m->cap <<= 1;
+    if (const char* e = getenv("YOUTH_MAP_LDS")) m->lds = atoi(e) != 0;
+    m->t.mask = (uint32_t)(m->cap - 1);
+    if (hipSetDevice(device) != hipSuccess ||
+        hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess ||
+        hipMalloc(&m->t.keys, (size_t)m->cap * sizeof(unsigned long long)) != hipSuccess ||
+        hipMalloc(&m->t.vals, (size_t)m->cap * kValWords * sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc(&m->t.stats, kStN * sizeof(unsigned long long)) != hipSuccess ||
+        hipMalloc(&m->d_T, 12 * sizeof(float)) != hipSuccess) {
+        map_error(YOUTH_ENOMEM, "youth_map_create: device allocation failed (%lld slots)", m->cap);
+        map_free(m);
+        return nullptr;
+    }
+    if (youth_map_clear(m) < 0) {
+        map_free(m);
+        return nullptr;
+    }
+    return m;
+}
+
+void youth_map_destroy(youth_map* m) { map_free(m); }
+
+int youth_map_clear(youth_map* m)
+{
+    if (!m) return map_error(YOUTH_EINVAL, "youth_map_clear: null map");
+    MAP_TRY(hipSetDevice(m->device));
+    MAP_TRY(hipMemsetAsync(m->t.keys, 0xff, (size_t)m->cap * sizeof(unsigned long long), m->stream));
+    MAP_TRY(hipMemsetAsync(m->t.vals, 0, (size_t)m->cap * kValWords * sizeof(uint32_t), m->stream));
+    MAP_TRY(hipMemsetAsync(m->t.stats, 0, kStN * sizeof(unsigned long long), m->stream));
+    return YOUTH_OK;
+}
+
+int youth_map_set_max_depth(youth_map* m, int max_depth)
+{
+    if (!m || max_depth < 0)
+        return map_error(YOUTH_EINVAL, "youth_map_set_max_depth: null map or negative depth");
+    m->max_depth = max_depth;
+    return YOUTH_OK;
+}
+
+int youth_map_integrate_device(youth_map* m, const int16_t* d_depth, const uint8_t* d_rgb,
+                               int n_frames, int W, int H, const youth_intrinsics* K,
+                               const float* d_T_world, void* stream)
+{
+    if (!m || !d_depth) return map_error(YOUTH_EINVAL, "youth_map_integrate_device: null argument");
+    if (n_frames < 0 || n_frames > 65535 || W < 1 || H < 1 || W > 16384 || H > 16384 ||
+        (long long)W * H > (1LL << 26))
+        return map_error(YOUTH_EINVAL,
+                         "youth_map_integrate_device: %d frames of %dx%d (need 0 <= frames <= 65535, "
+                         "1 <= W,H <= 16384, W*H <= 2^26)",
+                         n_frames, W, H);
+    if (n_frames == 0) return YOUTH_OK;
+    MAP_TRY(hipSetDevice(m->device));
+    const int N = W * H;
+    const int tile_px = kMapThreads * kMapPx;
+    const int tiles = (N + tile_px - 1) / tile_px;
+    CloudK k{570.3f, 570.3f, (float)(W / 2), (float)(H / 2), 1000.0f};   // the viewer's default
+    if (K) k = CloudK{K->fx, K->fy, K->cx, K->cy, K->depth_scale};
+    hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+    // vector loads: every frame base and thread offset aligned for the 16-byte
+    // depth word and the 8-byte colour words (as k_cloud_emit)
+    const bool vec = (N % kMapPx) == 0 && ((uintptr_t)d_depth % 16) == 0 &&
+                     (!d_rgb || ((uintptr_t)d_rgb % 8) == 0);
+    using Fn = void (*)(const int16_t*, const uint8_t*, int, int, CloudK, const float*, float, int,
+                        MapTable);
+    static const Fn fn[2][2][2] = {
+        {{k_map_integrate<false, false, false>, k_map_integrate<false, false, true>},
+         {k_map_integrate<false, true, false>, k_map_integrate<false, true, true>}},
+        {{k_map_integrate<true, false, false>, k_map_integrate<true, false, true>},
+         {k_map_integrate<true, true, false>, k_map_integrate<true, true, true>}}};
+    hipLaunchKernelGGL(fn[vec][m->lds][d_rgb != nullptr], dim3(tiles, n_frames), dim3(kMapThreads),
+                       0, s, d_depth, d_rgb, W, N, k, d_T_world, m->vpm, m->max_depth, m->t);
+    MAP_TRY(hipGetLastError());
+    return YOUTH_OK;
+}
+
+int youth_map_integrate_host(youth_map* m, const int16_t* depth, const uint8_t* rgb, int W, int H,
+                             const youth_intrinsics* K, const double* T_world)
+{
+    if (!m || !depth) return map_error(YOUTH_EINVAL, "youth_map_integrate_host: null argument");
+    if (W < 1 || H < 1 || W > 16384 || H > 16384 || (long long)W * H > (1LL << 26))
+        return map_error(YOUTH_EINVAL, "youth_map_integrate_host: %dx%d frame", W, H);
+    float T32[12];
+    if (T_world) {
+        for (int q = 0; q < 12; ++q) {
+            T32[q] = (float)T_world[q];
+            if (!std::isfinite(T_world[q]) || !std::isfinite(T32[q]))
+                return map_error(YOUTH_EINVAL, "youth_map_integrate_host: pose entry %d is not finite", q);
+        }
+    }
+    MAP_TRY(hipSetDevice(m->device));
+    const size_t N = (size_t)W * H;
+    if (m->depth_cap < N || (rgb && m->rgb_cap < N)) {
+        MAP_TRY(hipStreamSynchronize(m->stream));
+        if (m->depth_cap < N) {
+            (void)hipFree(m->d_depth);
+            m->d_depth = nullptr;
+            m->depth_cap = 0;
+            MAP_TRY(hipMalloc(&m->d_depth, N * sizeof(int16_t)));
+            m->depth_cap = N;
+        }
+        if (rgb && m->rgb_cap < N) {
+            (void)hipFree(m->d_rgb);
+            m->d_rgb = nullptr;
+            m->rgb_cap = 0;
+            MAP_TRY(hipMalloc(&m->d_rgb, N * 3));
+            m->rgb_cap = N;
+        }
+    }
+    MAP_TRY(hipMemcpyAsync(m->d_depth, depth, N * sizeof(int16_t), hipMemcpyHostToDevice, m->stream));
+    if (rgb) MAP_TRY(hipMemcpyAsync(m->d_rgb, rgb, N * 3, hipMemcpyHostToDevice, m->stream));
+    if (T_world)
+        MAP_TRY(hipMemcpyAsync(m->d_T, T32, sizeof(T32), hipMemcpyHostToDevice, m->stream));
+    const int rc = youth_map_integrate_device(m, m->d_depth, rgb ? m->d_rgb : nullptr, 1, W, H, K,
+                                              T_world ? m->d_T : nullptr, m->stream);
+    if (rc < 0) return rc;
+    // the staging buffers and the caller's frame are free again on return
+    MAP_TRY(hipStreamSynchronize(m->stream));
+    return YOUTH_OK;
+}
+
+long long youth_map_voxels(youth_map* m)
+{
+    if (!m) return map_error(YOUTH_EINVAL, "youth_map_voxels: null map");
+    unsigned long long st[kStN];
+    const int rc = map_read_stats(m, st);
+    return rc < 0 ? rc : (long long)st[kStOccupied];
+}
+
+int youth_map_stats(youth_map* m, struct youth_map_stats* out)
+{
+    if (!m || !out) return map_error(YOUTH_EINVAL, "youth_map_stats: null argument");
+    unsigned long long st[kStN];
+    const int rc = map_read_stats(m, st);
+    if (rc < 0) return rc;
+    out->integrated = st[kStIntegrated];
+    out->out_of_range = st[kStOutOfRange];
+    out->dropped = st[kStDropped];
+    out->occupied = st[kStOccupied];
+    out->direct = st[kStDirect];
+    out->capacity = (uint64_t)m->cap;
+    return YOUTH_OK;
+}
+
+int youth_map_extract(youth_map* m, youth_voxel* out, int cap)
+{
+    if (!m || cap < 0 || (!out && cap > 0))
+        return map_error(YOUTH_EINVAL, "youth_map_extract: null argument");
+    unsigned long long st[kStN];
+    int rc = map_read_stats(m, st);
+    if (rc < 0) return rc;
+    const size_t n = (size_t)st[kStOccupied];
+    if (n > (size_t)cap)
+        return map_error(YOUTH_EINVAL, "youth_map_extract: %zu voxels, room for %d", n, cap);
+    if (n == 0) return 0;
+    if (m->rec_cap < n) {
+        (void)hipFree(m->d_rec);
+        m->d_rec = nullptr;
+        m->rec_cap = 0;
+        MAP_TRY(hipMalloc(&m->d_rec, n * sizeof(youth_voxel)));
+        m->rec_cap = n;
+    }
+    MAP_TRY(hipMemsetAsync(m->t.stats + kStExtracted, 0, sizeof(unsigned long long), m->stream));
+    const unsigned blocks = (unsigned)((m->cap + kMapThreads - 1) / kMapThreads);
+    k_map_extract<<<blocks, kMapThreads, 0, m->stream>>>(m->t, m->d_rec, (uint32_t)n);
+    MAP_TRY(hipGetLastError());
+    MAP_TRY(hipMemcpyAsync(out, m->d_rec, n * sizeof(youth_voxel), hipMemcpyDeviceToHost, m->stream));
+    MAP_TRY(hipStreamSynchronize(m->stream));
+    // the slot order depends on which wave won an insert: never leaves here
+    std::sort(out, out + n, [](const youth_voxel& a, const youth_voxel& b) {
+        if (a.iz != b.iz) return a.iz < b.iz;
+        if (a.iy != b.iy) return a.iy < b.iy;
+        return a.ix < b.ix;
+    });
+    return (int)n;
+}
+
+int youth_map_sync(youth_map* m, void* stream)
+{
+    if (!m) return map_error(YOUTH_EINVAL, "youth_map_sync: null map");
+    MAP_TRY(hipSetDevice(m->device));
+    MAP_TRY(hipStreamSynchronize(stream ? (hipStream_t)stream : m->stream));
+    return YOUTH_OK;
+}
+
+int youth_map_points(const youth_voxel* vox, int n, float vpm, float* xyzrgb)
+{
+    if (n < 0 || (n > 0 && (!vox || !xyzrgb)) || !std::isfinite(vpm) || !(vpm > 0.0f))
+        return map_error(YOUTH_EINVAL, "youth_map_points: bad argument");
+    for (int k = 0; k < n; ++k) {
+        const youth_voxel& r = vox[k];
+        if (r.count == 0) return map_error(YOUTH_EINVAL, "youth_map_points: record %d is empty", k);
+        float* o = xyzrgb + (size_t)k * 6;
+        o[0] = (float)voxel_axis(r.ix, r.sum_q[0], r.count, vpm);
+        o[1] = (float)voxel_axis(r.iy, r.sum_q[1], r.count, vpm);
+        o[2] = (float)voxel_axis(r.iz, r.sum_q[2], r.count, vpm);
+        for (int j = 0; j < 3; ++j) o[3 + j] = (float)((double)r.sum_c[j] / (double)r.count / 255.0);
+    }
+    return YOUTH_OK;
+}
+
+int youth_map_write_ply(const char* path, const youth_voxel* vox, int n, float vpm)
+{
+    if (!path || n < 0 || (n > 0 && !vox) || !std::isfinite(vpm) || !(vpm > 0.0f))
+        return map_error(YOUTH_EINVAL, "youth_map_write_ply: bad argument");
+    for (int k = 0; k < n; ++k)
+        if (vox[k].count == 0)
+            return map_error(YOUTH_EINVAL, "youth_map_write_ply: record %d is empty", k);
+    FILE* f = fopen(path, "w");
+    if (!f) return map_error(YOUTH_EINVAL, "youth_map_write_ply: cannot open %s", path);
+    fprintf(f,
+            "ply\nformat ascii 1.0\ncomment youth_map voxels_per_metre %.9g\n"
+            "element vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+            "property uint count\nend_header\n",
+            (double)vpm, n);
+    for (int k = 0; k < n; ++k) {
+        const youth_voxel& r = vox[k];
+        unsigned c[3];
+        for (int j = 0; j < 3; ++j)   // the mean colour, rounded to nearest
+            c[j] = (unsigned)((2ull * r.sum_c[j] + r.count) / (2ull * r.count));
+        fprintf(f, "%.9g %.9g %.9g %u %u %u %u\n",
+                (double)(float)voxel_axis(r.ix, r.sum_q[0], r.count, vpm),
+                (double)(float)voxel_axis(r.iy, r.sum_q[1], r.count, vpm),
+                (double)(float)voxel_axis(r.iz, r.sum_q[2], r.count, vpm), c[0], c[1], c[2],
+                r.count);
+    }
+    const int ok = ferror(f) == 0;
+    if (fclose(f) != 0 || !ok) return map_error(YOUTH_EINVAL, "youth_map_write_ply: write to %s failed", path);
+    return YOUTH_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,229 @@
+"""Python host mirror of include/youth_map.h (ctypes, no torch): the voxel map,
+world-frame point fusion of tracked frames.
+
+``VoxelMap`` accumulates every integrated frame's world points in a sparse
+voxel grid on the GPU.  A voxel is a 40-byte record of integers
+(``VOXEL_DTYPE``); the map is the same bit pattern for any launch shape, frame
+order or split of the frames over calls.  ``points`` and ``write_ply`` are the
+derived float forms, computed on the host.
+
+Lives in libyouth_icp.so; no CPU fallback (a missing library raises, a
+machine without a HIP device raises ``IcpError(YOUTH_ENODEV)``).
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int16, c_longlong, c_uint8, \
+    c_uint64, c_void_p
+
+import numpy as np
+
+import youth_icp
+from youth_icp import YOUTH_EHIP, YOUTH_EINVAL, YOUTH_ENODEV, YOUTH_ENOMEM, IcpError, Intrinsics
+
+HEADER_PATH = os.path.join(os.path.dirname(youth_icp.HERE), "include", "youth_map.h")
+
+# youth_voxel
+VOXEL_DTYPE = np.dtype([("ix", "<i4"), ("iy", "<i4"), ("iz", "<i4"), ("count", "<u4"),
+                        ("sum_q", "<u4", (3,)), ("sum_c", "<u4", (3,))])
+assert VOXEL_DTYPE.itemsize == 40
+
+
+class MapStats(ctypes.Structure):
+    """struct youth_map_stats."""
+    _fields_ = [("integrated", c_uint64), ("out_of_range", c_uint64), ("dropped", c_uint64),
+                ("occupied", c_uint64), ("direct", c_uint64), ("capacity", c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+_bound = False
+
+
+def load_library() -> ctypes.CDLL:
+    global _bound
+    lib = youth_icp.load_library()
+    if not _bound:
+        PI = POINTER(Intrinsics)
+        lib.youth_map_create.restype = c_void_p
+        lib.youth_map_create.argtypes = [c_int, c_float, c_longlong]
+        lib.youth_map_destroy.restype = None
+        lib.youth_map_destroy.argtypes = [c_void_p]
+        lib.youth_map_last_error.restype = c_char_p
+        lib.youth_map_last_error.argtypes = []
+        lib.youth_map_clear.restype = c_int
+        lib.youth_map_clear.argtypes = [c_void_p]
+        lib.youth_map_set_max_depth.restype = c_int
+        lib.youth_map_set_max_depth.argtypes = [c_void_p, c_int]
+        lib.youth_map_integrate_device.restype = c_int
+        lib.youth_map_integrate_device.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                                   c_int, PI, c_void_p, c_void_p]
+        lib.youth_map_integrate_host.restype = c_int
+        lib.youth_map_integrate_host.argtypes = [c_void_p, POINTER(c_int16), POINTER(c_uint8),
+                                                 c_int, c_int, PI, POINTER(c_double)]
+        lib.youth_map_voxels.restype = c_longlong
+        lib.youth_map_voxels.argtypes = [c_void_p]
+        lib.youth_map_extract.restype = c_int
+        lib.youth_map_extract.argtypes = [c_void_p, c_void_p, c_int]
+        lib.youth_map_stats.restype = c_int
+        lib.youth_map_stats.argtypes = [c_void_p, POINTER(MapStats)]
+        lib.youth_map_sync.restype = c_int
+        lib.youth_map_sync.argtypes = [c_void_p, c_void_p]
+        lib.youth_map_points.restype = c_int
+        lib.youth_map_points.argtypes = [c_void_p, c_int, c_float, POINTER(c_float)]
+        lib.youth_map_write_ply.restype = c_int
+        lib.youth_map_write_ply.argtypes = [c_char_p, c_void_p, c_int, c_float]
+        lib.youth_slam_map_voxels.restype = c_longlong
+        lib.youth_slam_map_voxels.argtypes = []
+        lib.youth_slam_map_extract.restype = c_int
+        lib.youth_slam_map_extract.argtypes = [c_void_p, c_int]
+        lib.youth_slam_map_vpm.restype = c_float
+        lib.youth_slam_map_vpm.argtypes = []
+        _bound = True
+    return lib
+
+
+def _check(lib, code: int) -> int:
+    if code < 0:
+        raise IcpError(code, (lib.youth_map_last_error() or b"").decode())
+    return code
+
+
+def _records(voxels: np.ndarray) -> np.ndarray:
+    v = np.ascontiguousarray(voxels, VOXEL_DTYPE)
+    if v.ndim != 1:
+        raise ValueError("voxels: a 1-D array of VOXEL_DTYPE records")
+    return v
+
+
+def points(voxels: np.ndarray, vpm: float) -> np.ndarray:
+    """youth_map_points: records -> [n, 6] float32 {x, y, z, r, g, b} (host only)."""
+    lib = load_library()
+    v = _records(voxels)
+    out = np.empty((v.shape[0], 6), np.float32)
+    _check(lib, lib.youth_map_points(v.ctypes.data, v.shape[0], vpm,
+                                     out.ctypes.data_as(POINTER(c_float))))
+    return out
+
+
+def write_ply(path: str, voxels: np.ndarray, vpm: float) -> None:
+    """youth_map_write_ply: ASCII PLY, one vertex per record (host only)."""
+    lib = load_library()
+    v = _records(voxels)
+    _check(lib, lib.youth_map_write_ply(os.fsencode(path), v.ctypes.data, v.shape[0], vpm))
+
+
+def slam_map_voxels() -> int:
+    """Voxels in the SLAM module's map (0 when YOUTH_SLAM_MAP_VPM was not set)."""
+    return int(load_library().youth_slam_map_voxels())
+
+
+def slam_map_vpm() -> float:
+    return float(load_library().youth_slam_map_vpm())
+
+
+def slam_map_extract() -> np.ndarray:
+    """The SLAM module's map, sorted by (iz, iy, ix)."""
+    lib = load_library()
+    while True:
+        n = int(lib.youth_slam_map_voxels())
+        out = np.zeros(n, VOXEL_DTYPE)
+        m = lib.youth_slam_map_extract(out.ctypes.data, n)
+        if m == YOUTH_EINVAL and int(lib.youth_slam_map_voxels()) > n:
+            continue   # the worker integrated a frame in between
+        return out[:_check(lib, m)]
+
+
+class VoxelMap:
+    """A map of ``vpm`` voxels per metre with ``slots`` hash slots (rounded up
+    to a power of two) on HIP device ``device`` (youth_map_create)."""
+
+    def __init__(self, vpm: float, slots: int = 1 << 20, device: int = 0):
+        self._lib = load_library()
+        self.vpm = float(np.float32(vpm))
+        self._map = self._lib.youth_map_create(device, vpm, slots)
+        if not self._map:
+            msg = (self._lib.youth_map_last_error() or b"").decode()
+            code = (YOUTH_ENODEV if "no HIP device" in msg else
+                    YOUTH_ENOMEM if "allocation failed" in msg else
+                    YOUTH_EHIP if "(line " in msg else YOUTH_EINVAL)
+            raise IcpError(code, msg)
+
+    def close(self):
+        if getattr(self, "_map", None):
+            self._lib.youth_map_destroy(self._map)
+            self._map = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    def clear(self) -> None:
+        _check(self._lib, self._lib.youth_map_clear(self._map))
+
+    def set_max_depth(self, max_depth: int) -> None:
+        """Pixels deeper than max_depth (raw units) do not contribute; 0 = no gate."""
+        _check(self._lib, self._lib.youth_map_set_max_depth(self._map, max_depth))
+
+    def integrate(self, depth: np.ndarray, rgb: np.ndarray | None = None,
+                  K: Intrinsics | None = None, T_world: np.ndarray | None = None) -> None:
+        """One host frame with its camera -> world pose (4x4 or 3x4, fp64; None =
+        identity); synchronous."""
+        d = np.ascontiguousarray(depth, np.int16)
+        H, W = d.shape
+        c = None if rgb is None else np.ascontiguousarray(rgb, np.uint8).reshape(H, W, 3)
+        T = None
+        if T_world is not None:
+            T = np.zeros(16, np.float64)
+            T[:12] = np.asarray(T_world, np.float64).reshape(-1)[:12]
+            T[15] = 1.0
+        _check(self._lib, self._lib.youth_map_integrate_host(
+            self._map, d.ctypes.data_as(POINTER(c_int16)),
+            None if c is None else c.ctypes.data_as(POINTER(c_uint8)), W, H,
+            None if K is None else ctypes.byref(K),
+            None if T is None else T.ctypes.data_as(POINTER(c_double))))
+
+    def integrate_device(self, d_depth: int, d_rgb: int, n_frames: int, W: int, H: int,
+                         d_T_world: int = 0, K: Intrinsics | None = None,
+                         stream: int = 0) -> None:
+        """Device pointers (ints, e.g. torch data_ptr()); d_T_world = device
+        [n_frames][12] fp32 poses (0: identity); asynchronous on `stream` (0: the
+        map's own stream)."""
+        _check(self._lib, self._lib.youth_map_integrate_device(
+            self._map, d_depth or None, d_rgb or None, n_frames, W, H,
+            None if K is None else ctypes.byref(K), d_T_world or None, stream or None))
+
+    def voxels(self) -> int:
+        return int(_check(self._lib, self._lib.youth_map_voxels(self._map)))
+
+    def extract(self) -> np.ndarray:
+        """The map's records (VOXEL_DTYPE) sorted by (iz, iy, ix)."""
+        n = self.voxels()
+        out = np.zeros(n, VOXEL_DTYPE)
+        m = _check(self._lib, self._lib.youth_map_extract(self._map, out.ctypes.data, n))
+        return out[:m]
+
+    def points(self) -> np.ndarray:
+        """The derived float map: [n, 6] float32 {x, y, z, r, g, b}."""
+        return points(self.extract(), self.vpm)
+
+    def stats(self) -> dict:
+        st = MapStats()
+        _check(self._lib, self._lib.youth_map_stats(self._map, ctypes.byref(st)))
+        return st.as_dict()
+
+    def write_ply(self, path: str) -> int:
+        """The map as an ASCII PLY; returns the vertex count."""
+        v = self.extract()
+        write_ply(path, v, self.vpm)
+        return int(v.shape[0])
+
+    def sync(self, stream: int = 0) -> None:
+        _check(self._lib, self._lib.youth_map_sync(self._map, stream or None))
