@@ -518,6 +518,44 @@ int youth_icp_track_host_sequence(youth_icp_ctx* ctx, const int16_t* frames, int
 /* Forget the reference frame (next tracked frame starts a new sequence). */
 void youth_icp_track_reset(youth_icp_ctx* ctx);
 
+/* Edge-preserving depth filter in front of the tracker (youth_filter.h holds
+ * the definition and the stand-alone entry points).  Off by
+ * default: a context with the filter off allocates nothing for it, launches
+ * nothing for it and computes what it always did, bit for bit.
+ * When on, every frame the tracker family uploads (youth_icp_track_frame,
+ * _track_submit, _submit_batch, _submit_pinned, _track_host_sequence and both
+ * frames of _track_realign) lands in a raw staging slot on the device
+ * (allocated when the filter is first enabled) and is filtered into the
+ * context's depth slot, on the stream that uploaded it, before anything reads
+ * it.  The tracker's promises hold unchanged: batched = per-frame submission,
+ * track_realign reproduces the tracked pose, track_frame = submit + collect,
+ * each bit for bit.
+ * NOT affected: the device APIs (youth_icp_align_pairs_device,
+ * _align_sequence_device) read the caller's buffers in place, so the caller
+ * filters them with youth_depth_filter_device; the one-shot host batch API
+ * (youth_icp_align_batch, youth_icp_align_batch_multi) and the stage-level
+ * entry points (prepare / reduce / solve) take the frames as given.  The SLAM
+ * module's voxel map (youth_map.h) keeps integrating the raw frame.
+ *
+ * youth_icp_set_depth_filter: P = the parameters (1 <= t0 <= 255,
+ * 0 <= t2 <= 1000), NULL = off.  YOUTH_EINVAL for parameters out of range and
+ * while frames are in flight (youth_icp_track_pending > 0); the reference the
+ * tracker holds is kept either way.  youth_icp_get_depth_filter returns 1
+ * (on, *out filled when out != NULL) or 0 (off), or YOUTH_EINVAL.
+ * The environment variable YOUTH_ICP_DEPTH_FILTER, read by youth_icp_create,
+ * sets a new context's filter: "1" = the defaults (8, 96), "t0,t2" = those
+ * values, unset or "0" = off; on a malformed or out-of-range value the filter
+ * stays off and one line goes to stderr.  The SLAM.h drop-in's worker gets the
+ * filter this way. */
+#ifndef YOUTH_FILTER_PARAMS_DEFINED
+#define YOUTH_FILTER_PARAMS_DEFINED
+typedef struct youth_filter_params {
+    int t0, t2;
+} youth_filter_params;
+#endif
+int youth_icp_set_depth_filter(youth_icp_ctx* ctx, const youth_filter_params* P);
+int youth_icp_get_depth_filter(const youth_icp_ctx* ctx, youth_filter_params* out);
+
 /* --- Host utilities (no device needed) ----------------------------------- */
 
 /* Reads Camera.fx/fy/cx/cy/width/height and DepthMapFactor from an

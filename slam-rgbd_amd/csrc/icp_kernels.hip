@@ -2718,6 +2718,11 @@ struct youth_icp_ctx {
     long long trk_chained_frames = 0; // frames those launches aligned (youth_icp_track_chained_frames)
     long long trk_realigned[3] = {};  // youth_icp_track_realign: coop / persistent / still failed
     long long batch_realigned = 0;    // host batch API chunks realigned after a coop timeout
+    // depth filter in front of the tracker (youth_icp_set_depth_filter,
+    // YOUTH_ICP_DEPTH_FILTER): off = nothing allocated, nothing launched
+    bool flt_on = false;
+    youth_filter_params flt{8, 96};
+    int16_t* d_raw = nullptr;        // [trk_raw_slots][N] raw frames of one launch, filtered into d_depth
     int queues = 0;                  // k_icp work queues (YOUTH_ICP_QUEUES=1..8; 0: by batch size)
     int share = 1;                   // contexts launching k_icp concurrently (set_concurrency)
     int prep_xcd_map = 0;             // YOUTH_ICP_PREP_XCD_MAP=1: k_prep tiles contiguous per XCD (slower)
@@ -3536,7 +3541,7 @@ void youth_icp_destroy(youth_icp_ctx* c)
     void* bufs[] = {c->d_depth, c->d_rec,   c->d_xyz,      c->d_T64, c->d_T32,   c->d_status,
                     c->d_Tinit, c->d_stats, c->d_partials, c->d_neq, c->d_assoc, c->d_Tout,
                     c->d_flag,  c->d_arrivals, c->d_arr_it, c->d_epoch, c->d_head,
-                    c->d_coop,  c->d_status_out, c->d_coop_part};
+                    c->d_coop,  c->d_status_out, c->d_coop_part, c->d_raw};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (c->device >= 0 && c->device < 64) {
@@ -3553,6 +3558,11 @@ void youth_icp_destroy(youth_icp_ctx* c)
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->xfer) (void)hipStreamDestroy(c->xfer);
     delete c;
+}
+
+static bool filter_params_ok(const youth_filter_params* p)
+{
+    return p->t0 >= 1 && p->t0 <= 255 && p->t2 >= 0 && p->t2 <= 1000;
 }
 
 youth_icp_ctx* youth_icp_create(int device, int W, int H, int max_frames,
@@ -3719,6 +3729,23 @@ youth_icp_ctx* youth_icp_create(int device, int W, int H, int max_frames,
         const char* rd = getenv("YOUTH_ICP_REDUCE");
         if (rd && strcmp(rd, "lane32") == 0) c->reduce = YOUTH_REDUCE_LANE32;
         if (rd && strcmp(rd, "exact") == 0) c->reduce = YOUTH_REDUCE_EXACT;
+        // the tracker's depth filter: "1" (defaults), "t0,t2", unset / "0" (off)
+        const char* df = getenv("YOUTH_ICP_DEPTH_FILTER");
+        if (df && *df && strcmp(df, "0") != 0) {
+            youth_filter_params fp{8, 96};
+            char tail = 0;
+            const bool ok = strcmp(df, "1") == 0 ||
+                            (sscanf(df, "%d,%d%c", &fp.t0, &fp.t2, &tail) == 2 &&
+                             filter_params_ok(&fp));
+            if (ok) {
+                c->flt = fp;
+                c->flt_on = true;   // the raw staging comes with the first tracked frame
+            } else {
+                fprintf(stderr, "youth_icp: YOUTH_ICP_DEPTH_FILTER=%s ignored (want 1, 0 or t0,t2 "
+                                "with 1 <= t0 <= 255, 0 <= t2 <= 1000): the depth filter stays off\n",
+                        df);
+            }
+        }
     }
     if ((e = hipMalloc(&c->d_coop, 2 * kCoopSetWords * sizeof(unsigned))) != hipSuccess)
         return fail("hipMalloc coop", e);
@@ -4406,6 +4433,62 @@ static inline void trace_step(int step)
     if (youth_slam_trace_hook) youth_slam_trace_hook(YOUTH_SLAM_EV_SUBMIT_STEP, step);
 }
 
+// The depth filter's launcher (depth_filter.hip, youth_filter.h).  Weak: tools
+// that compile this file alone (tools/kbench ...) have no filter to turn on.
+__attribute__((weak)) int youth_depth_filter_device(int device, const int16_t* d_in, int16_t* d_out,
+                                                    int n_frames, int W, int H,
+                                                    const youth_filter_params* P, void* stream);
+__attribute__((weak)) const char* youth_depth_filter_last_error(void);
+
+// Raw staging of the filter: the frames of one launch (the transfer stream
+// pulls, then filters, launch after launch in order), two for a realign.
+static int trk_raw_slots(const youth_icp_ctx* c) { return std::max(2, trk_half(c)); }
+
+static int ensure_raw(youth_icp_ctx* c)
+{
+    if (c->d_raw) return YOUTH_OK;
+    if (!youth_depth_filter_device)
+        return set_error(YOUTH_EINVAL, "depth filter: not part of this build");
+    HIP_TRY(hipMalloc(&c->d_raw, (size_t)trk_raw_slots(c) * c->N * sizeof(int16_t)));
+    return YOUTH_OK;
+}
+
+// d_raw[0 .. n) -> dst[0 .. n) on `stream`
+static int track_filter(youth_icp_ctx* c, int n, int16_t* dst, hipStream_t stream)
+{
+    const int rc = youth_depth_filter_device(c->device, c->d_raw, dst, n, c->W, c->H, &c->flt, stream);
+    if (rc) return set_error(rc, "depth filter: %s", youth_depth_filter_last_error());
+    return YOUTH_OK;
+}
+
+int youth_icp_set_depth_filter(youth_icp_ctx* c, const youth_filter_params* P)
+{
+    if (!c) return set_error(YOUTH_EINVAL, "set_depth_filter: null context");
+    if (P && !filter_params_ok(P))
+        return set_error(YOUTH_EINVAL,
+                         "set_depth_filter: t0 %d, t2 %d (need 1 <= t0 <= 255, 0 <= t2 <= 1000)",
+                         P->t0, P->t2);
+    if (c->trk_n > 0)
+        return set_error(YOUTH_EINVAL, "set_depth_filter: %d frames in flight (collect them first)",
+                         c->trk_n);
+    if (P) {
+        int rc = bind_device(c);
+        if (rc) return rc;
+        rc = ensure_raw(c);
+        if (rc) return rc;
+        c->flt = *P;
+    }
+    c->flt_on = P != nullptr;
+    return YOUTH_OK;
+}
+
+int youth_icp_get_depth_filter(const youth_icp_ctx* c, youth_filter_params* out)
+{
+    if (!c) return set_error(YOUTH_EINVAL, "get_depth_filter: null context");
+    if (c->flt_on && out) *out = c->flt;
+    return c->flt_on ? 1 : 0;
+}
+
 static int track_submit_frames(youth_icp_ctx* c, const int16_t* depth, int m,
                                const double* T_init, const int16_t* const* frames = nullptr)
 {
@@ -4421,6 +4504,12 @@ static int track_submit_frames(youth_icp_ctx* c, const int16_t* depth, int m,
     for (int r = 0, k = 0; r < nrs && k < m; ++r)
         if (r != ref) rs[k++] = r;
     int qi[kCoopMaxChain];
+    if (c->flt_on) {   // enabled by the environment: the staging comes with the first frame
+        const int rc = ensure_raw(c);
+        if (rc) return rc;
+    }
+    // where the upload lands: the depth slots, or the filter's raw staging
+    int16_t* const land = c->flt_on ? c->d_raw : c->d_depth + (size_t)d0 * N;
     track_grow(c, c->trk_n + m);
     for (int i = 0; i < m; ++i) {
         qi[i] = (c->trk_head + c->trk_n + i) % c->trk_cap;
@@ -4478,13 +4567,17 @@ static int track_submit_frames(youth_icp_ctx* c, const int16_t* depth, int m,
         // the pull runs on the CUs the plan left free instead of slowing the
         // grid's barriers (youth_icp_track_set_batch)
         hipLaunchKernelGGL(k_pull_frames, dim3(wg, m), dim3(64), (unsigned)c->trk_pull_lds, xs, fp,
-                           c->d_depth + (size_t)d0 * N, (int)N, m);
+                           land, (int)N, m);
         HIP_TRY(hipGetLastError());
     } else {
         for (int i = 0; i < m; ++i)
-            HIP_TRY(hipMemcpyAsync(c->d_depth + (size_t)(d0 + i) * N,
+            HIP_TRY(hipMemcpyAsync(land + (size_t)i * N,
                                    frames ? frames[i] : c->trk[qi[i]].pinned, N * sizeof(int16_t),
                                    hipMemcpyHostToDevice, xs));
+    }
+    if (c->flt_on) {   // raw staging -> depth slots, before the H2D event
+        const int rc = track_filter(c, m, c->d_depth + (size_t)d0 * N, xs);
+        if (rc) return rc;
     }
     trace_step(3);
     if (xs != s) {
@@ -4719,8 +4812,17 @@ int youth_icp_track_realign(youth_icp_ctx* c, const int16_t* ref_depth, const in
     if (c->xfer) HIP_TRY(hipStreamSynchronize(c->xfer));
     const size_t N = c->N;
     const int rslot = c->track_ref == 0 ? 1 : 0;
-    HIP_TRY(hipMemcpyAsync(c->d_depth, depth, N * sizeof(int16_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->d_depth + N, ref_depth, N * sizeof(int16_t), hipMemcpyHostToDevice, s));
+    if (c->flt_on) {
+        rc = ensure_raw(c);
+        if (rc) return rc;
+    }
+    int16_t* const land = c->flt_on ? c->d_raw : c->d_depth;
+    HIP_TRY(hipMemcpyAsync(land, depth, N * sizeof(int16_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(land + N, ref_depth, N * sizeof(int16_t), hipMemcpyHostToDevice, s));
+    if (c->flt_on) {
+        rc = track_filter(c, 2, c->d_depth, s);
+        if (rc) return rc;
+    }
     const PrepJob job{c->d_depth + N, 1, rslot, true};
     c->coop_res_host = nullptr;
     int32_t st = YOUTH_STATUS_TIMEOUT;

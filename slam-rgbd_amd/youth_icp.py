@@ -70,6 +70,11 @@ class Params(ctypes.Structure):
     _fields_ = [("iters", c_int), ("dist_thresh", c_float)]
 
 
+class FilterParams(ctypes.Structure):
+    """youth_filter_params: the depth filter's gate, T = min(255, t0 + ((t2 * (c >> 4)^2) >> 16))."""
+    _fields_ = [("t0", c_int), ("t2", c_int)]
+
+
 _lib = None
 
 
@@ -151,6 +156,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "youth_icp_host_alloc": (P16, [c_size_t]),
         "youth_icp_host_free": (None, [P16]),
         "youth_icp_track_host_sequence": (c_int, [c_void_p, P16, c_int, PD, POINTER(c_int32)]),
+        "youth_icp_set_depth_filter": (c_int, [c_void_p, POINTER(FilterParams)]),
+        "youth_icp_get_depth_filter": (c_int, [c_void_p, POINTER(FilterParams)]),
         "youth_parse_camera_yaml": (c_int, [c_char_p, POINTER(Intrinsics), POINTER(c_int),
                                             POINTER(c_int)]),
         "youth_queue_create": (c_void_p, [c_int, c_int]),
@@ -460,6 +467,24 @@ class IcpContext:
         g = Lanes()
         _check(self._lib.youth_icp_get_lanes(self._ctx, ctypes.byref(g)))
         return g.as_tuple()
+
+    def set_depth_filter(self, t0: int | None = 8, t2: int = 96) -> None:
+        """Filter every frame the tracker family uploads with the edge-preserving
+        depth filter (youth_icp_set_depth_filter, include/youth_filter.h);
+        ``set_depth_filter(None)`` turns it off.  Refused while tracked frames
+        are in flight."""
+        if t0 is None:
+            _check(self._lib.youth_icp_set_depth_filter(self._ctx, None))
+        else:
+            _check(self._lib.youth_icp_set_depth_filter(
+                self._ctx, ctypes.byref(FilterParams(int(t0), int(t2)))))
+
+    @property
+    def depth_filter(self):
+        """(t0, t2) of the tracker's depth filter, or None when it is off."""
+        p = FilterParams()
+        on = _check(self._lib.youth_icp_get_depth_filter(self._ctx, ctypes.byref(p)))
+        return (p.t0, p.t2) if on else None
 
     def set_concurrency(self, contexts: int) -> int:
         """Declare `contexts` contexts aligning concurrently on this device
