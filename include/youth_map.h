@@ -73,8 +73,9 @@ typedef struct youth_map youth_map;
 /* A map of vpm voxels per metre (finite, > 0) with capacity_slots slots
  * (rounded up to a power of two; 64 <= slots <= 2^28) on HIP device `device`.
  * The environment variable YOUTH_MAP_LDS=0, read here, sends every point
- * straight to the global table (no per-workgroup aggregation).  NULL on
- * failure. */
+ * straight to the global table (no per-workgroup aggregation);
+ * YOUTH_MAP_RENDER_QUEUE=0, read here too, picks the render's other splat
+ * kernel (youth_map_render.h).  NULL on failure. */
 youth_map* youth_map_create(int device, float vpm, long long capacity_slots);
 void youth_map_destroy(youth_map* map);
 const char* youth_map_last_error(void);
@@ -147,5 +148,9 @@ float youth_slam_map_vpm(void);                           /* 0 when disabled */
 #ifdef __cplusplus
 }
 #endif
+
+/* Rendering the map into depth and colour frames from any pose (DESIGN.md
+ * §12): part of this interface, kept in a file of its own. */
+#include "youth_map_render.h"
 
 #endif /* YOUTH_MAP_H */

@@ -34,6 +34,7 @@
 
 #include "host_copy.h"
 #include "slam_map_hooks.h"
+#include "youth_map.h"
 #include "youth_icp.h"
 
 // ----------------------------------------------------------- event trace --
@@ -1053,6 +1054,20 @@ int youth_slam_wait_idle(int timeout_ms)
 }
 
 void youth_slam_set_map_hooks(const youth_slam_map_hooks* hooks) { g_map_hooks.store(hooks); }
+
+// youth_map_render.h: the module's map seen from a pose, by default the last
+// recorded one; under the trajectory lock, so no reset and no new pose falls
+// between reading the pose and the render
+int youth_slam_map_render(const struct youth_map_view* view, const youth_intrinsics* K,
+                          const double* T_world, int16_t* depth, uint8_t* rgb)
+{
+    const youth_slam_map_hooks* mh = g_map_hooks.load();
+    if (!mh || !view) return 0;
+    std::lock_guard<std::mutex> lk(g_slam_mu);
+    if (!T_world && g_traj.empty()) return 0;
+    const youth_intrinsics Kd = K ? *K : intrinsics_for(view->W, view->H);
+    return mh->render(view, &Kd, T_world ? T_world : g_traj.back().T, depth, rgb);
+}
 
 // recorded from inside the tracker (icp_kernels.hip: a submission's steps)
 void youth_slam_trace_hook(int kind, int arg) { trace(kind, arg); }

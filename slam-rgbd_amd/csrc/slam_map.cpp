@@ -8,7 +8,8 @@
 //
 // Threads: the worker integrates and clears (slam_api.cpp calls both under its
 // trajectory lock, so a reset cannot fall between a pose's recording and its
-// frame's integration); API threads start / stop the module, save and query.
+// frame's integration); API threads start / stop the module, save, query and
+// render (youth_slam_map_render holds the trajectory lock too).
 // Everything here runs under g_map_mu, always taken after the trajectory lock
 // where both are held.
 #include <stdio.h>
@@ -94,7 +95,20 @@ int map_save(const char* base)
     return youth_map_write_ply(path.c_str(), vox.data(), (int)vox.size(), vpm) == YOUTH_OK;
 }
 
-const youth_slam_map_hooks g_hooks = {map_start, map_stop, map_integrate, map_clear, map_save};
+int map_render(const struct youth_map_view* view, const youth_intrinsics* K, const double* T_world,
+               int16_t* depth, uint8_t* rgb)
+{
+    std::lock_guard<std::mutex> lk(g_map_mu);
+    if (!g_map) return 0;
+    if (youth_map_render_host(g_map, view, K, T_world, depth, rgb) < 0) {
+        fprintf(stderr, "youth_icp: map render failed: %s\n", youth_map_last_error());
+        return 0;
+    }
+    return 1;
+}
+
+const youth_slam_map_hooks g_hooks = {map_start, map_stop, map_integrate,
+                                      map_clear, map_save, map_render};
 
 struct Registrar {
     Registrar() { youth_slam_set_map_hooks(&g_hooks); }

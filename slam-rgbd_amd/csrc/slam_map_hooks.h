@@ -9,6 +9,8 @@
 
 #include "youth_icp.h"
 
+struct youth_map_view;   // youth_map_render.h
+
 struct youth_slam_map_hooks {
     // initSlamModule: read YOUTH_SLAM_MAP_* and create the map (or leave it off)
     void (*start)(int device);
@@ -22,6 +24,10 @@ struct youth_slam_map_hooks {
     void (*clear)(void);
     // saveSlamMap: <base>_map.ply; 1 written or map off, 0 failed
     int (*save)(const char* base);
+    // youth_slam_map_render, called under the trajectory lock with the pose
+    // resolved: 1 rendered, 0 map off or failed (outputs untouched)
+    int (*render)(const struct youth_map_view* view, const youth_intrinsics* K,
+                  const double* T_world, int16_t* depth, uint8_t* rgb);
 };
 
 extern "C" void youth_slam_set_map_hooks(const youth_slam_map_hooks* hooks);

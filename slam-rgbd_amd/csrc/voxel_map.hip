@@ -23,6 +23,9 @@
 //   k_map_extract    compacts the occupied slots into youth_voxel records
 //                    (slot order; the host sorts).
 //
+// The table's layout is shared with map_render.hip (map_table.h), which renders
+// the map from a pose and reaches a youth_map through youth_map_render_acquire.
+//
 // Atomics execute at the memory side and a hashed scatter is the one-lane-
 // per-row shape, the slowest there is; the rate known for this chip was
 // measured for float adds, the integer rate is not known.  The LDS table is
@@ -40,6 +43,7 @@
 #include <vector>
 
 #include "cloud_backproject.h"
+#include "map_table.h"
 #include "youth_map.h"
 
 namespace {
@@ -51,16 +55,7 @@ constexpr int kMapPx = 8;                       // pixels per thread
 constexpr int kLdsSlots = kMapThreads * kMapPx / 2;   // per-workgroup table: half the tile
 constexpr int kLdsProbe = 8;                    // LDS probe bound
 constexpr int kProbe = 128;                     // global probe bound
-constexpr unsigned long long kEmpty = ~0ull;    // a key is 63 bits: never all ones
-constexpr int kValWords = 8;                    // count, q[3], c[3], pad: 32 B per slot
 enum { kStIntegrated, kStOutOfRange, kStDropped, kStOccupied, kStDirect, kStExtracted, kStN };
-
-struct MapTable {
-    unsigned long long* keys;   // [cap]
-    uint32_t* vals;             // [cap][kValWords]
-    unsigned long long* stats;  // [kStN]
-    uint32_t mask;              // cap - 1
-};
 
 struct Acc {
     unsigned long long key;
@@ -297,9 +292,7 @@ __global__ __launch_bounds__(kMapThreads) void k_map_extract(MapTable t, youth_v
     if (at >= cap) return;
     const uint32_t* v = t.vals + (size_t)s * kValWords;
     youth_voxel r;
-    r.ix = (int32_t)(key & 0x1fffff) - (1 << 20);
-    r.iy = (int32_t)((key >> 21) & 0x1fffff) - (1 << 20);
-    r.iz = (int32_t)((key >> 42) & 0x1fffff) - (1 << 20);
+    key_cell(key, r.ix, r.iy, r.iz);
     r.count = v[0];
     for (int j = 0; j < 3; ++j) {
         r.sum_q[j] = v[1 + j];
@@ -314,7 +307,8 @@ __global__ __launch_bounds__(kMapThreads) void k_map_extract(MapTable t, youth_v
 
 static thread_local std::string g_map_error;
 
-__attribute__((format(printf, 2, 3))) static int map_error(int code, const char* fmt, ...)
+// (map_table.h: map_render.hip reports its errors through the same text)
+int youth_map_set_error(int code, const char* fmt, ...)
 {
     char buf[512];
     va_list ap;
@@ -324,6 +318,7 @@ __attribute__((format(printf, 2, 3))) static int map_error(int code, const char*
     g_map_error = buf;
     return code;
 }
+#define map_error youth_map_set_error
 
 #define MAP_TRY(expr)                                                                    \
     do {                                                                                 \
@@ -347,6 +342,10 @@ struct youth_map {
     float* d_T = nullptr;   // [12]
     youth_voxel* d_rec = nullptr;
     size_t rec_cap = 0;
+    // rendering (map_render.hip): the z-buffer, all ones between renders
+    bool render_queue = true;   // YOUTH_MAP_RENDER_QUEUE
+    unsigned long long* d_zbuf = nullptr;
+    size_t zbuf_cap = 0;        // bytes
 };
 
 static void map_free(youth_map* m)
@@ -361,6 +360,7 @@ static void map_free(youth_map* m)
         (void)hipFree(m->d_rgb);
         (void)hipFree(m->d_T);
         (void)hipFree(m->d_rec);
+        (void)hipFree(m->d_zbuf);
         if (m->stream) (void)hipStreamDestroy(m->stream);
     }
     delete m;
@@ -373,6 +373,61 @@ static int map_read_stats(youth_map* m, unsigned long long* st)
     MAP_TRY(hipMemcpyAsync(st, m->t.stats, kStN * sizeof(unsigned long long),
                            hipMemcpyDeviceToHost, m->stream));
     MAP_TRY(hipStreamSynchronize(m->stream));
+    return YOUTH_OK;
+}
+
+// the host API's staging buffers, grown to N pixels
+static int map_stage(youth_map* m, size_t N, bool rgb)
+{
+    if (m->depth_cap < N || (rgb && m->rgb_cap < N)) {
+        MAP_TRY(hipStreamSynchronize(m->stream));
+        if (m->depth_cap < N) {
+            (void)hipFree(m->d_depth);
+            m->d_depth = nullptr;
+            m->depth_cap = 0;
+            MAP_TRY(hipMalloc(&m->d_depth, N * sizeof(int16_t)));
+            m->depth_cap = N;
+        }
+        if (rgb && m->rgb_cap < N) {
+            (void)hipFree(m->d_rgb);
+            m->d_rgb = nullptr;
+            m->rgb_cap = 0;
+            MAP_TRY(hipMalloc(&m->d_rgb, N * 3));
+            m->rgb_cap = N;
+        }
+    }
+    return YOUTH_OK;
+}
+
+// map_table.h: the renderer's door to a map
+int youth_map_render_acquire(youth_map* m, size_t zbuf_bytes, size_t stage_px, bool stage_rgb,
+                             hipStream_t stream, youth_map_render_res* out)
+{
+    MAP_TRY(hipSetDevice(m->device));
+    if (m->zbuf_cap < zbuf_bytes) {
+        // no render may still be reading the old buffer: hipFree waits for the device
+        (void)hipFree(m->d_zbuf);
+        m->d_zbuf = nullptr;
+        m->zbuf_cap = 0;
+        MAP_TRY(hipMalloc(&m->d_zbuf, zbuf_bytes));
+        m->zbuf_cap = zbuf_bytes;
+        MAP_TRY(hipMemsetAsync(m->d_zbuf, 0xff, zbuf_bytes, stream ? stream : m->stream));
+    }
+    if (stage_px) {
+        const int rs = map_stage(m, stage_px, stage_rgb);
+        if (rs < 0) return rs;
+    }
+    out->device = m->device;
+    out->vpm = m->vpm;
+    out->queue = m->render_queue;
+    out->stream = m->stream;
+    out->keys = m->t.keys;
+    out->vals = m->t.vals;
+    out->mask = m->t.mask;
+    out->zbuf = m->d_zbuf;
+    out->depth = m->d_depth;
+    out->rgb = m->d_rgb;
+    out->V = m->d_T;
     return YOUTH_OK;
 }
 
@@ -409,6 +464,7 @@ youth_map* youth_map_create(int device, float vpm, long long capacity_slots)
     m->cap = 64;
     while (m->cap < capacity_slots) m->cap <<= 1;
     if (const char* e = getenv("YOUTH_MAP_LDS")) m->lds = atoi(e) != 0;
+    if (const char* e = getenv("YOUTH_MAP_RENDER_QUEUE")) m->render_queue = atoi(e) != 0;
     m->t.mask = (uint32_t)(m->cap - 1);
     if (hipSetDevice(device) != hipSuccess ||
         hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess ||
@@ -499,23 +555,8 @@ int youth_map_integrate_host(youth_map* m, const int16_t* depth, const uint8_t* 
     }
     MAP_TRY(hipSetDevice(m->device));
     const size_t N = (size_t)W * H;
-    if (m->depth_cap < N || (rgb && m->rgb_cap < N)) {
-        MAP_TRY(hipStreamSynchronize(m->stream));
-        if (m->depth_cap < N) {
-            (void)hipFree(m->d_depth);
-            m->d_depth = nullptr;
-            m->depth_cap = 0;
-            MAP_TRY(hipMalloc(&m->d_depth, N * sizeof(int16_t)));
-            m->depth_cap = N;
-        }
-        if (rgb && m->rgb_cap < N) {
-            (void)hipFree(m->d_rgb);
-            m->d_rgb = nullptr;
-            m->rgb_cap = 0;
-            MAP_TRY(hipMalloc(&m->d_rgb, N * 3));
-            m->rgb_cap = N;
-        }
-    }
+    const int rs = map_stage(m, N, rgb != nullptr);
+    if (rs < 0) return rs;
     MAP_TRY(hipMemcpyAsync(m->d_depth, depth, N * sizeof(int16_t), hipMemcpyHostToDevice, m->stream));
     if (rgb) MAP_TRY(hipMemcpyAsync(m->d_rgb, rgb, N * 3, hipMemcpyHostToDevice, m->stream));
     if (T_world)

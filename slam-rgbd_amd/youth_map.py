@@ -15,7 +15,7 @@ from __future__ import annotations
 import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int16, c_longlong, c_uint8, \
-    c_uint64, c_void_p
+    c_uint32, c_uint64, c_void_p
 
 import numpy as np
 
@@ -37,6 +37,11 @@ class MapStats(ctypes.Structure):
 
     def as_dict(self) -> dict:
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class MapView(ctypes.Structure):
+    """struct youth_map_view (youth_map_render.h); 0 = the default for the last two."""
+    _fields_ = [("W", c_int), ("H", c_int), ("max_splat", c_int), ("min_count", c_uint32)]
 
 
 _bound = False
@@ -81,6 +86,19 @@ def load_library() -> ctypes.CDLL:
         lib.youth_slam_map_extract.argtypes = [c_void_p, c_int]
         lib.youth_slam_map_vpm.restype = c_float
         lib.youth_slam_map_vpm.argtypes = []
+        # youth_map_render.h
+        PV = POINTER(MapView)
+        lib.youth_map_view_from_pose.restype = c_int
+        lib.youth_map_view_from_pose.argtypes = [POINTER(c_double), POINTER(c_float)]
+        lib.youth_map_render_device.restype = c_int
+        lib.youth_map_render_device.argtypes = [c_void_p, c_int, PV, PI, c_void_p, c_void_p,
+                                                c_void_p, c_void_p]
+        lib.youth_map_render_host.restype = c_int
+        lib.youth_map_render_host.argtypes = [c_void_p, PV, PI, POINTER(c_double),
+                                              POINTER(c_int16), POINTER(c_uint8)]
+        lib.youth_slam_map_render.restype = c_int
+        lib.youth_slam_map_render.argtypes = [PV, PI, POINTER(c_double), POINTER(c_int16),
+                                              POINTER(c_uint8)]
         _bound = True
     return lib
 
@@ -134,6 +152,43 @@ def slam_map_extract() -> np.ndarray:
         if m == YOUTH_EINVAL and int(lib.youth_slam_map_voxels()) > n:
             continue   # the worker integrated a frame in between
         return out[:_check(lib, m)]
+
+
+def _pose16(T_world) -> np.ndarray:
+    """A 4x4 or 3x4 pose as 16 fp64 values, last row 0 0 0 1."""
+    T = np.zeros(16, np.float64)
+    T[:12] = np.asarray(T_world, np.float64).reshape(-1)[:12]
+    T[15] = 1.0
+    return T
+
+
+def view_from_pose(T_world) -> np.ndarray:
+    """youth_map_view_from_pose: camera -> world (4x4 or 3x4 fp64) to the
+    world -> camera view matrix, [3, 4] float32 (host only)."""
+    lib = load_library()
+    T = _pose16(T_world)
+    V = np.zeros((3, 4), np.float32)
+    _check(lib, lib.youth_map_view_from_pose(T.ctypes.data_as(POINTER(c_double)),
+                                             V.ctypes.data_as(POINTER(c_float))))
+    return V
+
+
+def slam_map_render(W: int, H: int, T_world=None, K: Intrinsics | None = None, max_splat: int = 0,
+                    min_count: int = 0, want_rgb: bool = True):
+    """youth_slam_map_render: the SLAM module's map seen from T_world (None: the
+    last recorded pose) -> (depth [H, W] int16, rgb [H, W, 3] uint8 or None), or
+    None when the module keeps no map (or has no pose yet)."""
+    lib = load_library()
+    view = MapView(W, H, max_splat, min_count)
+    depth = np.zeros((H, W), np.int16)
+    rgb = np.zeros((H, W, 3), np.uint8) if want_rgb else None
+    T = None if T_world is None else _pose16(T_world)
+    ok = lib.youth_slam_map_render(
+        ctypes.byref(view), None if K is None else ctypes.byref(K),
+        None if T is None else T.ctypes.data_as(POINTER(c_double)),
+        depth.ctypes.data_as(POINTER(c_int16)),
+        None if rgb is None else rgb.ctypes.data_as(POINTER(c_uint8)))
+    return (depth, rgb) if ok == 1 else None
 
 
 class VoxelMap:
@@ -199,6 +254,33 @@ class VoxelMap:
         _check(self._lib, self._lib.youth_map_integrate_device(
             self._map, d_depth or None, d_rgb or None, n_frames, W, H,
             None if K is None else ctypes.byref(K), d_T_world or None, stream or None))
+
+    def render(self, T_world=None, W: int = 640, H: int = 480, K: Intrinsics | None = None,
+               max_splat: int = 0, min_count: int = 0, want_rgb: bool = True):
+        """The map seen from the camera -> world pose T_world (4x4 or 3x4 fp64;
+        None = identity) -> (depth [H, W] int16, rgb [H, W, 3] uint8 or None);
+        synchronous (youth_map_render_host)."""
+        view = MapView(W, H, max_splat, min_count)
+        depth = np.zeros((max(H, 0), max(W, 0)), np.int16)
+        rgb = np.zeros((max(H, 0), max(W, 0), 3), np.uint8) if want_rgb else None
+        T = None if T_world is None else _pose16(T_world)
+        _check(self._lib, self._lib.youth_map_render_host(
+            self._map, ctypes.byref(view), None if K is None else ctypes.byref(K),
+            None if T is None else T.ctypes.data_as(POINTER(c_double)),
+            depth.ctypes.data_as(POINTER(c_int16)),
+            None if rgb is None else rgb.ctypes.data_as(POINTER(c_uint8))))
+        return depth, rgb
+
+    def render_device(self, d_V: int, d_depth: int, d_rgb: int, n_views: int, W: int, H: int,
+                      K: Intrinsics | None = None, max_splat: int = 0, min_count: int = 0,
+                      stream: int = 0) -> None:
+        """Device pointers (ints): d_V [n_views][12] fp32 world -> camera,
+        d_depth [n][H][W] int16, d_rgb [n][H][W][3] uint8 (0: depth only);
+        asynchronous on `stream` (0: the map's own stream)."""
+        view = MapView(W, H, max_splat, min_count)
+        _check(self._lib, self._lib.youth_map_render_device(
+            self._map, n_views, ctypes.byref(view), None if K is None else ctypes.byref(K),
+            d_V or None, d_depth or None, d_rgb or None, stream or None))
 
     def voxels(self) -> int:
         return int(_check(self._lib, self._lib.youth_map_voxels(self._map)))
