@@ -1,0 +1,131 @@
+/*
+ * youth_rgbd.h — RGB-D alignment: a photometric term beside point-to-plane ICP.
+ *
+ * Depth alone leaves the pose undetermined where the scene is a near-frontal
+ * wall (a valley of the point-to-plane cost).  This path adds
+ * the colour frame the sensor delivers with every depth frame: each
+ * Gauss-Newton iteration sums the geometric term of youth_icp.h (spec a7/a8 in
+ * the survey arithmetic, unchanged) and a photometric term on 8-bit intensity
+ * into one 6x6 system.  Opt-in and beside the depth-only paths, which compute
+ * what they always did.  Definition: DESIGN.md §13; numpy restatement:
+ * tests/rgbd_truth.py.
+ *
+ *   intensity   Y = (77 R + 150 G + 29 B + 128) >> 8, uint8 [H][W]
+ *   target      gx = Y[v][u+1] - Y[v][u-1], gy = Y[v+1][u] - Y[v-1][u],
+ *               photometric-valid iff 1 <= u <= W-2 and 1 <= v <= H-2
+ *   per pixel   (accepted by the geometric gate, target pixel (u', v') valid)
+ *               It = Y_t[v'][u'] + 0.5 (gx du + gy dv),  du = uf - u', dv = vf - v'
+ *               rp = (It - Y_s[v][u]) w,  w = lambda / 255
+ *               h  = (gx kx / P'z, gy ky / P'z, -(hx P'x + hy P'y) / P'z),
+ *               kx = 0.5 w fx, ky = 0.5 w fy;  Jp = [P' x h, h]
+ *   sums        A = sum J J^T + sum Jp Jp^T, b = sum J r + sum Jp rp (exact fp64
+ *               products), then the solve and update of youth_icp.h (a10)
+ *
+ * Plain C99; streams travel as void*; return codes are youth_icp.h's YOUTH_OK /
+ * YOUTH_E*.  Lives in libyouth_icp.so.
+ */
+#ifndef YOUTH_RGBD_H
+#define YOUTH_RGBD_H
+
+#include <stdint.h>
+
+#include "youth_icp.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* fp64 values in one record of the joint normal equations:
+ * [0..20] upper triangle of A, [21..26] b, [27] sum r^2 and [28] count of the
+ * geometric term, [29] sum rp^2 and [30] count of the photometric term.  With
+ * lambda = 0 the first YOUTH_NEQ values are the depth-only record. */
+#define YOUTH_RGBD_NEQ 31
+
+typedef struct youth_rgbd_params {
+    int   iters;        /* fixed Gauss-Newton iterations, no early exit */
+    float dist_thresh;  /* the geometric gate |P' - P_t| < dist_thresh (m) */
+    float lambda;       /* metres of geometric residual per unit of intensity in [0, 1] */
+} youth_rgbd_params;
+
+/* 10 iterations, dist_thresh 0.10, lambda 0.1. */
+youth_rgbd_params youth_rgbd_default_params(void);
+
+typedef struct youth_rgbd_ctx youth_rgbd_ctx;
+
+/* Human-readable text of the last error on this thread ("" if none). */
+const char* youth_rgbd_last_error(void);
+
+/* Device workspace for max_frames pairs of W x H (the limits of
+ * youth_icp_create: 3 <= W, H <= 16384, W*H <= 2^26, max_frames >= 2).  K NULL:
+ * the viewer's intrinsics; params NULL: the defaults.  iters >= 0, dist_thresh
+ * and lambda finite, dist_thresh > 0, lambda >= 0 (NULL and YOUTH_EINVAL in
+ * youth_rgbd_last_error otherwise; YOUTH_ENODEV without a device).  The
+ * environment variable YOUTH_RGBD_CHUNKS=k, read here, makes every iteration
+ * launch k workgroups per pair (at most one per 1024 pixels) instead of the
+ * planned number: a test knob, results move in the last bits of the sums only. */
+youth_rgbd_ctx* youth_rgbd_create(int device, int W, int H, int max_frames,
+                                  const youth_intrinsics* K, const youth_rgbd_params* params);
+void youth_rgbd_destroy(youth_rgbd_ctx* ctx);
+
+/* RGB [n][H][W][3] -> intensity [n][H][W], both uint8 on `device`;
+ * asynchronous on `stream`.  0 <= n <= 65535. */
+int youth_rgbd_luma_device(int device, const uint8_t* d_rgb, uint8_t* d_gray, int n, int W, int H,
+                           void* stream);
+
+/* Device-resident align of n_pairs pairs with the semantics of
+ * youth_icp_align_pairs_device: depth [n_pairs][H][W] int16, intensity
+ * [n_pairs][H][W] uint8, all on the device and alive until the align has
+ * completed on `stream`; T_init nullable HOST [n_pairs][16] fp64 (finite);
+ * d_T_out nullable DEVICE [n_pairs][16] fp32; asynchronous.  n_pairs <=
+ * max_frames.  One launch per iteration plus the target preps. */
+int youth_rgbd_align_pairs_device(youth_rgbd_ctx* ctx, const int16_t* d_src_depth,
+                                  const uint8_t* d_src_gray, const int16_t* d_dst_depth,
+                                  const uint8_t* d_dst_gray, int n_pairs, const double* T_init,
+                                  float* d_T_out, void* stream);
+
+/* Streamed sequence: the n_frames - 1 relative poses T_k (P_k = T_k P_{k+1}) of
+ * d_depth / d_gray [n_frames][H][W]; every frame is prepped once.
+ * 2 <= n_frames <= max_frames + 1. */
+int youth_rgbd_align_sequence_device(youth_rgbd_ctx* ctx, const int16_t* d_depth,
+                                     const uint8_t* d_gray, int n_frames, float* d_T_out,
+                                     void* stream);
+
+/* Block until the context's last enqueued work on `stream` is done. */
+int youth_rgbd_sync(youth_rgbd_ctx* ctx, void* stream);
+
+/* Results of the last align (synchronises): T64 [n][16] fp64, T32 [n][16] fp32,
+ * status [n] YOUTH_STATUS_* bits; each nullable. */
+int youth_rgbd_get_poses(youth_rgbd_ctx* ctx, int n, double* T64, float* T32, int32_t* status);
+
+/* Per iteration of the last align, the record's values 27..30:
+ * stats [n][iters][4] = sum r^2, geometric count, sum rp^2, photometric count. */
+int youth_rgbd_get_stats(youth_rgbd_ctx* ctx, int n, int iters, double* stats);
+
+/* --- Stage-level entry points (validation / parity tests) --------------- */
+
+/* The target preparation alone: n frames of `channels` = 3 (RGB [n][H][W][3])
+ * or 1 (intensity [n][H][W]) on the device -> d_gray (nullable) [n][H][W] uint8
+ * and d_photo (nullable) [n][H*W] packed words: bits 0..7 Y, 8..16 gx + 255,
+ * 17..25 gy + 255, bit 31 the valid bit (gx = gy = 0 where it is clear).
+ * Asynchronous on `stream`. */
+int youth_rgbd_prep_device(youth_rgbd_ctx* ctx, const uint8_t* d_in, int channels, int n,
+                           uint8_t* d_gray, uint32_t* d_photo, void* stream);
+
+/* One association + reduction pass for one pair of HOST frames at a given fp32
+ * pose T12 (3x4 row-major): neq31 [YOUTH_RGBD_NEQ].  Synchronous. */
+int youth_rgbd_reduce_host(youth_rgbd_ctx* ctx, const int16_t* src_depth, const uint8_t* src_gray,
+                           const int16_t* dst_depth, const uint8_t* dst_gray, const float* T12,
+                           double* neq31);
+
+/* Host frames in (depth [n_frames][H][W] int16, rgb [n_frames][H][W][3]),
+ * relative poses out: T_rel [n_frames - 1][16] fp64 (P_k = T_rel[k] P_{k+1}) and
+ * status [n_frames - 1] (nullable).  Upload, intensity, the sequence align and
+ * the download; synchronous.  Returns n_frames - 1 or a negative YOUTH_E* code. */
+int youth_rgbd_track_host_sequence(youth_rgbd_ctx* ctx, const int16_t* depth, const uint8_t* rgb,
+                                   int n_frames, double* T_rel, int32_t* status);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* YOUTH_RGBD_H */

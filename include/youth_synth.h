@@ -64,6 +64,27 @@ void youth_synth_sequence(uint64_t seed, int first_frame, int n, int W, int H,
                           const youth_intrinsics* K, int flags, int16_t* frames,
                           double* T_wc);
 
+/* Colour beside the depth: the same arguments plus rgb, uint8 [n][H][W][3] in
+ * the viewer's layout.  The depth written is byte for byte what the function
+ * without _rgb writes for the same arguments.  Colour is a procedural texture
+ * of the ray's fp64 world hit point p = (x, y, z), taken before noise and also
+ * where the depth is a hole or out of range (a colour camera has no holes); a
+ * ray that hits nothing gives 0.  It depends on neither the noise seed nor the
+ * flags.  With bump(t) = 4 f (1 - f), f = t - floor(t), and
+ * b4 = bump((x + y + z) / 0.9):
+ *   R = floor(32 + 192 (0.5 bump((x + 0.3 z) / 0.23) + 0.5 b4) + 0.5)
+ *   G likewise with bump((y - 0.4 x) / 0.31), B with bump((z + 0.5 y) / 0.27).
+ * youth_synth_pairs_rgb: src_rgb / dst_rgb [n][H][W][3]. */
+void youth_synth_render_rgb(const double T_wc[16], int W, int H,
+                            const youth_intrinsics* K, uint64_t noise_seed,
+                            int flags, int16_t* depth, uint8_t* rgb);
+void youth_synth_pairs_rgb(uint64_t base_seed, int first_index, int n, int W, int H,
+                           const youth_intrinsics* K, int flags, int16_t* src,
+                           int16_t* dst, double* T_gt, uint8_t* src_rgb, uint8_t* dst_rgb);
+void youth_synth_sequence_rgb(uint64_t seed, int first_frame, int n, int W, int H,
+                              const youth_intrinsics* K, int flags, int16_t* frames,
+                              double* T_wc, uint8_t* rgb);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4978,3 +4978,8 @@ void youth_icp_track_reset(youth_icp_ctx* c)
 }
 
 }  // extern "C"
+
+// The RGB-D alignment (include/youth_rgbd.h): k_rgbd_prep,
+// k_rgbd_reduce and their host side, on this file's device code and context.
+#include "youth_rgbd.h"
+#include "rgbd_align.inc"

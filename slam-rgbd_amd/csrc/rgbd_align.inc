@@ -1,0 +1,846 @@
+// rgbd_align.inc — RGB-D alignment on gfx950 (C-ABI: include/youth_rgbd.h;
+// definition: DESIGN.md §13).  The tail of icp_kernels.hip: it shares that
+// file's device code (back-projection, lane masks, the wave reduce-scatter's
+// stages, the a10 solve) and its context, and leaves every kernel above as it
+// is.
+//
+//   k_rgbd_prep    once per target frame: RGB -> Y (or a grey copy) and one
+//                  32-bit word per pixel {Y, gx + 255, gy + 255, valid}.  Four
+//                  pixels of a row per thread.  Not LDS-staged: the rows above
+//                  and below and the two columns beside the four are read from
+//                  global memory again and come from cache.  The geometric
+//                  records {z, nx, ny, nz} come from k_prep, unchanged.
+//   k_rgbd_reduce  one launch per iteration, modelled on k_reduce with its
+//                  fused solve: a workgroup takes a chunk of a pair's source
+//                  pixels, four per lane and step, branch-free under lane
+//                  masks; the 16-byte record and the 4-byte photometric word of
+//                  a lane's four pixels are gathered back to back; exact fp64
+//                  products into 29 per-lane sums and two wave counts; wave
+//                  reduce-scatter, one partial row [pair][chunk][31] and an
+//                  arrival ticket; the pair's last workgroup adds the rows in a
+//                  fixed order and runs the a10 solve and update.
+//                  23 B/px/iteration: depth 2, Y 1, record 16, word 4.
+//
+// Always the survey arithmetic of a7/a8 (no FMA, IEEE division) and the exact
+// reduction of a9, whatever the ICP context's spec and reduce modes are.
+
+namespace {
+
+constexpr int kRgbdNeq = YOUTH_RGBD_NEQ;
+constexpr int kRgbdStride = 32;          // doubles per partial row (31 + a pad)
+constexpr int kRgbdPrepThreads = 256;
+constexpr unsigned kPhotoValid = 0x80000000u;
+
+// host constants of §13: w = lambda / 255, kx = (0.5 w) fx, ky = (0.5 w) fy
+struct PhotoK {
+    float w, kx, ky;
+};
+
+__device__ __forceinline__ unsigned luma8(unsigned r, unsigned g, unsigned b)
+{
+    return (77u * r + 150u * g + 29u * b + 128u) >> 8;
+}
+
+// Y of pixel (row, x) of a frame of kCh channels; the caller keeps it inside
+template <int kCh>
+__device__ __forceinline__ unsigned load_y1(const uint8_t* __restrict__ f, int row, int x, int W)
+{
+    const uint8_t* p = f + ((size_t)row * W + x) * kCh;
+    return kCh == 1 ? (unsigned)p[0] : luma8(p[0], p[1], p[2]);
+}
+
+// Y of pixels (row, x0 .. x0 + 3).  kVec: W % 4 == 0 and a 4-byte aligned
+// frame base, so the four pixels lie in the row and move as one (grey) or
+// three (RGB) aligned words; else each pixel alone, columns clamped to W - 1.
+template <int kCh, bool kVec>
+__device__ __forceinline__ void load_y4(const uint8_t* __restrict__ f, int row, int x0, int W,
+                                        unsigned y[4])
+{
+    if (kVec) {
+        const unsigned* q = reinterpret_cast<const unsigned*>(f + ((size_t)row * W + x0) * kCh);
+        if (kCh == 1) {
+            const unsigned a = q[0];
+            y[0] = a & 255u;
+            y[1] = (a >> 8) & 255u;
+            y[2] = (a >> 16) & 255u;
+            y[3] = a >> 24;
+        } else {
+            const unsigned a = q[0], b = q[1], c = q[2];
+            y[0] = luma8(a & 255u, (a >> 8) & 255u, (a >> 16) & 255u);
+            y[1] = luma8(a >> 24, b & 255u, (b >> 8) & 255u);
+            y[2] = luma8((b >> 16) & 255u, b >> 24, c & 255u);
+            y[3] = luma8((c >> 8) & 255u, (c >> 16) & 255u, c >> 24);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) y[k] = load_y1<kCh>(f, row, min(x0 + k, W - 1), W);
+    }
+}
+
+// grid (ceil(ceil(W / 4) H / 256), frames).  gray / photo may be null.
+template <int kCh, bool kVec>
+__global__ __launch_bounds__(kRgbdPrepThreads) void k_rgbd_prep(const uint8_t* __restrict__ in,
+                                                                uint8_t* __restrict__ gray,
+                                                                unsigned* __restrict__ photo, int W,
+                                                                int H)
+{
+    const int gpr = (W + 3) >> 2;  // groups of four pixels per row
+    const int idx = blockIdx.x * kRgbdPrepThreads + threadIdx.x;
+    if (idx >= gpr * H) return;
+    const int v = idx / gpr;
+    const int x0 = (idx - v * gpr) * 4;
+    const size_t N = (size_t)W * H;
+    const uint8_t* __restrict__ f = in + (size_t)blockIdx.y * N * kCh;
+
+    // rows and columns clamped into the frame: a clamped read feeds only a
+    // border pixel, whose gradient is defined as 0
+    unsigned yc[4], yu[4], yd[4];
+    load_y4<kCh, kVec>(f, v, x0, W, yc);
+    load_y4<kCh, kVec>(f, max(v - 1, 0), x0, W, yu);
+    load_y4<kCh, kVec>(f, min(v + 1, H - 1), x0, W, yd);
+    const unsigned row[6] = {load_y1<kCh>(f, v, max(x0 - 1, 0), W), yc[0], yc[1], yc[2], yc[3],
+                             load_y1<kCh>(f, v, min(x0 + 4, W - 1), W)};
+    const bool vin = v >= 1 && v <= H - 2;
+    unsigned word[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int u = x0 + k;
+        const bool valid = vin && u >= 1 && u <= W - 2;
+        const int gx = valid ? (int)row[k + 2] - (int)row[k] : 0;
+        const int gy = valid ? (int)yd[k] - (int)yu[k] : 0;
+        word[k] = yc[k] | ((unsigned)(gx + 255) << 8) | ((unsigned)(gy + 255) << 17) |
+                  (valid ? kPhotoValid : 0u);
+    }
+    const size_t o = (size_t)blockIdx.y * N + (size_t)v * W + x0;
+    if (kVec) {
+        if (gray)
+            *reinterpret_cast<unsigned*>(gray + o) =
+                yc[0] | (yc[1] << 8) | (yc[2] << 16) | (yc[3] << 24);
+        if (photo) *reinterpret_cast<uint4*>(photo + o) = uint4{word[0], word[1], word[2], word[3]};
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (x0 + k < W) {
+                if (gray) gray[o + k] = (uint8_t)yc[k];
+                if (photo) photo[o + k] = word[k];
+            }
+    }
+}
+
+// Spec a7 in the survey arithmetic, as xform_project<kSpecSurvey>, handing out
+// the sub-pixel coordinates uf = (fx P'x) / P'z + cx and vf as well.
+__device__ __forceinline__ void rgbd_project(const float* T, float sx, float sy, float sz,
+                                             const Intr& K, int W, int H, float& qx, float& qy,
+                                             float& qz, float& uf, float& vf, float& fu, float& fv,
+                                             LaneMask& inm, int& j)
+{
+    qx = ((T[0] * sx + T[1] * sy) + T[2] * sz) + T[3];
+    qy = ((T[4] * sx + T[5] * sy) + T[6] * sz) + T[7];
+    qz = ((T[8] * sx + T[9] * sy) + T[10] * sz) + T[11];
+    const float nu = K.fx * qx, nv = K.fy * qy;
+    const LaneMask sok = mask_gt(sz, 0.0f);
+    const LaneMask dok = mask_ule(__float_as_uint(qz) - 0x21800000u, 0x5d800000u - 0x21800000u);
+    const float r = proj_recip(qz);
+    float pu = proj_quot(nu, qz, r);
+    float pv = proj_quot(nv, qz, r);
+    LaneMask vz = sok & dok;
+    const LaneMask slow = sok & ~dok;
+    if (__builtin_expect(slow != 0, 0)) {  // wave-uniform
+        const LaneMask qpos = mask_gt(qz, 0.0f);
+        if (lane_in(slow)) {
+            const float den = lane_in(qpos) ? qz : 1.0f;
+            pu = nu / den;
+            pv = nv / den;
+        }
+        vz |= slow & qpos;
+    }
+    uf = pu + K.cx;
+    vf = pv + K.cy;
+    const int iu = floor_i32(uf + 0.5f);
+    const int iv = floor_i32(vf + 0.5f);
+    const unsigned ivc = min((unsigned)iv, (unsigned)H);
+    inm = vz & mask_ult((unsigned)iu, (unsigned)W);
+    fu = (float)iu;
+    fv = (float)iv;
+    j = (int)(__umul24(ivc, (unsigned)W) + (unsigned)iu);
+}
+
+// a7's gate and a8 as match_accumulate<kSpecSurvey, kFast, true>, then §13's
+// photometric term where the gate accepted the pixel and the target's word is
+// valid.  acc: [0..26] A and b of both terms, [27] sum r^2, [29] sum rp^2.
+template <bool kFast>
+__device__ __forceinline__ void rgbd_accumulate(float qx, float qy, float qz, f4v t, unsigned pw,
+                                                float ys, float uf, float vf, float fu, float fv,
+                                                LaneMask inm, const Intr& K, const FastK& F,
+                                                float thr2, const PhotoK& pk, double* acc,
+                                                int& cnt_g, int& cnt_p)
+{
+    const float tz = t.x;
+    const float tx = bp_div<kFast>((fu - K.cx) * tz, K.fx, F.hfx, F.lfx);
+    const float ty = bp_div<kFast>((fv - K.cy) * tz, K.fy, F.hfy, F.lfy);
+    const float dx = qx - tx, dy = qy - ty, dz = qz - tz;
+    const float d2 = (dx * dx + dy * dy) + dz * dz;
+    const LaneMask okm = inm & mask_gt(tz, 0.0f) & mask_lt(d2, thr2);
+    const LaneMask pvm = okm & mask_ult(~kPhotoValid, pw);
+    if (lane_in(okm)) {
+        const float n0 = t.y, n1 = t.z, n2 = t.w;
+        const float r = (n0 * dx + n1 * dy) + n2 * dz;
+        const float Jf[6] = {qy * n2 - qz * n1, qz * n0 - qx * n2, qx * n1 - qy * n0, n0, n1, n2};
+        int k = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int bb = a; bb < 6; ++bb) {
+                acc[k] = fma((double)Jf[a], (double)Jf[bb], acc[k]);
+                ++k;
+            }
+#pragma unroll
+        for (int a = 0; a < 6; ++a) acc[21 + a] = fma((double)Jf[a], (double)r, acc[21 + a]);
+        acc[27] = fma((double)r, (double)r, acc[27]);
+    }
+    if (lane_in(pvm)) {
+        const float yt = (float)(pw & 255u);
+        const float gx = (float)((int)((pw >> 8) & 511u) - 255);
+        const float gy = (float)((int)((pw >> 17) & 511u) - 255);
+        const float du = uf - fu, dv = vf - fv;
+        const float it = yt + 0.5f * (gx * du + gy * dv);
+        const float rp = (it - ys) * pk.w;
+        // IEEE divisions, as the definition words them
+        const float hx = (gx * pk.kx) / qz;
+        const float hy = (gy * pk.ky) / qz;
+        const float hz = -((hx * qx + hy * qy) / qz);
+        const float Jp[6] = {qy * hz - qz * hy, qz * hx - qx * hz, qx * hy - qy * hx, hx, hy, hz};
+        int k = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int bb = a; bb < 6; ++bb) {
+                acc[k] = fma((double)Jp[a], (double)Jp[bb], acc[k]);
+                ++k;
+            }
+#pragma unroll
+        for (int a = 0; a < 6; ++a) acc[21 + a] = fma((double)Jp[a], (double)rp, acc[21 + a]);
+        acc[29] = fma((double)rp, (double)rp, acc[29]);
+    }
+    // both counts per wave on the scalar unit
+    cnt_g += __builtin_popcountll(okm);
+    cnt_p += __builtin_popcountll(pvm);
+}
+
+// wave_reduce_scatter for the 31 values of the joint record: the same stages,
+// partners and add order; lanes 2q and 2q + 1 end with the wave total of value q.
+__device__ __forceinline__ void rgbd_wave_reduce_scatter(const double* acc, int lane, double& total)
+{
+    double v[32];
+#pragma unroll
+    for (int q = 0; q < 32; ++q) v[q] = q < kRgbdNeq ? acc[q] : 0.0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {  // m = 32
+        const auto l = __builtin_amdgcn_permlane32_swap(lo32(v[q]), lo32(v[q + 16]), false, false);
+        const auto h = __builtin_amdgcn_permlane32_swap(hi32(v[q]), hi32(v[q + 16]), false, false);
+        v[q] = join64(l[0], h[0]) + join64(l[1], h[1]);
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {  // m = 16
+        const auto l = __builtin_amdgcn_permlane16_swap(lo32(v[q]), lo32(v[q + 8]), false, false);
+        const auto h = __builtin_amdgcn_permlane16_swap(hi32(v[q]), hi32(v[q + 8]), false, false);
+        v[q] = join64(l[0], h[0]) + join64(l[1], h[1]);
+    }
+    rs_stage_small<8>(v, lane);
+    rs_stage_small<4>(v, lane);
+    rs_stage_small<2>(v, lane);
+    total = v[0] + xchg_small<1>(v[0]);
+}
+
+// Per-iteration pose state, as k_reduce's PoseState.  neq_out (stage-level
+// entry point): the pair's last workgroup stores the 31 sums there instead of
+// solving.
+struct RgbdState {
+    double* T64;         // [pair][16]
+    float* T32;          // [pair][12]
+    int32_t* status;     // [pair]
+    double* stats;       // [pair][iters][4] or null
+    unsigned* arrivals;  // [pair], zero at launch; re-armed by the last arriver
+    double* neq_out;     // [pair][31] or null
+    int it, iters;
+};
+
+// grid (chunks, pairs).  kAligned: W % 4 == 0, the depth base 8-byte and the
+// intensity base 4-byte aligned, centred columns exact (centred_exact): a
+// lane's four pixels share a row and load as one word each.
+template <bool kFast, bool kAligned>
+__global__ __launch_bounds__(kRedThreads) void k_rgbd_reduce(
+    const int16_t* __restrict__ dsrc, const uint8_t* __restrict__ gsrc,
+    const float4* __restrict__ recs, size_t P, const unsigned* __restrict__ photo, PairMap pm, int W,
+    int H, Intr K, FastK F, float thr2, PhotoK pk, int chunk, double* __restrict__ partials,
+    RgbdState ps)
+{
+    __shared__ double red[kRedThreads / 64][kRgbdNeq];
+    const int p = blockIdx.y;
+    const int b = blockIdx.x;
+    const int N = W * H;
+    const int16_t* __restrict__ sD = dsrc + (size_t)(pm.src0 + p) * N;
+    const uint8_t* __restrict__ sG = gsrc + (size_t)(pm.src0 + p) * N;
+    // the pair's target records and words through buffer descriptors: a gather
+    // past them (an unmatched lane's index) returns 0, an invalid record / word
+    const __amdgpu_buffer_rsrc_t rrec = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float4*>(recs + (size_t)(pm.tgt0 + p) * P), (short)0,
+        (int)(P * sizeof(float4)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rpho = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<unsigned*>(photo + (size_t)(pm.tgt0 + p) * N), (short)0,
+        N * (int)sizeof(unsigned), 0x00020000);
+    float T[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) T[k] = ps.T32[p * 12 + k];
+
+    double acc[kRgbdNeq];
+#pragma unroll
+    for (int k = 0; k < kRgbdNeq; ++k) acc[k] = 0.0;
+    int cnt_g = 0, cnt_p = 0;
+
+    const int start = b * chunk;
+    const int end = min(start + chunk, N);
+    const int stepV = kRedStep / W;
+    const int stepU = kRedStep - stepV * W;
+    int i = start + threadIdx.x * 4;
+    int v0 = i / W;
+    int u0 = i - v0 * W;
+    for (; i < end; i += kRedStep) {
+        const short4 d4 = load_depth4<kAligned>(sD, i, end);
+        const int dd[4] = {d4.x, d4.y, d4.z, d4.w};
+        unsigned g4;
+        if (kAligned) {
+            g4 = *reinterpret_cast<const unsigned*>(sG + i);
+        } else {
+            g4 = sG[i];
+#pragma unroll
+            for (int q = 1; q < 4; ++q)
+                if (i + q < end) g4 |= (unsigned)sG[i + q] << (8 * q);
+        }
+        float qx[4], qy[4], qz[4], uf[4], vf[4], fu[4], fv[4];
+        LaneMask in[4];
+        int j[4];
+        const float uc0 = (float)u0 - K.cx, vc0 = (float)v0 - K.cy;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float sx, sy, sz;
+            if (kAligned) {
+                backproject_c<kFast>(dd[q], uc0 + (float)q, vc0, K, F, sx, sy, sz);
+            } else {
+                int u = u0 + q, v = v0;
+                const bool wrap = u >= W;
+                u = wrap ? u - W : u;
+                v = wrap ? v + 1 : v;
+                backproject<kFast>((i + q) < end ? dd[q] : 0, u, v, K, F, sx, sy, sz);
+            }
+            rgbd_project(T, sx, sy, sz, K, W, H, qx[q], qy[q], qz[q], uf[q], vf[q], fu[q], fv[q],
+                         in[q], j[q]);
+        }
+        u0 += stepU;
+        v0 += stepV;
+        if (u0 >= W) {
+            u0 -= W;
+            ++v0;
+        }
+        // eight gathers back to back: the records, then the words
+        f4v t[4];
+        unsigned pw[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            t[q] = __builtin_bit_cast(
+                f4v, __builtin_amdgcn_raw_buffer_load_b128(rrec, (int)((unsigned)j[q] * 16u), 0, 0));
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            pw[q] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rpho, (int)((unsigned)j[q] * 4u),
+                                                                   0, 0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            rgbd_accumulate<kFast>(qx[q], qy[q], qz[q], t[q], pw[q],
+                                   (float)((g4 >> (8 * q)) & 255u), uf[q], vf[q], fu[q], fv[q],
+                                   in[q], K, F, thr2, pk, acc, cnt_g, cnt_p);
+    }
+    // the wave's counts, carried by lane 0 into the wave / workgroup sums
+    const int ln = threadIdx.x & 63;
+    acc[28] = ln == 0 ? (double)cnt_g : 0.0;
+    acc[30] = ln == 0 ? (double)cnt_p : 0.0;
+
+    // wave reduce-scatter, then the four waves in fixed order through LDS
+    const int wave = threadIdx.x >> 6;
+    {
+        double tot;
+        rgbd_wave_reduce_scatter(acc, ln, tot);
+        if (!(ln & 1) && (ln >> 1) < kRgbdNeq) red[wave][ln >> 1] = tot;
+    }
+    __syncthreads();
+    if (threadIdx.x >= 64) return;  // wave 0 publishes and, if last, solves
+    const int lane = threadIdx.x;
+    const int nblk = gridDim.x;
+    double* mine = partials + ((size_t)p * nblk + b) * kRgbdStride;
+    double s = 0.0;
+    if (lane < kRgbdNeq) {
+#pragma unroll
+        for (int w = 0; w < kRedThreads / 64; ++w) s += red[w][lane];
+    }
+    // the hand-off of k_reduce's fused solve: write-through partial stores,
+    // drained by the storing wave, then one agent-scope atomic per workgroup;
+    // the workgroup whose add returns nblk - 1 reads every partial of pair p
+    // with sc1 loads only
+    if (lane < kRgbdNeq)
+        __hip_atomic_store(reinterpret_cast<unsigned long long*>(mine) + lane,
+                           (unsigned long long)__double_as_longlong(s), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    unsigned ticket = 0;
+    if (lane == 0)
+        ticket = __hip_atomic_fetch_add(ps.arrivals + p, 1u, __ATOMIC_RELAXED,
+                                        __HIP_MEMORY_SCOPE_AGENT);
+    ticket = __shfl(ticket, 0, 64);
+    if (ticket != (unsigned)nblk - 1) return;
+    // fixed order: lanes 0..30 add the first half of the rows, lanes 32..62
+    // the second half, loads in batches of 8; then one add
+    const unsigned long long* base =
+        reinterpret_cast<const unsigned long long*>(partials + (size_t)p * nblk * kRgbdStride);
+    const int half = (nblk + 1) >> 1;
+    const int k = lane & 31;
+    double tsum = 0.0;
+    if (k < kRgbdNeq) {
+        const int b0 = lane < 32 ? 0 : half;
+        const int b1 = lane < 32 ? half : nblk;
+        for (int bb = b0; bb < b1; bb += 8) {
+            double v[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                v[q] = bb + q < b1 ? __longlong_as_double((long long)__hip_atomic_load(
+                                         base + (size_t)(bb + q) * kRgbdStride + k, __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT))
+                                   : 0.0;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) tsum += v[q];
+        }
+    }
+    tsum += __shfl_down(tsum, 32, 64);
+    double neq[kRgbdNeq];
+#pragma unroll
+    for (int q = 0; q < kRgbdNeq; ++q) neq[q] = __shfl(tsum, q, 64);
+    if (lane == 0) {
+        ps.arrivals[p] = 0;  // re-armed for the next launch (stream order)
+        if (ps.stats) {
+            double* st = ps.stats + ((size_t)p * ps.iters + ps.it) * 4;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) st[q] = neq[27 + q];
+        }
+        if (ps.neq_out) {
+#pragma unroll
+            for (int q = 0; q < kRgbdNeq; ++q) ps.neq_out[(size_t)p * kRgbdNeq + q] = neq[q];
+        } else {
+            // a10 unchanged on (A, b): its gates read the geometric count [28]
+            solve_update(neq, ps.T64 + (size_t)p * 16, ps.T32 + (size_t)p * 12, ps.status + p);
+        }
+    }
+}
+
+}  // namespace
+
+// =============================================================== host side ==
+
+struct youth_rgbd_ctx {
+    youth_icp_ctx* icp = nullptr;  // records, poses, status, arrival counters, staging depth
+    youth_rgbd_params prm{};
+    PhotoK pk{};
+    int frames = 0;                // frames the workspace holds: max_frames + 1
+    int chunks = 0;                // YOUTH_RGBD_CHUNKS (0: planned)
+    unsigned* d_photo = nullptr;   // [frames][N] packed words of the targets
+    uint8_t* d_gray = nullptr;     // [frames][N] staging for the host entry points
+    uint8_t* d_rgb = nullptr;      // [frames][N][3] (lazy: youth_rgbd_track_host_sequence)
+    double* d_part = nullptr;      // [pair][chunk][kRgbdStride]
+    size_t part_cap = 0;           // doubles
+    double* d_stats = nullptr;     // [frames][stats_iters][4]
+    int stats_iters = 0;
+    double* d_neq = nullptr;       // [kRgbdNeq]
+    int last_pairs = 0, last_iters = 0;
+    hipStream_t last_stream = nullptr;
+};
+
+static int rgbd_size_ok(const char* who, int n, int W, int H)
+{
+    if (n < 0 || n > 65535 || W < 3 || H < 3 || W > 16384 || H > 16384 ||
+        (long long)W * H > (1LL << 26))
+        return set_error(YOUTH_EINVAL,
+                         "%s: %d frames of %dx%d (need 0 <= frames <= 65535, 3 <= W, H <= 16384, "
+                         "W*H <= 2^26)",
+                         who, n, W, H);
+    return YOUTH_OK;
+}
+
+// k_rgbd_prep over n frames of `channels` channels; gray / photo nullable
+static int rgbd_launch_prep(hipStream_t s, const uint8_t* in, int channels, int n, int W, int H,
+                            uint8_t* gray, unsigned* photo)
+{
+    if (n <= 0) return YOUTH_OK;
+    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 3) == 0 &&
+                     (reinterpret_cast<uintptr_t>(gray) & 3) == 0 &&
+                     (reinterpret_cast<uintptr_t>(photo) & 15) == 0;
+    const long long groups = (long long)((W + 3) / 4) * H;
+    const dim3 grid((unsigned)((groups + kRgbdPrepThreads - 1) / kRgbdPrepThreads), (unsigned)n);
+    auto kern = channels == 3 ? (vec ? k_rgbd_prep<3, true> : k_rgbd_prep<3, false>)
+                              : (vec ? k_rgbd_prep<1, true> : k_rgbd_prep<1, false>);
+    hipLaunchKernelGGL(kern, grid, dim3(kRgbdPrepThreads), 0, s, in, gray, photo, W, H);
+    HIP_TRY(hipGetLastError());
+    return YOUTH_OK;
+}
+
+// chunks per pair and pixels per chunk of one iteration's launch
+static int rgbd_geometry(const youth_rgbd_ctx* r, int n_pairs, int* chunk_out)
+{
+    if (!r->chunks) return reduce_geometry(r->icp, n_pairs, chunk_out);
+    const int N = r->icp->N;
+    int nb = std::min(r->chunks, (N + kRedStep - 1) / kRedStep);
+    int chunk = (N + nb - 1) / nb;
+    chunk = (chunk + kRedStep - 1) / kRedStep * kRedStep;
+    nb = (N + chunk - 1) / chunk;
+    *chunk_out = chunk;
+    return nb;
+}
+
+static int rgbd_ensure_stats(youth_rgbd_ctx* r, int iters)
+{
+    if (iters <= r->stats_iters) return YOUTH_OK;
+    if (r->d_stats) HIP_TRY(hipFree(r->d_stats));
+    r->d_stats = nullptr;
+    r->stats_iters = 0;
+    HIP_TRY(hipMalloc(&r->d_stats, (size_t)r->frames * iters * 4 * sizeof(double)));
+    r->stats_iters = iters;
+    return YOUTH_OK;
+}
+
+// One k_rgbd_reduce launch over n_pairs pairs: iteration `it` with its fused
+// solve, or (neq_out) the sums alone.
+static int rgbd_launch_reduce(youth_rgbd_ctx* r, hipStream_t s, const int16_t* dsrc,
+                              const uint8_t* gsrc, PairMap pm, int n_pairs, int it,
+                              double* neq_out)
+{
+    youth_icp_ctx* c = r->icp;
+    int chunk = 0;
+    const int nb = rgbd_geometry(r, n_pairs, &chunk);
+    const size_t need = (size_t)nb * n_pairs * kRgbdStride;
+    if (need > r->part_cap) {
+        if (r->d_part) HIP_TRY(hipFree(r->d_part));
+        r->d_part = nullptr;
+        r->part_cap = 0;
+        HIP_TRY(hipMalloc(&r->d_part, need * sizeof(double)));
+        r->part_cap = need;
+    }
+    const float thr2 = r->prm.dist_thresh * r->prm.dist_thresh;
+    const bool aligned = (reinterpret_cast<uintptr_t>(dsrc) % 8 == 0) &&
+                         (reinterpret_cast<uintptr_t>(gsrc) % 4 == 0) && (c->W % 4 == 0) &&
+                         c->centred_exact;
+    const RgbdState ps{c->d_T64, c->d_T32, c->d_status, neq_out ? nullptr : r->d_stats,
+                       c->d_arrivals, neq_out, it, r->prm.iters};
+    auto kern = c->fast ? (aligned ? k_rgbd_reduce<true, true> : k_rgbd_reduce<true, false>)
+                        : (aligned ? k_rgbd_reduce<false, true> : k_rgbd_reduce<false, false>);
+    hipLaunchKernelGGL(kern, dim3(nb, n_pairs), dim3(kRedThreads), 0, s, dsrc, gsrc, c->d_rec, c->P,
+                       r->d_photo, pm, c->W, c->H, c->K, c->F, thr2, r->pk, chunk, r->d_part, ps);
+    HIP_TRY(hipGetLastError());
+    return YOUTH_OK;
+}
+
+// Targets prepped (records by k_prep, words by k_rgbd_prep) into workspace
+// frames [0, n_tgt); then the initial poses and prm.iters launches.
+static int rgbd_align(youth_rgbd_ctx* r, hipStream_t s, const int16_t* dsrc, const uint8_t* gsrc,
+                      const int16_t* dtgt, const uint8_t* gtgt, int n_tgt, PairMap pm, int n_pairs,
+                      const double* T_init_host, float* d_T_out)
+{
+    youth_icp_ctx* c = r->icp;
+    const double* dTi = nullptr;
+    if (T_init_host) {
+        for (size_t i = 0; i < (size_t)n_pairs * 16; ++i)
+            if (!std::isfinite(T_init_host[i]))
+                return set_error(YOUTH_EINVAL, "T_init: non-finite entry in pair %d", (int)(i / 16));
+        HIP_TRY(hipMemcpyAsync(c->d_Tinit, T_init_host, (size_t)n_pairs * 16 * sizeof(double),
+                               hipMemcpyHostToDevice, s));
+        dTi = c->d_Tinit;
+    }
+    const int iters = r->prm.iters;
+    int rc = rgbd_ensure_stats(r, iters > 0 ? iters : 1);
+    if (rc) return rc;
+    rc = launch_prep(c, s, dtgt, n_tgt, 0, false);
+    if (rc) return rc;
+    rc = rgbd_launch_prep(s, gtgt, 1, n_tgt, c->W, c->H, nullptr, r->d_photo);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_init, dim3((n_pairs + 63) / 64), dim3(64), 0, s, dTi, n_pairs, c->d_T64,
+                       c->d_T32, c->d_status, (unsigned*)nullptr, (unsigned*)nullptr, iters,
+                       c->d_head);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(c->d_arrivals, 0, (size_t)c->max_frames * sizeof(unsigned), s));
+    for (int it = 0; it < iters; ++it) {
+        rc = rgbd_launch_reduce(r, s, dsrc, gsrc, pm, n_pairs, it, nullptr);
+        if (rc) return rc;
+    }
+    r->last_pairs = n_pairs;
+    r->last_iters = iters;
+    r->last_stream = s;
+    if (!d_T_out) return YOUTH_OK;
+    hipLaunchKernelGGL(k_finish, dim3((n_pairs * 16 + 255) / 256), dim3(256), 0, s, c->d_T64,
+                       n_pairs, d_T_out, c->d_status, (const unsigned*)nullptr);
+    HIP_TRY(hipGetLastError());
+    return YOUTH_OK;
+}
+
+extern "C" {
+
+const char* youth_rgbd_last_error(void) { return g_last_error.c_str(); }
+
+youth_rgbd_params youth_rgbd_default_params(void)
+{
+    youth_rgbd_params p;
+    p.iters = 10;
+    p.dist_thresh = 0.10f;
+    p.lambda = 0.1f;
+    return p;
+}
+
+void youth_rgbd_destroy(youth_rgbd_ctx* r)
+{
+    if (!r) return;
+    if (r->icp) {
+        (void)hipSetDevice(r->icp->device);
+        if (r->last_stream) (void)hipStreamSynchronize(r->last_stream);
+        (void)hipStreamSynchronize(r->icp->stream);
+    }
+    void* bufs[] = {r->d_photo, r->d_gray, r->d_rgb, r->d_part, r->d_stats, r->d_neq};
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    youth_icp_destroy(r->icp);
+    delete r;
+}
+
+youth_rgbd_ctx* youth_rgbd_create(int device, int W, int H, int max_frames,
+                                  const youth_intrinsics* K, const youth_rgbd_params* params)
+{
+    const youth_rgbd_params prm = params ? *params : youth_rgbd_default_params();
+    if (prm.iters < 0 || !std::isfinite(prm.dist_thresh) || !(prm.dist_thresh > 0.0f) ||
+        !std::isfinite(prm.lambda) || prm.lambda < 0.0f) {
+        set_error(YOUTH_EINVAL,
+                  "youth_rgbd_create: bad parameters: iters %d, dist_thresh %g, lambda %g (need "
+                  "iters >= 0, dist_thresh > 0 and lambda >= 0, both finite)",
+                  prm.iters, (double)prm.dist_thresh, (double)prm.lambda);
+        return nullptr;
+    }
+    if (W < 3 || H < 3 || W > 16384 || H > 16384 || max_frames < 2 || max_frames > 65535 ||
+        (long long)W * H > (1LL << 26)) {
+        set_error(YOUTH_EINVAL,
+                  "youth_rgbd_create: bad size %dx%d / max_frames %d (need 3 <= W, H <= 16384, "
+                  "W*H <= 2^26, 2 <= max_frames <= 65535)",
+                  W, H, max_frames);
+        return nullptr;
+    }
+    const youth_icp_params ip{prm.iters, prm.dist_thresh};
+    // one frame more than pairs: a sequence of max_frames pairs stages
+    // max_frames + 1 host frames
+    youth_icp_ctx* c = youth_icp_create(device, W, H, max_frames + 1, K, &ip);
+    if (!c) return nullptr;  // youth_icp_create's text stands
+    auto* r = new youth_rgbd_ctx();
+    r->icp = c;
+    r->prm = prm;
+    r->frames = max_frames + 1;
+    r->pk.w = prm.lambda / 255.0f;
+    r->pk.kx = (0.5f * r->pk.w) * c->K.fx;
+    r->pk.ky = (0.5f * r->pk.w) * c->K.fy;
+    const char* ck = getenv("YOUTH_RGBD_CHUNKS");  // test knob
+    if (ck && atoi(ck) > 0) r->chunks = atoi(ck);
+    const size_t N = (size_t)c->N, F = (size_t)r->frames;
+    hipError_t e;
+    if ((e = hipMalloc(&r->d_photo, F * N * sizeof(unsigned))) != hipSuccess ||
+        (e = hipMalloc(&r->d_gray, F * N)) != hipSuccess ||
+        (e = hipMalloc(&r->d_neq, kRgbdNeq * sizeof(double))) != hipSuccess) {
+        set_error(e == hipErrorOutOfMemory ? YOUTH_ENOMEM : YOUTH_EHIP,
+                  "youth_rgbd_create: hipMalloc: %s", hipGetErrorString(e));
+        youth_rgbd_destroy(r);
+        return nullptr;
+    }
+    if (rgbd_ensure_stats(r, prm.iters > 0 ? prm.iters : 1) != YOUTH_OK) {
+        youth_rgbd_destroy(r);
+        return nullptr;
+    }
+    return r;
+}
+
+int youth_rgbd_luma_device(int device, const uint8_t* d_rgb, uint8_t* d_gray, int n, int W, int H,
+                           void* stream)
+{
+    static const char* who = "youth_rgbd_luma_device";
+    if (!d_rgb || !d_gray) return set_error(YOUTH_EINVAL, "%s: null buffer", who);
+    int rc = rgbd_size_ok(who, n, W, H);
+    if (rc) return rc;
+    const int ndev = youth_icp_device_count();
+    if (ndev <= 0) return set_error(YOUTH_ENODEV, "%s: no HIP device visible", who);
+    if (device < 0 || device >= ndev)
+        return set_error(YOUTH_EINVAL, "%s: device %d of %d", who, device, ndev);
+    HIP_TRY(hipSetDevice(device));
+    return rgbd_launch_prep((hipStream_t)stream, d_rgb, 3, n, W, H, d_gray, nullptr);
+}
+
+int youth_rgbd_prep_device(youth_rgbd_ctx* r, const uint8_t* d_in, int channels, int n,
+                           uint8_t* d_gray, uint32_t* d_photo, void* stream)
+{
+    static const char* who = "youth_rgbd_prep_device";
+    if (!r || !d_in || (channels != 1 && channels != 3) || n < 0 || n > 65535)
+        return set_error(YOUTH_EINVAL, "%s: bad arguments (channels %d, %d frames)", who, channels,
+                         n);
+    int rc = bind_device(r->icp);
+    if (rc) return rc;
+    return rgbd_launch_prep(pick_stream(r->icp, stream), d_in, channels, n, r->icp->W, r->icp->H,
+                            d_gray, d_photo);
+}
+
+int youth_rgbd_align_pairs_device(youth_rgbd_ctx* r, const int16_t* d_src_depth,
+                                  const uint8_t* d_src_gray, const int16_t* d_dst_depth,
+                                  const uint8_t* d_dst_gray, int n_pairs, const double* T_init,
+                                  float* d_T_out, void* stream)
+{
+    static const char* who = "youth_rgbd_align_pairs_device";
+    if (!r) return set_error(YOUTH_EINVAL, "%s: null context", who);
+    if (!d_src_depth || !d_src_gray || !d_dst_depth || !d_dst_gray)
+        return set_error(YOUTH_EINVAL, "%s: null buffer", who);
+    if (n_pairs <= 0 || n_pairs > r->frames - 1)
+        return set_error(YOUTH_EINVAL, "%s: %d pairs (need 1 .. max_frames = %d)", who, n_pairs,
+                         r->frames - 1);
+    int rc = bind_device(r->icp);
+    if (rc) return rc;
+    return rgbd_align(r, pick_stream(r->icp, stream), d_src_depth, d_src_gray, d_dst_depth,
+                      d_dst_gray, n_pairs, PairMap{0, 0}, n_pairs, T_init, d_T_out);
+}
+
+int youth_rgbd_align_sequence_device(youth_rgbd_ctx* r, const int16_t* d_depth,
+                                     const uint8_t* d_gray, int n_frames, float* d_T_out,
+                                     void* stream)
+{
+    static const char* who = "youth_rgbd_align_sequence_device";
+    if (!r) return set_error(YOUTH_EINVAL, "%s: null context", who);
+    if (!d_depth || !d_gray) return set_error(YOUTH_EINVAL, "%s: null buffer", who);
+    if (n_frames < 2 || n_frames > r->frames)
+        return set_error(YOUTH_EINVAL, "%s: %d frames (need 2 .. max_frames + 1 = %d)", who,
+                         n_frames, r->frames);
+    int rc = bind_device(r->icp);
+    if (rc) return rc;
+    // every frame but the last is a target, prepped once; pair k: source frame
+    // k + 1, target frame k
+    return rgbd_align(r, pick_stream(r->icp, stream), d_depth, d_gray, d_depth, d_gray,
+                      n_frames - 1, PairMap{1, 0}, n_frames - 1, nullptr, d_T_out);
+}
+
+int youth_rgbd_sync(youth_rgbd_ctx* r, void* stream)
+{
+    if (!r) return set_error(YOUTH_EINVAL, "youth_rgbd_sync: null context");
+    int rc = bind_device(r->icp);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(pick_stream(r->icp, stream)));
+    return YOUTH_OK;
+}
+
+int youth_rgbd_get_poses(youth_rgbd_ctx* r, int n, double* T64, float* T32, int32_t* status)
+{
+    if (!r || n < 0 || n > r->frames - 1)
+        return set_error(YOUTH_EINVAL, "youth_rgbd_get_poses: bad arguments (%d poses)", n);
+    youth_icp_ctx* c = r->icp;
+    int rc = bind_device(c);
+    if (rc) return rc;
+    hipStream_t s = r->last_stream ? r->last_stream : c->stream;
+    if (n == 0) {
+        HIP_TRY(hipStreamSynchronize(s));
+        return YOUTH_OK;
+    }
+    if (T64)
+        HIP_TRY(hipMemcpyAsync(T64, c->d_T64, (size_t)n * 16 * sizeof(double),
+                               hipMemcpyDeviceToHost, s));
+    if (T32) {
+        hipLaunchKernelGGL(k_finish, dim3((n * 16 + 255) / 256), dim3(256), 0, s, c->d_T64, n,
+                           c->d_Tout, c->d_status, (const unsigned*)nullptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(T32, c->d_Tout, (size_t)n * 16 * sizeof(float),
+                               hipMemcpyDeviceToHost, s));
+    }
+    if (status)
+        HIP_TRY(hipMemcpyAsync(status, c->d_status, (size_t)n * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return YOUTH_OK;
+}
+
+int youth_rgbd_get_stats(youth_rgbd_ctx* r, int n, int iters, double* stats)
+{
+    if (!r || !stats || n < 0 || n > r->last_pairs || iters != r->last_iters || iters < 1 ||
+        iters > r->stats_iters)
+        return set_error(YOUTH_EINVAL, "youth_rgbd_get_stats: bad arguments (%d pairs, %d iterations)",
+                         n, iters);
+    int rc = bind_device(r->icp);
+    if (rc) return rc;
+    hipStream_t s = r->last_stream ? r->last_stream : r->icp->stream;
+    if (n > 0)
+        HIP_TRY(hipMemcpyAsync(stats, r->d_stats, (size_t)n * iters * 4 * sizeof(double),
+                               hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return YOUTH_OK;
+}
+
+int youth_rgbd_reduce_host(youth_rgbd_ctx* r, const int16_t* src_depth, const uint8_t* src_gray,
+                           const int16_t* dst_depth, const uint8_t* dst_gray, const float* T12,
+                           double* neq31)
+{
+    static const char* who = "youth_rgbd_reduce_host";
+    if (!r) return set_error(YOUTH_EINVAL, "%s: null context", who);
+    if (!src_depth || !src_gray || !dst_depth || !dst_gray || !T12 || !neq31)
+        return set_error(YOUTH_EINVAL, "%s: null buffer", who);
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(T12[i])) return set_error(YOUTH_EINVAL, "%s: non-finite pose", who);
+    youth_icp_ctx* c = r->icp;
+    int rc = bind_device(c);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    const size_t N = c->N;
+    // frame 0 the source, frame 1 the target
+    HIP_TRY(hipMemcpyAsync(c->d_depth, src_depth, N * sizeof(int16_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->d_depth + N, dst_depth, N * sizeof(int16_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(r->d_gray, src_gray, N, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(r->d_gray + N, dst_gray, N, hipMemcpyHostToDevice, s));
+    rc = launch_prep(c, s, c->d_depth + N, 1, 1, false);
+    if (rc) return rc;
+    rc = rgbd_launch_prep(s, r->d_gray + N, 1, 1, c->W, c->H, nullptr, r->d_photo + N);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_T32, T12, 12 * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(c->d_arrivals, 0, sizeof(unsigned), s));
+    rc = rgbd_launch_reduce(r, s, c->d_depth, r->d_gray, PairMap{0, 1}, 1, 0, r->d_neq);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(neq31, r->d_neq, kRgbdNeq * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return YOUTH_OK;
+}
+
+int youth_rgbd_track_host_sequence(youth_rgbd_ctx* r, const int16_t* depth, const uint8_t* rgb,
+                                   int n_frames, double* T_rel, int32_t* status)
+{
+    static const char* who = "youth_rgbd_track_host_sequence";
+    if (!r) return set_error(YOUTH_EINVAL, "%s: null context", who);
+    if (!depth || !rgb || !T_rel) return set_error(YOUTH_EINVAL, "%s: null buffer", who);
+    if (n_frames < 2 || n_frames > r->frames)
+        return set_error(YOUTH_EINVAL, "%s: %d frames (need 2 .. max_frames + 1 = %d)", who,
+                         n_frames, r->frames);
+    youth_icp_ctx* c = r->icp;
+    int rc = bind_device(c);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    const size_t N = c->N;
+    if (!r->d_rgb) HIP_TRY(hipMalloc(&r->d_rgb, (size_t)r->frames * N * 3));
+    HIP_TRY(hipMemcpyAsync(c->d_depth, depth, (size_t)n_frames * N * sizeof(int16_t),
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(r->d_rgb, rgb, (size_t)n_frames * N * 3, hipMemcpyHostToDevice, s));
+    rc = rgbd_launch_prep(s, r->d_rgb, 3, n_frames, c->W, c->H, r->d_gray, nullptr);
+    if (rc) return rc;
+    rc = youth_rgbd_align_sequence_device(r, c->d_depth, r->d_gray, n_frames, nullptr, s);
+    if (rc) return rc;
+    rc = youth_rgbd_get_poses(r, n_frames - 1, T_rel, nullptr, status);
+    if (rc) return rc;
+    return n_frames - 1;
+}
+
+}  // extern "C"

@@ -120,9 +120,33 @@ static double cast_ray(const double o[3], const double d[3], const sphere_t* sp)
     return t;
 }
 
-void youth_synth_render(const double T_wc[16], int W, int H,
-                        const youth_intrinsics* K, uint64_t noise_seed,
-                        int flags, int16_t* depth)
+/* The procedural world-space texture of the colour generators
+ * (youth_synth.h): three bumps along oblique directions plus a shared coarse
+ * one, libm-free so the same bytes come out everywhere. */
+static double tex_bump(double t)
+{
+    double fl = (double)(long long)t;
+    if (fl > t) fl -= 1.0;
+    const double f = t - fl;
+    return 4.0 * f * (1.0 - f);
+}
+static uint8_t tex_channel(double fine, double b4)
+{
+    return (uint8_t)(int)(32.0 + 192.0 * (0.5 * fine + 0.5 * b4) + 0.5);
+}
+static void texture_rgb(const double p[3], uint8_t rgb[3])
+{
+    const double b4 = tex_bump((p[0] + p[1] + p[2]) / 0.9);
+    rgb[0] = tex_channel(tex_bump((p[0] + 0.3 * p[2]) / 0.23), b4);
+    rgb[1] = tex_channel(tex_bump((p[1] - 0.4 * p[0]) / 0.31), b4);
+    rgb[2] = tex_channel(tex_bump((p[2] + 0.5 * p[1]) / 0.27), b4);
+}
+
+/* One frame: depth as youth_synth_render documents it and, when rgb is not
+ * NULL, the texture at every ray's exact hit point (before noise, holes and
+ * the range test; 0 where the ray hits nothing). */
+static void render_frame(const double T_wc[16], int W, int H, const youth_intrinsics* K,
+                         uint64_t noise_seed, int flags, int16_t* depth, uint8_t* rgb)
 {
     sphere_t sp[N_SPHERES];
     scene_spheres(sp);
@@ -138,6 +162,14 @@ void youth_synth_render(const double T_wc[16], int W, int H,
                 dw[i] = T_wc[i * 4 + 0] * dc[0] + T_wc[i * 4 + 1] * dc[1] +
                         T_wc[i * 4 + 2] * dc[2];
             const double z = cast_ray(o, dw, sp);
+            if (rgb) {
+                uint8_t* c = rgb + ((size_t)v * W + u) * 3;
+                c[0] = c[1] = c[2] = 0;
+                if (isfinite(z)) {
+                    const double hit[3] = {o[0] + z * dw[0], o[1] + z * dw[1], o[2] + z * dw[2]};
+                    texture_rgb(hit, c);
+                }
+            }
             /* always three draws per pixel, so flags do not shift the stream */
             const double hole = u01(&rng);
             const double g1 = (double)((splitmix64(&rng) >> 11) + 1) * 0x1.0p-53;
@@ -156,6 +188,20 @@ void youth_synth_render(const double T_wc[16], int W, int H,
             depth[(size_t)v * W + u] = (int16_t)dq;
         }
     }
+}
+
+void youth_synth_render(const double T_wc[16], int W, int H,
+                        const youth_intrinsics* K, uint64_t noise_seed,
+                        int flags, int16_t* depth)
+{
+    render_frame(T_wc, W, H, K, noise_seed, flags, depth, NULL);
+}
+
+void youth_synth_render_rgb(const double T_wc[16], int W, int H,
+                            const youth_intrinsics* K, uint64_t noise_seed,
+                            int flags, int16_t* depth, uint8_t* rgb)
+{
+    render_frame(T_wc, W, H, K, noise_seed, flags, depth, rgb);
 }
 
 /* T = [R t; 0 1] from camera orientation angles and position. */
@@ -198,8 +244,9 @@ static void mat4_mul(const double A[16], const double B[16], double C[16])
     memcpy(C, O, sizeof(O));
 }
 
-void youth_synth_pair(uint64_t seed, int W, int H, const youth_intrinsics* K,
-                      int flags, int16_t* src, int16_t* dst, double* T_gt)
+static void pair_frames(uint64_t seed, int W, int H, const youth_intrinsics* K, int flags,
+                        int16_t* src, int16_t* dst, double* T_gt, uint8_t* src_rgb,
+                        uint8_t* dst_rgb)
 {
     uint64_t s = seed;
     const double pos[3] = {uniform(&s, -0.3, 0.3), uniform(&s, -0.3, 0.3),
@@ -228,9 +275,15 @@ void youth_synth_pair(uint64_t seed, int W, int H, const youth_intrinsics* K,
     mat4_mul(Twc0, T01, Twc1);
     const uint64_t seed_dst = splitmix64(&s);
     const uint64_t seed_src = splitmix64(&s);
-    youth_synth_render(Twc0, W, H, K, seed_dst, flags, dst);
-    youth_synth_render(Twc1, W, H, K, seed_src, flags, src);
+    render_frame(Twc0, W, H, K, seed_dst, flags, dst, dst_rgb);
+    render_frame(Twc1, W, H, K, seed_src, flags, src, src_rgb);
     if (T_gt) memcpy(T_gt, T01, sizeof(T01));
+}
+
+void youth_synth_pair(uint64_t seed, int W, int H, const youth_intrinsics* K,
+                      int flags, int16_t* src, int16_t* dst, double* T_gt)
+{
+    pair_frames(seed, W, H, K, flags, src, dst, T_gt, NULL, NULL);
 }
 
 void youth_synth_pairs(uint64_t base_seed, int first_index, int n, int W, int H,
@@ -246,9 +299,22 @@ void youth_synth_pairs(uint64_t base_seed, int first_index, int n, int W, int H,
                          T_gt ? T_gt + (size_t)p * 16 : NULL);
 }
 
-void youth_synth_sequence(uint64_t seed, int first_frame, int n, int W, int H,
-                          const youth_intrinsics* K, int flags, int16_t* frames,
-                          double* T_wc)
+void youth_synth_pairs_rgb(uint64_t base_seed, int first_index, int n, int W, int H,
+                           const youth_intrinsics* K, int flags, int16_t* src,
+                           int16_t* dst, double* T_gt, uint8_t* src_rgb, uint8_t* dst_rgb)
+{
+    const size_t N = (size_t)W * (size_t)H;
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int p = 0; p < n; ++p)
+        pair_frames(base_seed + (uint64_t)(first_index + p), W, H, K, flags,
+                    src + (size_t)p * N, dst + (size_t)p * N,
+                    T_gt ? T_gt + (size_t)p * 16 : NULL, src_rgb + (size_t)p * N * 3,
+                    dst_rgb + (size_t)p * N * 3);
+}
+
+static void sequence_frames(uint64_t seed, int first_frame, int n, int W, int H,
+                            const youth_intrinsics* K, int flags, int16_t* frames,
+                            double* T_wc, uint8_t* rgb)
 {
     const size_t N = (size_t)W * (size_t)H;
 #pragma omp parallel for schedule(dynamic, 1)
@@ -263,7 +329,22 @@ void youth_synth_sequence(uint64_t seed, int first_frame, int n, int W, int H,
         camera_pose(yaw, pitch, roll, pos, T);
         uint64_t s = seed ^ (0xD1B54A32D192ED03ull * (uint64_t)(k + 1));
         const uint64_t ns = splitmix64(&s);
-        youth_synth_render(T, W, H, K, ns, flags, frames + (size_t)f * N);
+        render_frame(T, W, H, K, ns, flags, frames + (size_t)f * N,
+                     rgb ? rgb + (size_t)f * N * 3 : NULL);
         if (T_wc) memcpy(T_wc + (size_t)f * 16, T, sizeof(T));
     }
+}
+
+void youth_synth_sequence(uint64_t seed, int first_frame, int n, int W, int H,
+                          const youth_intrinsics* K, int flags, int16_t* frames,
+                          double* T_wc)
+{
+    sequence_frames(seed, first_frame, n, W, H, K, flags, frames, T_wc, NULL);
+}
+
+void youth_synth_sequence_rgb(uint64_t seed, int first_frame, int n, int W, int H,
+                              const youth_intrinsics* K, int flags, int16_t* frames,
+                              double* T_wc, uint8_t* rgb)
+{
+    sequence_frames(seed, first_frame, n, W, H, K, flags, frames, T_wc, rgb);
 }

@@ -1,0 +1,221 @@
+"""Python host mirror of include/youth_rgbd.h (ctypes): RGB-D alignment, a
+photometric term beside point-to-plane ICP.
+
+``RgbdContext`` owns the device workspace.  Its device entry points take torch
+tensors (int16 depth, uint8 intensity) and run asynchronously; the host entry
+points take numpy frames.  Lives in libyouth_icp.so; no CPU fallback (a missing
+library raises, a machine without a HIP device raises
+``IcpError(YOUTH_ENODEV)``).
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int16, c_int32, c_uint8, c_void_p
+
+import numpy as np
+
+import youth_icp
+from youth_icp import IcpError, Intrinsics
+
+HEADER_PATH = os.path.join(os.path.dirname(youth_icp.HERE), "include", "youth_rgbd.h")
+NEQ = 31
+PHOTO_VALID = 0x80000000
+
+
+class RgbdParams(ctypes.Structure):
+    _fields_ = [("iters", c_int), ("dist_thresh", c_float), ("lam", c_float)]
+
+
+_bound = False
+
+
+def load_library() -> ctypes.CDLL:
+    global _bound
+    lib = youth_icp.load_library()
+    if not _bound:
+        PD = POINTER(c_double)
+        sigs = {
+            "youth_rgbd_default_params": (RgbdParams, []),
+            "youth_rgbd_last_error": (c_char_p, []),
+            "youth_rgbd_create": (c_void_p, [c_int, c_int, c_int, c_int, POINTER(Intrinsics),
+                                             POINTER(RgbdParams)]),
+            "youth_rgbd_destroy": (None, [c_void_p]),
+            "youth_rgbd_luma_device": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                               c_void_p]),
+            "youth_rgbd_align_pairs_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_void_p, c_int, PD, c_void_p, c_void_p]),
+            "youth_rgbd_align_sequence_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int,
+                                                         c_void_p, c_void_p]),
+            "youth_rgbd_sync": (c_int, [c_void_p, c_void_p]),
+            "youth_rgbd_get_poses": (c_int, [c_void_p, c_int, PD, POINTER(c_float),
+                                             POINTER(c_int32)]),
+            "youth_rgbd_get_stats": (c_int, [c_void_p, c_int, c_int, PD]),
+            "youth_rgbd_prep_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                               c_void_p, c_void_p]),
+            "youth_rgbd_reduce_host": (c_int, [c_void_p, POINTER(c_int16), POINTER(c_uint8),
+                                               POINTER(c_int16), POINTER(c_uint8),
+                                               POINTER(c_float), PD]),
+            "youth_rgbd_track_host_sequence": (c_int, [c_void_p, POINTER(c_int16),
+                                                       POINTER(c_uint8), c_int, PD,
+                                                       POINTER(c_int32)]),
+        }
+        for name, (res, args) in sigs.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _bound = True
+    return lib
+
+
+def _last_error(lib) -> str:
+    return (lib.youth_rgbd_last_error() or b"").decode()
+
+
+def _check(lib, code: int) -> int:
+    if code < 0:
+        raise IcpError(code, _last_error(lib))
+    return code
+
+
+def default_params() -> tuple[int, float, float]:
+    p = load_library().youth_rgbd_default_params()
+    return p.iters, p.dist_thresh, p.lam
+
+
+def unpack_photo(words: np.ndarray):
+    """A packed photometric word array -> (Y, gx, gy, valid)."""
+    w = np.asarray(words, np.uint32)
+    return ((w & 255).astype(np.uint8), ((w >> 8) & 511).astype(np.int32) - 255,
+            ((w >> 17) & 511).astype(np.int32) - 255, (w & PHOTO_VALID) != 0)
+
+
+def _ptr(t):
+    return None if t is None else (t.data_ptr() or None)
+
+
+def luma_device(d_rgb, d_gray=None, stream: int = 0):
+    """youth_rgbd_luma_device on torch uint8 tensors: [n][H][W][3] (or
+    [H][W][3]) -> [n][H][W]; asynchronous on ``stream``.  Returns ``d_gray``."""
+    import torch
+
+    lib = load_library()
+    if d_rgb.dtype != torch.uint8 or not d_rgb.is_cuda or not d_rgb.is_contiguous() \
+            or d_rgb.shape[-1] != 3 or d_rgb.ndim not in (3, 4):
+        raise ValueError("d_rgb: a contiguous uint8 [n][H][W][3] tensor on the GPU")
+    if d_gray is None:
+        d_gray = torch.empty(d_rgb.shape[:-1], dtype=torch.uint8, device=d_rgb.device)
+    if d_gray.dtype != torch.uint8 or d_gray.device != d_rgb.device or not d_gray.is_contiguous() \
+            or tuple(d_gray.shape) != tuple(d_rgb.shape[:-1]):
+        raise ValueError("d_gray: a contiguous uint8 tensor of d_rgb's frames and device")
+    n = 1 if d_rgb.ndim == 3 else d_rgb.shape[0]
+    H, W = d_rgb.shape[-3], d_rgb.shape[-2]
+    _check(lib, lib.youth_rgbd_luma_device(d_rgb.device.index or 0, _ptr(d_rgb), _ptr(d_gray), n,
+                                           W, H, stream or None))
+    return d_gray
+
+
+class RgbdContext:
+    """Device workspace for max_frames pairs of W x H (youth_rgbd_create)."""
+
+    def __init__(self, width: int, height: int, max_frames: int, K: Intrinsics | None = None,
+                 iters: int = 10, dist_thresh: float = 0.10, lam: float = 0.1, device: int = 0):
+        self._lib = load_library()
+        self.W, self.H, self.max_frames, self.iters = width, height, max_frames, iters
+        self.K = K if K is not None else youth_icp.default_intrinsics(width, height)
+        self.params = RgbdParams(iters, dist_thresh, lam)
+        self._ctx = self._lib.youth_rgbd_create(device, width, height, max_frames,
+                                                ctypes.byref(self.K), ctypes.byref(self.params))
+        if not self._ctx:
+            msg = _last_error(self._lib)
+            code = (youth_icp.YOUTH_ENODEV if "no HIP device" in msg
+                    else youth_icp.YOUTH_EINVAL if ": bad " in msg else youth_icp.YOUTH_EHIP)
+            raise IcpError(code, msg)
+
+    def close(self):
+        if getattr(self, "_ctx", None):
+            self._lib.youth_rgbd_destroy(self._ctx)
+            self._ctx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    # ---- device entry points (torch tensors) ----
+    def align_pairs_device(self, d_src_depth, d_src_gray, d_dst_depth, d_dst_gray, n_pairs=None,
+                           T_init=None, d_T_out=None, stream: int = 0):
+        n = d_src_depth.shape[0] if n_pairs is None else n_pairs
+        Ti = None
+        if T_init is not None:
+            Ti = np.ascontiguousarray(T_init, np.float64).reshape(-1, 16)
+        _check(self._lib, self._lib.youth_rgbd_align_pairs_device(
+            self._ctx, _ptr(d_src_depth), _ptr(d_src_gray), _ptr(d_dst_depth), _ptr(d_dst_gray), n,
+            None if Ti is None else Ti.ctypes.data_as(POINTER(c_double)), _ptr(d_T_out),
+            stream or None))
+
+    def align_sequence_device(self, d_depth, d_gray, n_frames=None, d_T_out=None, stream: int = 0):
+        n = d_depth.shape[0] if n_frames is None else n_frames
+        _check(self._lib, self._lib.youth_rgbd_align_sequence_device(
+            self._ctx, _ptr(d_depth), _ptr(d_gray), n, _ptr(d_T_out), stream or None))
+
+    def prep_device(self, d_in, channels: int, n: int, d_gray=None, d_photo=None, stream: int = 0):
+        _check(self._lib, self._lib.youth_rgbd_prep_device(
+            self._ctx, _ptr(d_in), channels, n, _ptr(d_gray), _ptr(d_photo), stream or None))
+
+    def sync(self, stream: int = 0):
+        _check(self._lib, self._lib.youth_rgbd_sync(self._ctx, stream or None))
+
+    def poses(self, n: int):
+        """-> (T64 [n,4,4], T32 [n,4,4], status [n]) of the last align."""
+        T64 = np.zeros((n, 4, 4), np.float64)
+        T32 = np.zeros((n, 4, 4), np.float32)
+        st = np.zeros(n, np.int32)
+        _check(self._lib, self._lib.youth_rgbd_get_poses(
+            self._ctx, n, T64.ctypes.data_as(POINTER(c_double)),
+            T32.ctypes.data_as(POINTER(c_float)), st.ctypes.data_as(POINTER(c_int32))))
+        T64[:, 3, :] = (0.0, 0.0, 0.0, 1.0)
+        return T64, T32, st
+
+    def stats(self, n: int, iters: int | None = None):
+        """-> [n, iters, 4]: sum r^2, geometric count, sum rp^2, photometric count."""
+        iters = self.iters if iters is None else iters
+        out = np.zeros((n, iters, 4), np.float64)
+        _check(self._lib, self._lib.youth_rgbd_get_stats(self._ctx, n, iters,
+                                                         out.ctypes.data_as(POINTER(c_double))))
+        return out
+
+    # ---- host entry points (numpy frames) ----
+    def reduce_host(self, src_depth, src_gray, dst_depth, dst_gray, T12) -> np.ndarray:
+        s = np.ascontiguousarray(src_depth, np.int16)
+        d = np.ascontiguousarray(dst_depth, np.int16)
+        sg = np.ascontiguousarray(src_gray, np.uint8)
+        dg = np.ascontiguousarray(dst_gray, np.uint8)
+        for a in (s, d, sg, dg):
+            if a.shape != (self.H, self.W):
+                raise ValueError("frames: [H][W] of the context's size")
+        T = np.ascontiguousarray(np.asarray(T12, np.float32).reshape(-1)[:12])
+        out = np.zeros(NEQ, np.float64)
+        _check(self._lib, self._lib.youth_rgbd_reduce_host(
+            self._ctx, s.ctypes.data_as(POINTER(c_int16)), sg.ctypes.data_as(POINTER(c_uint8)),
+            d.ctypes.data_as(POINTER(c_int16)), dg.ctypes.data_as(POINTER(c_uint8)),
+            T.ctypes.data_as(POINTER(c_float)), out.ctypes.data_as(POINTER(c_double))))
+        return out
+
+    def track_host_sequence(self, depth, rgb):
+        """-> (T_rel [n-1,4,4] fp64 with P_k = T_rel[k] P_{k+1}, status [n-1])."""
+        d = np.ascontiguousarray(depth, np.int16)
+        c = np.ascontiguousarray(rgb, np.uint8)
+        n = d.shape[0]
+        if d.shape != (n, self.H, self.W) or c.shape != (n, self.H, self.W, 3):
+            raise ValueError("depth [n][H][W] and rgb [n][H][W][3] of the context's size")
+        T = np.zeros((max(n - 1, 0), 4, 4), np.float64)
+        st = np.zeros(max(n - 1, 0), np.int32)
+        _check(self._lib, self._lib.youth_rgbd_track_host_sequence(
+            self._ctx, d.ctypes.data_as(POINTER(c_int16)), c.ctypes.data_as(POINTER(c_uint8)), n,
+            T.ctypes.data_as(POINTER(c_double)), st.ctypes.data_as(POINTER(c_int32))))
+        return T, st

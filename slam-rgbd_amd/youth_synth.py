@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_double, c_int, c_int16, c_uint64
+from ctypes import POINTER, c_double, c_int, c_int16, c_uint8, c_uint64
 
 import numpy as np
 
@@ -43,6 +43,15 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.youth_synth_sequence.argtypes = [c_uint64, c_int, c_int, c_int, c_int, PK, c_int, P16,
                                          PD]
     lib.youth_synth_sequence.restype = None
+    P8 = POINTER(c_uint8)
+    lib.youth_synth_render_rgb.argtypes = [PD, c_int, c_int, PK, c_uint64, c_int, P16, P8]
+    lib.youth_synth_render_rgb.restype = None
+    lib.youth_synth_pairs_rgb.argtypes = [c_uint64, c_int, c_int, c_int, c_int, PK, c_int, P16,
+                                          P16, PD, P8, P8]
+    lib.youth_synth_pairs_rgb.restype = None
+    lib.youth_synth_sequence_rgb.argtypes = [c_uint64, c_int, c_int, c_int, c_int, PK, c_int,
+                                             P16, PD, P8]
+    lib.youth_synth_sequence_rgb.restype = None
     _lib = lib
     return lib
 
@@ -88,3 +97,50 @@ def render(T_wc: np.ndarray, width: int, height: int, K=None, noise_seed: int = 
     load_library().youth_synth_render(_p(T, c_double), width, height, ctypes.byref(K),
                                       noise_seed, flags, _p(out, c_int16))
     return out
+
+
+def pairs_rgb(first_index: int, n: int, width: int = 640, height: int = 480, K=None,
+              flags: int = DEFAULT_FLAGS, base_seed: int = PAIR_SEED):
+    """pairs() with colour -> (src, dst, T_gt, src_rgb, dst_rgb); rgb uint8 [n][H][W][3]."""
+    K = K if K is not None else viewer_intrinsics(width, height)
+    src = np.zeros((n, height, width), np.int16)
+    dst = np.zeros((n, height, width), np.int16)
+    T = np.zeros((n, 4, 4), np.float64)
+    src_rgb = np.zeros((n, height, width, 3), np.uint8)
+    dst_rgb = np.zeros((n, height, width, 3), np.uint8)
+    load_library().youth_synth_pairs_rgb(base_seed, first_index, n, width, height,
+                                         ctypes.byref(K), flags, _p(src, c_int16),
+                                         _p(dst, c_int16), _p(T, c_double), _p(src_rgb, c_uint8),
+                                         _p(dst_rgb, c_uint8))
+    return src, dst, T, src_rgb, dst_rgb
+
+
+def sequence_rgb(first_frame: int, n: int, width: int = 640, height: int = 480, K=None,
+                 flags: int = DEFAULT_FLAGS, seed: int = SEQ_SEED):
+    """sequence() with colour -> (frames, T_wc, rgb); rgb uint8 [n][H][W][3]."""
+    K = K if K is not None else viewer_intrinsics(width, height)
+    frames = np.zeros((n, height, width), np.int16)
+    T = np.zeros((n, 4, 4), np.float64)
+    rgb = np.zeros((n, height, width, 3), np.uint8)
+    load_library().youth_synth_sequence_rgb(seed, first_frame, n, width, height,
+                                            ctypes.byref(K), flags, _p(frames, c_int16),
+                                            _p(T, c_double), _p(rgb, c_uint8))
+    return frames, T, rgb
+
+
+def render_rgb(T_wc: np.ndarray, width: int, height: int, K=None, noise_seed: int = 0,
+               flags: int = 0):
+    """render() with colour -> (depth, rgb)."""
+    K = K if K is not None else viewer_intrinsics(width, height)
+    T = np.ascontiguousarray(T_wc, np.float64)
+    out = np.zeros((height, width), np.int16)
+    rgb = np.zeros((height, width, 3), np.uint8)
+    load_library().youth_synth_render_rgb(_p(T, c_double), width, height, ctypes.byref(K),
+                                          noise_seed, flags, _p(out, c_int16), _p(rgb, c_uint8))
+    return out, rgb
+
+
+def luma(rgb: np.ndarray) -> np.ndarray:
+    """Y = (77 R + 150 G + 29 B + 128) >> 8, uint8."""
+    c = np.asarray(rgb, np.uint8).astype(np.int32)
+    return ((77 * c[..., 0] + 150 * c[..., 1] + 29 * c[..., 2] + 128) >> 8).astype(np.uint8)

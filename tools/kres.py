@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Per-kernel register use and spills of the HIP translation units
-(icp_kernels, viewer_cloud, voxel_map, map_render, depth_filter) as hipcc reports them
+(icp_kernels with the RGB-D kernels of csrc/rgbd_align.inc at its tail, viewer_cloud,
+voxel_map, map_render, depth_filter) as hipcc reports them
 (-Rpass-analysis=kernel-resource-usage): `python tools/kres.py [filter]`
 compiles each TU for gfx950 with the product flags (object discarded) and
-prints VGPRs / AGPRs / SGPRs / spills / LDS / occupancy per kernel."""
+prints VGPRs / AGPRs / SGPRs / spills / LDS / occupancy per kernel
+(`python tools/kres.py rgbd`: k_rgbd_prep and k_rgbd_reduce, profiles/rgbd/kres_rgbd.txt)."""
 import re
 import subprocess
 import sys
