@@ -25,293 +25,29 @@
 // k_verify_fastdiv has proven it equal to IEEE division on the ENTIRE domain
 // those divides can see (d in [1, 32767], u in [0, W), v in [0, H)); otherwise
 // the IEEE path is compiled in.
+//
+// This unit holds every depth-only __global__ kernel and, after them, the
+// launch layer (icp_host.h): the only code that names these kernels.  The
+// device code shared with rgbd_align.hip is in icp_device.h; the C API is in
+// icp_api.cpp, icp_batch.cpp and icp_track.cpp.
 
 #include <hip/hip_runtime.h>
 
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 
-#include <chrono>
-#include <condition_variable>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <type_traits>
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <vector>
+#include <condition_variable>
+#include <mutex>
 
-#include "host_copy.h"
-#include "youth_icp.h"
+#include "icp_device.h"
+#include "icp_host.h"
 
 namespace {
 
-// ----------------------------------------------------------------- layout --
-// Workspace frame f:
-//   recs + f*P            float4 {z, nx, ny, nz} per pixel (targets);
-//   xyz  + f*3*P (+P, +2P) optional X, Y, Z planes (stage-level API only).
-// P = plane stride = round_up(N + 4, 256); the pad is zeroed once, so a
-// clamped fetch or a float4 load past N reads an invalid point (z = 0).
-// Sources are read straight from the caller's int16 depth.
-constexpr int kTileW = 64;
-// k_prep tiles 128 x 24 by 512-thread workgroups: four per CU fill all 32
-// wave slots (LDS 40.6 KB each).  A 128-px row touches 2 lines of its own
-// and 2 of its neighbours' where a 64-px row touched 1 + 2, so the depth
-// over-fetch drops from 2.8x to 1.9x: k_prep's PMC traffic 1.21 -> 1.105x of
-// its 18 B/px, and 586 -> 582 us per 512 frames (profiles/r04/ab_r4c.txt,
-// prep128x24_pmc.txt).  Also measured: 128 x 16 650 us (1.11x), 256 x 12
-// 747 us (1.07x; three per CU, LDS-limited); earlier 64 x 48 593 us, 64 x 24 by
-// 256 threads 617 us, 64 x 80 / 1024 625 us (profiles/r02/ab_s44.txt,
-// ab_s45.txt); fewer workgroups per CU cost more (ab_s43.txt: 7 -> 6 per CU +8 %)
-constexpr int kPrepThreads = 512;
-// k_prep's own tile (k_icp_coop's fused prep keeps kTileW-wide tiles, whose
-// shape its lane partition and prep counters assume); -D knobs for A/B
-#ifndef YOUTH_PREP_TW
-#define YOUTH_PREP_TW 128
-#endif
-#ifndef YOUTH_PREP_TH
-#define YOUTH_PREP_TH 24
-#endif
-constexpr int kPrepTW = YOUTH_PREP_TW;
-constexpr int kPrepTH = YOUTH_PREP_TH;
-// frames in flight through youth_icp_track_submit (YOUTH_TRACK_MAX_IN_FLIGHT):
-// two one at a time, or two micro-batches of two, so the next submission's
-// host copy and H2D overlap the launch before it
-constexpr int kTrackDepth = YOUTH_TRACK_MAX_IN_FLIGHT;
-constexpr int kLdsW = kTileW + 2;
-
-constexpr int kRedThreads = 256;
-constexpr int kRedStep = kRedThreads * 4;  // pixels per workgroup loop step
-constexpr int kNeq = YOUTH_NEQ;
-// k_icp's chunk partials: rows of 30 doubles (29 + a zero pad, 240 B) so the
-// last arriver reads them as 16-byte pieces; kSumCols interleaved columns of
-// chunks are summed in parallel, then the column sums in column order.
-constexpr int kPartStride = 30;
-constexpr int kPieces = kPartStride / 2;  // 16-byte pieces per row
-constexpr int kSumCols = 16;              // kSumCols * kPieces <= kRedThreads
-// Persistent-queue words (unsigned index into ctx->d_head), one 128-B line
-// apart so the contended dequeue atomic shares no line with the polled flag.
-// k_icp's work queues: up to kMaxQueues heads, kQHeads + 32 q (queue q holds
-// the pairs p = q (mod n_queues)).
-constexpr int kQHead = 0, kQError = 32, kQSpins = 64, kQWaited = 96, kQHeads = 128;
-constexpr int kMaxQueues = 8, kQHeadStride = 32;
-constexpr int kQWords = kQHeads + kMaxQueues * kQHeadStride;
-
-typedef float f4v __attribute__((ext_vector_type(4)));  // a gathered {z, nx, ny, nz} record
-typedef unsigned u4v __attribute__((ext_vector_type(4)));  // two doubles, raw bits
-
-struct Intr {
-    float fx, fy, cx, cy, ds;
-};
-
-// Division by the constants fx, fy, ds in two operations (Brisebarre,
-// Muller & Raina, "Accelerating correctly rounded floating-point division
-// when the divisor is known in advance", IEEE TC 2004): for each divisor y,
-// h = RN(1/y) and l = RN((1 - y h) / y); then q = RN(n h + RN(n l)) =
-// fma(n, h, n * l).  Used only where k_verify_fastdiv finds it equal to IEEE
-// n / y on the whole domain the kernels divide.
-struct FastK {
-    float hfx, lfx, hfy, lfy, hds, lds;
-};
-
-// 64-bit lane helpers (two 32-bit halves)
-__device__ __forceinline__ double join64(unsigned lo, unsigned hi)
-{
-    return __hiloint2double((int)hi, (int)lo);
-}
-__device__ __forceinline__ unsigned lo32(double x) { return (unsigned)__double2loint(x); }
-__device__ __forceinline__ unsigned hi32(double x) { return (unsigned)__double2hiint(x); }
-
-// lane `l`'s value in every lane (wave-uniform l: two v_readlane into SGPRs)
-__device__ __forceinline__ double readlane64(double x, int l)
-{
-    return join64((unsigned)__builtin_amdgcn_readlane((int)lo32(x), l),
-                  (unsigned)__builtin_amdgcn_readlane((int)hi32(x), l));
-}
-
-// fma(n, h, RN(n l)): equal to RN(n / d) wherever k_verify_fastdiv found
-// no mismatch (h, l of the divisor d, FastK).
-__device__ __forceinline__ float div_fast(float n, float h, float l)
-{
-    return fmaf(n, h, n * l);
-}
-
-template <bool kFast>
-__device__ __forceinline__ float bp_div(float n, float d, float h, float l)
-{
-    return kFast ? div_fast(n, h, l) : n / d;
-}
-
-// Spec a7's two projection quotients nu/den and nv/den, IEEE correctly
-// rounded, sharing one reciprocal.  hipcc expands an fp32 a/b (denormals on)
-// to  s = div_scale(b,b,a); n = div_scale(a,b,a); r = rcp(s);
-//     r = fma(fma(-s,r,1), r, r); q = n*r; q = fma(fma(-s,q,n), r, q);
-//     q = div_fmas(fma(-s,q,n), r, q); result = div_fixup(q, b, a)   (`make asm`).
-// For b in [2^-60, 2^60] div_scale rescales neither operand except when a is
-// 0, |a/b| >= ~2^95, |a/b| < 2^-126 or |a| < 2^-103; otherwise div_fmas is a
-// plain fma and div_fixup returns q unchanged, so q = RN(n r) with those two
-// fma corrections equals a/b bit for bit, and its reciprocal part depends on
-// b only (one correction suffices from a correctly rounded r: proj_quot).  In the excepted
-// cases the results differ at most between 0 / tiny / huge / inf / NaN
-// values, which the projection (+cx, +0.5, floor, range test) maps to the same
-// pixel or to "outside".  Callers fall back to a/b when b is out of range.
-// youth_icp_selftest_projdiv compares the two bitwise on random and edge
-// cases (tests/test_gpu_parity.py).
-__device__ __forceinline__ float proj_recip(float den)
-{
-    const float r0 = __builtin_amdgcn_rcpf(den);
-    return fmaf(fmaf(-den, r0, 1.0f), r0, r0);
-}
-__device__ __forceinline__ bool proj_den_ok(float den)
-{
-    return (den >= 0x1p-60f) & (den <= 0x1p60f);
-}
-// Spec a7's projection reciprocal RN(1 / den): for den in [2^-60, 2^60] the
-// hardware reciprocal refined by ONE Newton step, fma(fma(-den, r0, 1), r0,
-// r0) (proj_recip), is already the correctly rounded 1.0f / den: measured
-// for EVERY fp32 den in that range (tools/rcp_probe.hip,
-// profiles/r02/rcp_probe.txt: 0 of 1,006,632,961 differ; the two further
-// quotient corrections used before changed nothing), and re-checked by
-// youth_icp_selftest_projdiv (tests/test_gpu_parity.py).  Outside: IEEE.
-__device__ __forceinline__ float proj_rcp_rn(float den)
-{
-    if (proj_den_ok(den))  // always in practice (den is a depth in metres)
-        return proj_recip(den);
-    return 1.0f / den;
-}
-
-// Which arithmetic spec a7/a8 runs in (youth_icp_set_spec):
-//   kSpecSurvey (default) SURVEY.md §8a a7/a8 + §7 literally: separately
-//               rounded products and sums in a fixed order (no FMA) and the
-//               projection quotient fx P'x / P'z as an IEEE division;
-//   kSpecFma    opt-in: fma chains and one correctly rounded reciprocal.
-// The oracle restates both (oracle_set_spec); every kernel of the iteration
-// (k_icp, k_icp_coop, k_reduce) is instantiated for each.
-constexpr int kSpecFma = YOUTH_SPEC_FMA;
-constexpr int kSpecSurvey = YOUTH_SPEC_SURVEY;
-// ... and for each reduction of spec a9 (youth_icp_set_reduce):
-//   lane32 (default) SURVEY.md §8a a9 as worded, "fp32 lanes -> fp64
-//          finalize": each lane sums its pixels' 28 products with v_fma_f32
-//          over its whole share of a work item, then converts once;
-//   exact  every product exact in fp64 (v_fmac_f64 per product).
-// The kernels' template parameter kSp is the VARIANT: bit 0 the arithmetic
-// (kSpecFma / kSpecSurvey), bit 1 (kRedLane32) the lane32 reduction.
-constexpr int kRedLane32 = 2;
-constexpr int kVariants = 4;
-__host__ __device__ constexpr bool sp_survey(int v) { return (v & 1) == kSpecSurvey; }
-__host__ __device__ constexpr bool sp_lane32(int v) { return (v & kRedLane32) != 0; }
-
-// kSpecSurvey's projection quotient RN(n / den) from r = RN(1 / den)
-// (proj_recip inside proj_den_ok: correctly rounded, checked exhaustively):
-// q0 = RN(n r) is within one ulp of n / den, the remainder n - den q0 is
-// exact in one fma, and one correction q0 + (n - den q0) r rounds to
-// RN(n / den) (Markstein, IBM J. Res. Dev. 34(1), 1990, Theorem 1; barring
-// under/overflow of the remainder, which only happens for quotients that
-// project to the same pixel or off the frame).  hipcc's a/b applies two
-// such corrections; youth_icp_selftest_projquot compares this one with
-// IEEE a/b bitwise and through the projection (tests/test_gpu_parity.py).
-__device__ __forceinline__ float proj_quot(float n, float den, float r)
-{
-    const float q0 = n * r;
-    return fmaf(fmaf(-den, q0, n), r, q0);
-}
-
-// (int)floorf(x) in one instruction (v_cvt_flr_i32_f32; floorf + the int
-// conversion are two 4-cycle VALU forms, profiles/r03/valu_cycles.txt).
-// Equal to (int)floorf(x) for every normal or zero x with |x| < 2^30, and
-// (unsigned) of it < 16384 exactly when 0 <= floorf(x) < 16384 for every
-// non-NaN x but denormals (saturating conversion): youth_icp_selftest_projquot
-// checks both over all 2^32 bit patterns.  kSpecSurvey's projected
-// coordinate ((q + c) + 0.5) is never NaN (T finite, q finite or +-inf) and
-// never denormal (it is 0 or at least 2^-25 in magnitude: s + 0.5 with s a
-// float near -0.5 is exact by Sterbenz, |s| < 0.25 leaves it above 0.25).
-__device__ __forceinline__ int floor_i32(float x)
-{
-    int r;
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
-
-// Spec a6's normalisation n = c / sqrtf(|c|^2) on its common range, bit for
-// bit.  hipcc's correctly rounded sqrtf is  x' = x < 2^-96 ? x 2^32 : x;
-// s = v_sqrt(x'); s -= (fma(-(s-1ulp), s, x') <= 0); s += (fma(-(s+1ulp), s,
-// x') > 0); unscale; return x for +-0 / +inf (`make asm`).  For x in
-// [2^-96, 2^118] the scaling and the class fix-up are identities, leaving
-// the sequence below.  The three quotients then share one reciprocal
-// (norm_div): len = sqrt(x) is in [2^-48, 2^59] and |c_i| <= ~len, so
-// div_scale rescales no operand when |c_i| >= 2^-64; c_i = 0
-// is exact through the sign: RN(c/len) = copysign(RN(|c|/len), c).  Callers
-// take the IEEE expressions when norm_fast_ok is false.
-// youth_icp_selftest_normalize checks both against IEEE on device.
-__device__ __forceinline__ float sqrt_rn_mid(float x)
-{
-    const float s = __builtin_amdgcn_sqrtf(x);
-    const float sdn = __uint_as_float(__float_as_uint(s) - 1u);
-    const float sup = __uint_as_float(__float_as_uint(s) + 1u);
-    const float t = fmaf(-sdn, s, x) <= 0.0f ? sdn : s;
-    return fmaf(-sup, s, x) > 0.0f ? sup : t;
-}
-__device__ __forceinline__ bool norm_comp_ok(float c)
-{
-    return !((fabsf(c) < 0x1p-64f) & (c != 0.0f));
-}
-__device__ __forceinline__ bool norm_fast_ok(float len2, float cx, float cy, float cz)
-{
-    return (len2 >= 0x1p-96f) && (len2 <= 0x1p118f) && norm_comp_ok(cx) && norm_comp_ok(cy) &&
-           norm_comp_ok(cz);
-}
-// The three quotients take ONE correction from the correctly rounded
-// reciprocal r = RN(1 / len) (proj_recip; len in [2^-48, 2^59]), as the
-// projection's proj_quot (Markstein's theorem; youth_icp_selftest_normalize
-// compares with IEEE c / sqrtf(len2) bitwise).
-__device__ __forceinline__ float norm_div(float c, float len, float r)
-{
-    return copysignf(proj_quot(fabsf(c), len, r), c);
-}
-// norm_fast_ok on the bits, for k_prep: len2 (>= +0 or NaN) in [2^-96,
-// 2^118] as one unsigned compare; a component c is "tiny" (0 < |c| < 2^-64)
-// iff t = 2 bits(c) - 2 (sign shifted out, wrapping: +-0 -> 2^32 - 2) is
-// below 2 bits(2^-64) - 2, so the three tests are one min3 and one compare.
-// The self-test checks it equals norm_fast_ok on every random vector.
-__device__ __forceinline__ bool norm_fast_ok_bits(float len2, float cx, float cy, float cz)
-{
-    constexpr unsigned kLo = 0x0F800000u, kHi = 0x7A800000u, kTiny = 2u * 0x1F800000u - 2u;
-    const unsigned tx = (__float_as_uint(cx) << 1) - 2u, ty = (__float_as_uint(cy) << 1) - 2u,
-                   tz = (__float_as_uint(cz) << 1) - 2u;
-    return (int)((__float_as_uint(len2) - kLo) <= (kHi - kLo)) & (int)(min(min(tx, ty), tz) >= kTiny);
-}
-
-// viewerModule.c:341-345 with explicit intrinsics (bit-identical to the
-// viewer for cx = W/2, cy = H/2, f = 570.3f, ds = 1000.0f):
-//   valid iff d > 0;  z = d / ds;  x = ((u - cx) z) / fx;  y = ((v - cy) z) / fy
-template <bool kFast>
-__device__ __forceinline__ void backproject(int d, int u, int v, const Intr& K,
-                                            const FastK& F, float& x, float& y, float& z)
-{
-    const float zz = bp_div<kFast>((float)max(d, 0), K.ds, F.hds, F.lds);  // d <= 0: 0/ds = +0
-    x = bp_div<kFast>(((float)u - K.cx) * zz, K.fx, F.hfx, F.lfx);
-    y = bp_div<kFast>(((float)v - K.cy) * zz, K.fy, F.hfy, F.lfy);
-    z = zz;
-}
-// The same with the centred pixel coordinates uc = (float)u - cx and
-// vc = (float)v - cy supplied (exact: integers below 2^24), so a caller
-// walking a row forms them by additions.
-template <bool kFast>
-__device__ __forceinline__ void backproject_c(int d, float uc, float vc, const Intr& K,
-                                              const FastK& F, float& x, float& y, float& z)
-{
-    const float zz = bp_div<kFast>((float)max(d, 0), K.ds, F.hds, F.lds);
-    x = bp_div<kFast>(uc * zz, K.fx, F.hfx, F.lfx);
-    y = bp_div<kFast>(vc * zz, K.fy, F.hfy, F.lfy);
-    z = zz;
-}
-
+// -------------------------------------------------- self-checks on device --
 // Exhaustive check of div_fast against IEEE division over the whole
 // back-projection domain: z = d/ds (d in [1, 32767]); ((u - cx) z)/fx
 // (u in [0, W)); ((v - cy) z)/fy (v in [0, H)).  Also covers the target
@@ -817,219 +553,8 @@ __global__ __launch_bounds__(kPrepThreads) void k_prep(const int16_t* __restrict
 }
 
 // ----------------------------------------------------------------- k_solve --
-// Spec a10 (round 5): A x = b by block elimination with 3x3 adjugates, xi =
-// -x; the same correctly rounded operations in the same order as
-// oracle_solve (oracle/icp_oracle.c), so xi and the status are bit-identical.
-// With P = A[0..2][0..2] (rotation), Q = A[0..2][3..5], R = A[3..5][3..5],
-// b = (b1, b2), C = adj(P):
-//   detP = P00 C00 + P01 C01 + P02 C02, M = C Q, u = C b1
-//   S' = detP R - Q^T M (detP times the Schur complement), y' = detP b2 - Q^T u
-//   x2 = adj(S') y' * (1 / det S'),  x1 = C (b1 - Q x2) * (1 / detP)
-// ONE division on the dependent chain (1 / detP runs beside it) and no value
-// crosses lanes, against LDL^T's six dependent reciprocals and lane
-// broadcasts (tools/solvebench).  The rotation block goes first,
-// as LDL^T's pivot order does: eliminating the translation block first was
-// faster on paper but 2-3x more sensitive to the sums' last bits on
-// ill-conditioned frames.  DEGENERATE iff an LDL^T pivot is
-// <= 1e-12 max diag, tested on the leading minors by products.
-__device__ __forceinline__ double dd2(double a, double b, double c, double d)
-{
-    return fma(a, b, -(c * d));  // a b - c d
-}
-__device__ __forceinline__ double dot3(double a0, double b0, double a1, double b1, double a2,
-                                       double b2)
-{
-    return fma(a2, b2, fma(a1, b1, a0 * b0));
-}
-// symmetric 3x3 {m00, m01, m02, m11, m12, m22}: adjugate, matrix-vector
-__device__ __forceinline__ void adj3(const double* p, double* c)
-{
-    c[0] = dd2(p[3], p[5], p[4], p[4]);
-    c[1] = dd2(p[2], p[4], p[1], p[5]);
-    c[2] = dd2(p[1], p[4], p[2], p[3]);
-    c[3] = dd2(p[0], p[5], p[2], p[2]);
-    c[4] = dd2(p[1], p[2], p[0], p[4]);
-    c[5] = dd2(p[0], p[3], p[1], p[1]);
-}
-__device__ __forceinline__ void symv3(const double* c, const double* v, double* o)
-{
-    o[0] = dot3(c[0], v[0], c[1], v[1], c[2], v[2]);
-    o[1] = dot3(c[1], v[0], c[3], v[1], c[4], v[2]);
-    o[2] = dot3(c[2], v[0], c[4], v[1], c[5], v[2]);
-}
-// neq wave-uniform (LDS or registers); every lane computes everything, so no
-// value crosses lanes.  xi is zeroed on a nonzero status.
-__device__ __forceinline__ int solve_block6(const double* neq, double xi[6])
-{
-#pragma unroll
-    for (int i = 0; i < 6; ++i) xi[i] = 0.0;
-    if (!(neq[28] >= 6.0)) return YOUTH_STATUS_FEW_MATCHES;
-    double maxd = 0.0;  // the diagonal, in order (a, a) = 0, 6, 11, 15, 18, 20
-    maxd = neq[0] > maxd ? neq[0] : maxd;
-    maxd = neq[6] > maxd ? neq[6] : maxd;
-    maxd = neq[11] > maxd ? neq[11] : maxd;
-    maxd = neq[15] > maxd ? neq[15] : maxd;
-    maxd = neq[18] > maxd ? neq[18] : maxd;
-    maxd = neq[20] > maxd ? neq[20] : maxd;
-    if (!(maxd > 0.0)) return YOUTH_STATUS_DEGENERATE;
-    const double eps = 1e-12 * maxd;
-    const double P[6] = {neq[0], neq[1], neq[2], neq[6], neq[7], neq[11]};
-    const double R[6] = {neq[15], neq[16], neq[17], neq[18], neq[19], neq[20]};
-    const double Q[3][3] = {{neq[3], neq[4], neq[5]}, {neq[8], neq[9], neq[10]},
-                            {neq[12], neq[13], neq[14]}};
-    const double b1[3] = {neq[21], neq[22], neq[23]}, b2[3] = {neq[24], neq[25], neq[26]};
-    double C[6], E[6], S[6], M[3][3], u[3], y[3], v[3], x2[3], w[3];
-    adj3(P, C);
-    const double detP = dot3(P[0], C[0], P[1], C[1], P[2], C[2]);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {  // M = C Q, column by column
-        const double q[3] = {Q[0][j], Q[1][j], Q[2][j]};
-        double o[3];
-        symv3(C, q, o);
-        M[0][j] = o[0];
-        M[1][j] = o[1];
-        M[2][j] = o[2];
-    }
-    symv3(C, b1, u);
-    // S' upper triangle (i <= j): detP R[i][j] - (Q^T M)[i][j]
-    S[0] = fma(detP, R[0], -dot3(Q[0][0], M[0][0], Q[1][0], M[1][0], Q[2][0], M[2][0]));
-    S[1] = fma(detP, R[1], -dot3(Q[0][0], M[0][1], Q[1][0], M[1][1], Q[2][0], M[2][1]));
-    S[2] = fma(detP, R[2], -dot3(Q[0][0], M[0][2], Q[1][0], M[1][2], Q[2][0], M[2][2]));
-    S[3] = fma(detP, R[3], -dot3(Q[0][1], M[0][1], Q[1][1], M[1][1], Q[2][1], M[2][1]));
-    S[4] = fma(detP, R[4], -dot3(Q[0][1], M[0][2], Q[1][1], M[1][2], Q[2][1], M[2][2]));
-    S[5] = fma(detP, R[5], -dot3(Q[0][2], M[0][2], Q[1][2], M[1][2], Q[2][2], M[2][2]));
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-        y[j] = fma(detP, b2[j], -dot3(Q[0][j], u[0], Q[1][j], u[1], Q[2][j], u[2]));
-    adj3(S, E);
-    const double detS = dot3(S[0], E[0], S[1], E[1], S[2], E[2]);
-    const double epsP = eps * detP;
-    // pivots P00, C22/P00, detP/C22, S'00/detP, E22/(detP S'00), detS/(detP E22)
-    const bool ok = (P[0] > eps) & (C[5] > eps * P[0]) & (detP > eps * C[5]) & (S[0] > epsP) &
-                    (E[5] > epsP * S[0]) & (detS > epsP * E[5]);
-    if (!ok) return YOUTH_STATUS_DEGENERATE;
-    const double rS = 1.0 / detS, rP = 1.0 / detP;
-    symv3(E, y, v);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) x2[i] = v[i] * rS;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) w[i] = b1[i] - dot3(Q[i][0], x2[0], Q[i][1], x2[1], Q[i][2], x2[2]);
-    symv3(C, w, v);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        xi[i] = -(v[i] * rP);
-        xi[3 + i] = -x2[i];
-    }
-    return 0;
-}
-
-__device__ void se3_exp_left(const double xi[6], double* T)
-{
-    const double wx = xi[0], wy = xi[1], wz = xi[2];
-    const double th2 = (wx * wx + wy * wy) + wz * wz;
-    double a, b, c;
-    if (th2 < 0x1p-7) {  // spec a10: Taylor in th2 (oracle_se3_exp: same fma chain)
-        const double x = th2;
-        a = fma(x, fma(x, fma(x, fma(x, fma(x, -0x1.ae64567f544e4p-26, 0x1.71de3a556c734p-19),
-                                        -0x1.a01a01a01a01ap-13), 0x1.1111111111111p-7),
-                       -0x1.5555555555555p-3), 0x1.0000000000000p+0);
-        b = fma(x, fma(x, fma(x, fma(x, fma(x, -0x1.1eed8eff8d898p-29, 0x1.27e4fb7789f5cp-22),
-                                        -0x1.a01a01a01a01ap-16), 0x1.6c16c16c16c17p-10),
-                       -0x1.5555555555555p-5), 0x1.0000000000000p-1);
-        c = fma(x, fma(x, fma(x, fma(x, fma(x, -0x1.6124613a86d09p-33, 0x1.ae64567f544e4p-26),
-                                        -0x1.71de3a556c734p-19), 0x1.a01a01a01a01ap-13),
-                       -0x1.1111111111111p-7), 0x1.5555555555555p-3);
-    } else {
-        const double th = sqrt(th2);
-        double s, co;
-        sincos(th, &s, &co);
-        a = s / th;
-        b = (1.0 - co) / th2;
-        c = (th - s) / (th2 * th);
-    }
-    const double Km[3][3] = {{0.0, -wz, wy}, {wz, 0.0, -wx}, {-wy, wx, 0.0}};
-    double K2[3][3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j)
-            K2[i][j] = (Km[i][0] * Km[0][j] + Km[i][1] * Km[1][j]) + Km[i][2] * Km[2][j];
-    double E[3][4];
-    for (int i = 0; i < 3; ++i) {
-        double V[3];
-        for (int j = 0; j < 3; ++j) {
-            const double I = (i == j) ? 1.0 : 0.0;
-            E[i][j] = (I + a * Km[i][j]) + b * K2[i][j];
-            V[j] = (I + b * Km[i][j]) + c * K2[i][j];
-        }
-        E[i][3] = (V[0] * xi[3] + V[1] * xi[4]) + V[2] * xi[5];
-    }
-    double O[12];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 4; ++j) {
-            double s = (E[i][0] * T[0 * 4 + j] + E[i][1] * T[1 * 4 + j]) + E[i][2] * T[2 * 4 + j];
-            if (j == 3) s += E[i][3];
-            O[i * 4 + j] = s;
-        }
-    for (int i = 0; i < 12; ++i) T[i] = O[i];
-}
-
-// Spec a10 by ONE wave (all 64 lanes call it): solve_block6 in every lane
-// (wave-uniform, no cross-lane traffic), then se3_exp_left with its
-// per-element operations and order, lane l < 12 computing output entry
-// (l / 4, l % 4) of exp(xi^) T.  neq (LDS, kNeq): the pair's sums; T64 (LDS,
-// 12): pose in/out; T32 (LDS, 12): fp32 copy out.  Returns the status bits;
-// the pose is updated only when they are 0.
-__device__ __forceinline__ int solve_update_wave(const double* neq, double* T64, float* T32, int lane)
-{
-    double xi[6];
-    const int st = solve_block6(neq, xi);
-    if (st) return st;
-
-    // T <- exp(xi^) T (se3_exp_left), one output entry per lane
-    const double wx = xi[0], wy = xi[1], wz = xi[2];
-    const double th2 = (wx * wx + wy * wy) + wz * wz;
-    double a, b, c;
-    if (th2 < 0x1p-7) {  // spec a10: Taylor in th2 (oracle_se3_exp: same fma chain)
-        const double x2 = th2;
-        a = fma(x2, fma(x2, fma(x2, fma(x2, fma(x2, -0x1.ae64567f544e4p-26, 0x1.71de3a556c734p-19),
-                                          -0x1.a01a01a01a01ap-13), 0x1.1111111111111p-7),
-                        -0x1.5555555555555p-3), 0x1.0000000000000p+0);
-        b = fma(x2, fma(x2, fma(x2, fma(x2, fma(x2, -0x1.1eed8eff8d898p-29, 0x1.27e4fb7789f5cp-22),
-                                          -0x1.a01a01a01a01ap-16), 0x1.6c16c16c16c17p-10),
-                        -0x1.5555555555555p-5), 0x1.0000000000000p-1);
-        c = fma(x2, fma(x2, fma(x2, fma(x2, fma(x2, -0x1.6124613a86d09p-33, 0x1.ae64567f544e4p-26),
-                                          -0x1.71de3a556c734p-19), 0x1.a01a01a01a01ap-13),
-                        -0x1.1111111111111p-7), 0x1.5555555555555p-3);
-    } else {
-        const double th = sqrt(th2);
-        double sn, co;
-        sincos(th, &sn, &co);
-        a = sn / th;
-        b = (1.0 - co) / th2;
-        c = (th - sn) / (th2 * th);
-    }
-    const double Km[3][3] = {{0.0, -wz, wy}, {wz, 0.0, -wx}, {-wy, wx, 0.0}};
-    const int l = lane < 12 ? lane : 11;
-    const int r = l >> 2, col = l & 3;
-    double Kr[3];  // row r of Km
-#pragma unroll
-    for (int k = 0; k < 3; ++k) Kr[k] = r == 0 ? Km[0][k] : (r == 1 ? Km[1][k] : Km[2][k]);
-    double Er[3], Vr[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double K2 = (Kr[0] * Km[0][k] + Kr[1] * Km[1][k]) + Kr[2] * Km[2][k];
-        const double I = (r == k) ? 1.0 : 0.0;
-        Er[k] = (I + a * Kr[k]) + b * K2;
-        Vr[k] = (I + b * Kr[k]) + c * K2;
-    }
-    const double Er3 = (Vr[0] * xi[3] + Vr[1] * xi[4]) + Vr[2] * xi[5];
-    double o = (Er[0] * T64[0 * 4 + col] + Er[1] * T64[1 * 4 + col]) + Er[2] * T64[2 * 4 + col];
-    if (col == 3) o += Er3;
-    if (lane < 12) {
-        T64[lane] = o;
-        T32[lane] = (float)o;
-    }
-    return 0;
-}
+// Spec a10 on one wave per pair; the solve itself is icp_device.h's
+// solve_update.
 
 // Out-of-line copy for k_icp: inlined there, the solve's loop-invariant
 // constants are hoisted into the kernel prologue and spilled across the
@@ -1060,20 +585,6 @@ __device__ __forceinline__ void sum_partials(const double* __restrict__ part, in
     __syncthreads();
 }
 
-__device__ __forceinline__ void solve_update(const double* neq, double* T64, float* T32,
-                                             int32_t* status)
-{
-    double xi[6];
-    const int st = solve_block6(neq, xi);
-    double T[16];
-    for (int i = 0; i < 16; ++i) T[i] = T64[i];
-    if (st == 0) se3_exp_left(xi, T);
-    for (int i = 0; i < 12; ++i) {
-        T64[i] = T[i];
-        T32[i] = (float)T[i];
-    }
-    *status |= st;
-}
 
 // grid n_pairs, one wave each.
 __global__ __launch_bounds__(64) void k_solve(const double* __restrict__ partials,
@@ -1152,25 +663,6 @@ __global__ void k_init(const double* __restrict__ T_init, int n, double* T64, fl
 // fp32 products: the result equals the oracle's row-major fp64 sum up to
 // fp64 summation order.  (tools/kbench: 205 us for the first SoA version ->
 // 107 us for this one at 64 pairs, partial sums unchanged.)
-struct PairMap {
-    int src0, tgt0;  // pair p: source depth frame src0 + p, target record frame tgt0 + p
-};
-
-template <bool kAligned>
-__device__ __forceinline__ short4 load_depth4(const int16_t* __restrict__ sD, int i, int end)
-{
-    // i < end always here; kAligned => i % 4 == 0 and i + 3 < end
-    short4 d;
-    if (kAligned) {
-        d = *reinterpret_cast<const short4*>(sD + i);
-    } else {
-        d.x = sD[i];
-        d.y = (i + 1) < end ? sD[i + 1] : (short)0;
-        d.z = (i + 2) < end ? sD[i + 2] : (short)0;
-        d.w = (i + 3) < end ? sD[i + 3] : (short)0;
-    }
-    return d;
-}
 
 // Per-iteration pose state for the fused solve (kFuse).  T32 is read by
 // every workgroup of pair p at entry and rewritten only by p's LAST
@@ -1196,18 +688,6 @@ struct PoseState {
 //   kSpecSurvey: P'_i = ((R_i0 x + R_i1 y) + R_i2 z) + t_i and
 //       u' = floor(((fx P'_x) / P'_z + cx) + 0.5), the
 //       quotient IEEE (proj_quot on the shared correctly rounded reciprocal).
-// Lane masks (one bit per lane of the wave, bit set only on active lanes):
-// compares go straight to SGPR masks (v_cmp), combine on the scalar unit and
-// feed selects through inverse_ballot, and a wave's match count is one
-// s_bcnt1; a per-lane boolean would be rebuilt from a 0/1 select and a
-// compare wherever it is counted (two 4-cycle VALU forms per pixel).
-typedef unsigned long long LaneMask;
-constexpr int kFcmpOgt = 2, kFcmpOlt = 4, kIcmpUlt = 36, kIcmpUle = 37;
-__device__ __forceinline__ LaneMask mask_gt(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kFcmpOgt); }
-__device__ __forceinline__ LaneMask mask_lt(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kFcmpOlt); }
-__device__ __forceinline__ LaneMask mask_ult(unsigned a, unsigned b) { return __builtin_amdgcn_uicmp(a, b, kIcmpUlt); }
-__device__ __forceinline__ LaneMask mask_ule(unsigned a, unsigned b) { return __builtin_amdgcn_uicmp(a, b, kIcmpUle); }
-__device__ __forceinline__ bool lane_in(LaneMask m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 
 template <int kSp>
 __device__ __forceinline__ void xform_project(const float* T, float sx, float sy, float sz,
@@ -1465,55 +945,7 @@ __device__ __forceinline__ void accumulate_chunk(const int16_t* __restrict__ sD,
     acc[28] += (threadIdx.x & 63) == 0 ? (double)cnt : 0.0;
 }
 
-// Wave sum of the kNeq per-lane accumulators by recursive halving: at lane
-// mask m = 32, 16, 8, 4, 2 each lane keeps one half of its remaining values
-// (the upper half iff lane & m) and sends the other half to lane ^ m, so the
-// fp64 exchanges number 16 + 8 + 4 + 2 + 1 + 1 = 32 instead of 29 x 6 for a
-// symmetric butterfly.  On exit lane 2q and 2q+1 both hold the wave total of
-// value q (q < kNeq); the summation tree is fixed, so results are
-// deterministic.  Shared by k_reduce, k_icp and k_icp_coop.
-//   m = 32, 16: v_permlane32_swap / v_permlane16_swap exchange the upper
-//     half-wave (odd rows) of one register with the lower half (even rows) of
-//     another.  With vdst = v[q] and src = v[q+h], each lane is left holding
-//     the value it keeps in one register and its partner's send in the other,
-//     so v[q] = D + S with no select (keep + recv, commutative: bitwise the
-//     same as the shuffle form).
-//   m = 8, 2, 1: DPP (row_ror:8, quad_perm) moves; m = 4: ds_swizzle xor.
-// No LDS bpermute; the partners (lane ^ m) and the add order are unchanged,
-// so the sums are bit-identical to the shuffle form.
-template <int kM>
-__device__ __forceinline__ double xchg_small(double x)
-{
-    int lo = (int)lo32(x), hi = (int)hi32(x);
-    if (kM == 8) {
-        lo = __builtin_amdgcn_update_dpp(0, lo, 0x128, 0xf, 0xf, false);  // row_ror:8
-        hi = __builtin_amdgcn_update_dpp(0, hi, 0x128, 0xf, 0xf, false);
-    } else if (kM == 4) {
-        lo = __builtin_amdgcn_ds_swizzle(lo, 0x1F | (4 << 10));  // bit mode, xor 4
-        hi = __builtin_amdgcn_ds_swizzle(hi, 0x1F | (4 << 10));
-    } else if (kM == 2) {
-        lo = __builtin_amdgcn_update_dpp(0, lo, 0x4E, 0xf, 0xf, false);  // quad_perm [2,3,0,1]
-        hi = __builtin_amdgcn_update_dpp(0, hi, 0x4E, 0xf, 0xf, false);
-    } else {
-        lo = __builtin_amdgcn_update_dpp(0, lo, 0xB1, 0xf, 0xf, false);  // quad_perm [1,0,3,2]
-        hi = __builtin_amdgcn_update_dpp(0, hi, 0xB1, 0xf, 0xf, false);
-    }
-    return join64((unsigned)lo, (unsigned)hi);
-}
-
-template <int kM>
-__device__ __forceinline__ void rs_stage_small(double* v, int lane)
-{
-    constexpr int h = kM / 2;
-    const bool up = (lane & kM) != 0;
-#pragma unroll
-    for (int q = 0; q < h; ++q) {
-        const double send = up ? v[q] : v[q + h];
-        const double keep = up ? v[q + h] : v[q];
-        v[q] = keep + xchg_small<kM>(send);
-    }
-}
-
+// The wave reduce-scatter of the kNeq sums (stages and order: icp_device.h).
 __device__ __forceinline__ void wave_reduce_scatter(const double* acc, int lane, double& total)
 {
     double v[32];
@@ -2025,33 +1457,6 @@ __global__ __launch_bounds__(kRedThreads, 4) void k_icp(const int16_t* __restric
 // tiles before it first waits (a timed-out launch still leaves complete
 // records), and the tracker realigns a timed-out frame
 // (youth_icp_track_realign: the same plan again, then the persistent k_icp).
-constexpr int kCoopShardStride = 32;  // words: one 128-B line per counter
-constexpr int kCoopMaxPx = 32;       // source pixels per lane (LDS: 3 x 32 KB)
-constexpr int kCoopMaxPairs = 16;
-constexpr int kCoopBufs = 3;         // partial-row buffers per arena (iteration k % 3)
-constexpr unsigned kPartEmptyHi = 0x7FF7A5A5u;  // EMPTY = 0x7FF7A5A5'7FF7A5A5 (a signalling NaN)
-constexpr unsigned long long kPartEmpty = 0x7FF7A5A57FF7A5A5ull;
-// counter set layout (words): timeout word (one line) | [pair][shard][32]
-// prep-done counters: workgroup c of a pair arrives on shard c % 8 (one
-// 128-B line each), so no line takes more than ~G/8 of the pair's arrivals
-// (MI355X_MICROARCH.md "fanin": 255 arrivals on one word take 3.2 us)
-constexpr int kCoopPrepShards = 8;
-constexpr int kCoopErrWord = 0;
-constexpr int kCoopPrepWords = kCoopErrWord + kCoopShardStride;
-constexpr int kCoopPrepPair = kCoopPrepShards * kCoopShardStride;  // words per pair
-constexpr int kCoopSetWords = kCoopPrepWords + kCoopMaxPairs * kCoopPrepPair;
-constexpr int kCoopTileH = 24;  // fused prep tiles: 64 x 24 pixels (one per workgroup of a 640x480 pair: 200 tiles, G = 200)
-constexpr int kCoopTileHTall = 80;  // 64 x 80 (= 10 px per lane x 512: one per workgroup of a 1280x960 pair, G = 240)
-// Polls before a wait gives up (~0.5-1 us each: ~35-65 ms).  A wait of a
-// co-resident grid ends within microseconds; one that reaches the bound has
-// a workgroup that never started (the grid is not co-resident: another
-// process holds CUs), and the tracker's realign then runs after one stalled
-// frame instead of a stall of seconds (round 6; 2^22 polls, ~4 s, before).
-// The bound counts polls, not time: a wave that is preempted does not poll.
-// (A bound chosen per iteration, short for iteration 0 only, cost C2 1.9 %:
-// profiles/r06/coop_spin_bound_ab_r6j.txt.)
-constexpr unsigned kCoopSpinMax = 1u << 16;
-constexpr int kCoopMaxChain = YOUTH_TRACK_MAX_BATCH;  // frames per tracker micro-batch
 
 struct CoopState {
     const double* T_init;  // [pair][16] or null (identity)
@@ -2603,167 +2008,12 @@ __global__ void k_status_out(const int32_t* __restrict__ status, int n,
 
 }  // namespace
 
-// =============================================================== host side ==
+// ============================================================ launch layer ==
+// Declared in icp_host.h; `static` what only this unit uses.
 
-static thread_local std::string g_last_error;
+namespace youth_icp {
 
-__attribute__((format(printf, 2, 3))) static int set_error(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                    \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess)                                                            \
-            return set_error(YOUTH_EHIP, "%s (line %d)", hipGetErrorString(e_), __LINE__); \
-    } while (0)
-
-struct EventPair {
-    hipEvent_t a, b;
-    int kind;
-};
-
-struct youth_icp_ctx {
-    int device = 0;
-    int W = 0, H = 0, N = 0;
-    size_t P = 0;
-    int max_frames = 0;
-    Intr K{};
-    FastK F{};
-    bool fast = false;  // verified 2-op back-projection division
-    bool centred_exact = true;  // aligned loop's centred columns exact (centred_exact)
-    int spec = kSpecSurvey;  // spec a7/a8 arithmetic (youth_icp_set_spec, YOUTH_ICP_SPEC)
-    youth_icp_params prm{};
-    hipStream_t stream = nullptr;
-
-    int16_t* d_depth = nullptr;  // [max_frames][N] staging for host-side APIs
-    float4* d_rec = nullptr;     // [max_frames][P] target records {z, nx, ny, nz}
-    float* d_xyz = nullptr;      // [max_frames][3][P] (lazy: stage-level API only)
-    double* d_T64 = nullptr;     // [max_frames][16]
-    float* d_T32 = nullptr;      // [max_frames][12]
-    int32_t* d_status = nullptr; // [max_frames]
-    double* d_Tinit = nullptr;   // [max_frames][16]
-    double* d_stats = nullptr;   // [max_frames][stats_iters][2]
-    int stats_iters = 0;
-    double* d_partials = nullptr;
-    size_t partials_cap = 0;  // doubles
-    double* d_neq = nullptr;  // [max_frames][29]
-    int32_t* d_assoc = nullptr;
-    float* d_Tout = nullptr;  // [max_frames][16]
-    unsigned* d_flag = nullptr;
-    unsigned* d_arrivals = nullptr;  // [max_frames] fused-solve arrival counters
-    unsigned* d_arr_it = nullptr;    // [max_frames][stats_iters] persistent arrival tickets
-    unsigned* d_epoch = nullptr;     // [max_frames] persistent pose epochs
-    unsigned* d_head = nullptr;      // queue words kQHead / kQError / kQSpins / kQWaited
-    bool persistent = true;          // one k_icp launch per align (else per-iteration k_reduce)
-    int reduce = YOUTH_REDUCE_EXACT; // spec a9 (youth_icp_set_reduce, YOUTH_ICP_REDUCE)
-    youth_lanes lanes{};             // lane partition of the last align's iterations
-    bool has_lanes = false;
-    bool lanes_mixed = false;        // the last host batch call ran more than one partition
-    int icp_blocks_per_cu[4 * kVariants] = {};  // occupancy of k_icp<variant, fast, aligned> [variant 4 + fast 2 + aligned]
-    int n_cu = 0;
-    // small batches: k_icp_coop (youth_icp_create reads the knobs)
-    bool coop = true;                // YOUTH_ICP_NO_COOP=1 disables
-    int coop_px = 0;                 // YOUTH_ICP_COOP_PX: force pixels per lane (0: plan)
-    int coop_px_env = 0;             // coop_px outside the tracker's batch mode
-    int coop_threads = 512;          // YOUTH_ICP_COOP_THREADS=256: one wave per SIMD
-    int coop_max_pairs = kCoopMaxPairs;  // YOUTH_ICP_COOP_MAX_PAIRS (<= kCoopMaxPairs)
-    int coop_launch = 0;             // YOUTH_ICP_COOP_LAUNCH: 0 serial (default), 1 runtime, 2 plain
-    bool trk_copy_compute = false;   // YOUTH_ICP_TRACK_COPY=compute: tracker H2D on the launch stream
-    bool trk_copy_sdma = false;      // YOUTH_ICP_TRACK_COPY=sdma: hipMemcpyAsync, not k_pull_frames
-    int trk_pull_wg = 0;             // YOUTH_ICP_PULL_WG: k_pull_frames workgroups per frame (0: auto)
-    int trk_pull_lds = 48 << 10;     // YOUTH_ICP_PULL_LDS: LDS bytes a k_pull_frames workgroup reserves
-    int trk_pull_reserve = 32;       // YOUTH_ICP_PULL_RESERVE_CU: CUs a micro-batch plan leaves free
-    // staging copies of host frames (track_submit_batch / track_host_sequence):
-    // split over the submitting thread and trk_copy_helpers persistent threads
-    // once a submission holds trk_copy_min bytes (host_copy.h); the pool starts
-    // with the first such submission
-    int trk_copy_helpers = 3;        // YOUTH_ICP_COPY_THREADS: helper threads (0: one thread copies)
-    size_t trk_copy_min = 1u << 20;  // bytes per submission from which the copy is split
-    std::unique_ptr<youth::HostCopyPool> copy_pool;
-    bool coop_refuse = false;       // YOUTH_ICP_TEST_REFUSE_COOP=1 (test hook)
-    // occupancy of k_icp_coop<variant, fast, threads> [threads 256?][variant 2 + fast] at npx (LDS)
-    int coop_bpc[2][2 * kVariants][kCoopMaxPx + 1] = {};
-    int coop_bpc_tall[2 * kVariants] = {};  // the 64 x 80 prep-tile kernel at 10 px per lane
-    unsigned* d_coop = nullptr;      // 2 counter sets of kCoopSetWords
-    int32_t* d_status_out = nullptr; // [max_frames] host batch API: status per pair of the call
-    int coop_par = 0;                // set (and partial-row arena) used by the next coop call
-    double* d_coop_part = nullptr;   // 2 arenas x kCoopBufs x coop_part_cap rows (EMPTY when idle)
-    int coop_part_cap = 0;           // rows per buffer
-    int coop_part_rows[2] = {0, 0};  // rows per buffer the last call on each arena used
-    int coop_poll_delay = -1;        // YOUTH_ICP_COOP_POLL_DELAY (x 64 clocks); -1: G / 8
-    int coop_stall_once = -1;        // YOUTH_ICP_TEST_COOP_STALL (test hook): chunk that stalls
-    int coop_stall_left = 0;         // coop launches the hook still stalls
-    int coop_stall_iter = 1;         // YOUTH_ICP_TEST_COOP_STALL_ITER: the iteration whose row is lost
-    bool realign_stall = false;      // YOUTH_ICP_TEST_REALIGN_STALL=1 (test hook): realigns' coop launches stall
-    int last_coop_G = 0, last_coop_px = 0;
-    bool last_coop = false;          // the last align ran k_icp_coop
-
-    int last_pairs = 0;
-    int last_iters = 0;
-    hipStream_t last_stream = nullptr;
-
-    int track_ref = -1;  // ring slot (0/1) of the tracker's reference frame
-    double* coop_res_host = nullptr;  // set around a tracker align: k_icp_coop writes its result there
-    bool coop_tile_src = true;        // YOUTH_ICP_COOP_TILE_SRC=0: contiguous source chunks
-    int trk_batch = 1;                // frames per submission in youth_icp_track_host_sequence
-    long long trk_chained = 0;        // micro-batch launches so far (youth_icp_track_chained)
-    long long trk_chained_frames = 0; // frames those launches aligned (youth_icp_track_chained_frames)
-    long long trk_realigned[3] = {};  // youth_icp_track_realign: coop / persistent / still failed
-    long long batch_realigned = 0;    // host batch API chunks realigned after a coop timeout
-    // depth filter in front of the tracker (youth_icp_set_depth_filter,
-    // YOUTH_ICP_DEPTH_FILTER): off = nothing allocated, nothing launched
-    bool flt_on = false;
-    youth_filter_params flt{8, 96};
-    int16_t* d_raw = nullptr;        // [trk_raw_slots][N] raw frames of one launch, filtered into d_depth
-    int queues = 0;                  // k_icp work queues (YOUTH_ICP_QUEUES=1..8; 0: by batch size)
-    int share = 1;                   // contexts launching k_icp concurrently (set_concurrency)
-    int prep_xcd_map = 0;             // YOUTH_ICP_PREP_XCD_MAP=1: k_prep tiles contiguous per XCD (slower)
-    // pipelined tracking (youth_icp_track_submit / _collect): up to
-    // kTrackDepth frames in flight, each with a pinned staging buffer, pinned
-    // results and events
-    struct TrackSlot {
-        int16_t* pinned = nullptr;     // host depth copy, H2D source
-        double* res = nullptr;         // pinned: T64 [16], then the status word
-        hipEvent_t h2d = nullptr;      // staging -> device depth done (xfer)
-        hipEvent_t done = nullptr;     // align + result D2H done (stream)
-        hipEvent_t done_nf = nullptr;  // the same without the system-scope fence (the
-                                       // kernel stored the result to host memory itself)
-        hipEvent_t ev = nullptr;       // the one of the two recorded for this submission
-        int has_ref = 0;
-    } trk[kTrackDepth];
-    int trk_dslot_last[2 * YOUTH_TRACK_MAX_BATCH];  // trk[] entry of the last launch that read depth slot d (-1: none)
-    int trk_prev_d0 = -1;                       // first depth slot of the last launch
-    int trk_head = 0, trk_n = 0;       // oldest in-flight submission, count in flight
-    int trk_cap = 2;                   // ring entries in use (grows to kTrackDepth on demand)
-
-    // host-buffer batch API: H2D of chunk k+1 on xfer overlaps the align of chunk k
-    hipStream_t xfer = nullptr;
-    std::vector<hipEvent_t> xfer_ev;
-
-    bool timing = false;
-    bool timing_iter_only = false;  // set_timing(2): events around the iteration kernel only
-    std::vector<EventPair> ev_live;
-    std::vector<EventPair> ev_free;
-    double t_ms[3] = {0, 0, 0};
-    int t_n[3] = {0, 0, 0};
-};
-
-// The kernels' template variant of a context: spec a7/a8 arithmetic in bit
-// 0, the lane32 reduction of spec a9 in bit 1.
-static int variant(const youth_icp_ctx* c)
-{
-    return c->spec | (c->reduce == YOUTH_REDUCE_LANE32 ? kRedLane32 : 0);
-}
-
-static int reduce_geometry(const youth_icp_ctx* c, int n_pairs, int* chunk_out)
+int reduce_geometry(const youth_icp_ctx* c, int n_pairs, int* chunk_out)
 {
     // work chunks per iteration: fewer chunks make items wait for their
     // pair's pose, more pay the per-item hand-off.  Measured
@@ -2814,7 +2064,7 @@ static int ensure_coop_part(youth_icp_ctx* c, hipStream_t s, int rows)
     return YOUTH_OK;
 }
 
-static int ensure_partials(youth_icp_ctx* c, size_t doubles)
+int ensure_partials(youth_icp_ctx* c, size_t doubles)
 {
     if (doubles <= c->partials_cap) return YOUTH_OK;
     if (c->d_partials) HIP_TRY(hipFree(c->d_partials));
@@ -2825,7 +2075,7 @@ static int ensure_partials(youth_icp_ctx* c, size_t doubles)
     return YOUTH_OK;
 }
 
-static int ensure_stats(youth_icp_ctx* c, int iters)
+int ensure_stats(youth_icp_ctx* c, int iters)
 {
     if (iters <= c->stats_iters) return YOUTH_OK;
     if (c->d_stats) HIP_TRY(hipFree(c->d_stats));
@@ -2879,7 +2129,7 @@ static int ev_end(youth_icp_ctx* c, hipStream_t s, EventPair* ep)
     return YOUTH_OK;
 }
 
-static int ev_harvest(youth_icp_ctx* c)
+int ev_harvest(youth_icp_ctx* c)
 {
     for (auto& e : c->ev_live) {
         HIP_TRY(hipEventSynchronize(e.b));
@@ -2893,10 +2143,9 @@ static int ev_harvest(youth_icp_ctx* c)
     return YOUTH_OK;
 }
 
-// Target records (and optionally XYZ planes) for n_frames depth frames at
-// `depth`, into workspace frames [out0, out0 + n_frames).
-static int launch_prep(youth_icp_ctx* c, hipStream_t s, const int16_t* depth, int n_frames,
-                       int out0, bool want_xyz, const InitArgs* init = nullptr)
+// init (nullable): the persistent path's per-call state, set by the same launch.
+static int launch_prep_with(youth_icp_ctx* c, hipStream_t s, const int16_t* depth, int n_frames,
+                            int out0, bool want_xyz, const InitArgs* init)
 {
     if (n_frames <= 0) return YOUTH_OK;
     if (want_xyz) {
@@ -2920,6 +2169,12 @@ static int launch_prep(youth_icp_ctx* c, hipStream_t s, const int16_t* depth, in
                        c->prep_xcd_map);
     HIP_TRY(hipGetLastError());
     return ev_end(c, s, &ep);
+}
+
+int launch_prep(youth_icp_ctx* c, hipStream_t s, const int16_t* depth, int n_frames, int out0,
+                bool want_xyz)
+{
+    return launch_prep_with(c, s, depth, n_frames, out0, want_xyz, nullptr);
 }
 
 template <int kSp, bool kAssoc, bool kFast, bool kAligned, bool kFuse>
@@ -2952,11 +2207,10 @@ static void launch_reduce_sel(youth_icp_ctx* c, hipStream_t s, dim3 grid, const 
     }
 }
 
-// fuse_it >= 0: fused solve of iteration fuse_it (k_reduce's last workgroup
-// per pair updates the pose); fuse_it < 0: partials only (k_solve follows).
-static int launch_reduce(youth_icp_ctx* c, hipStream_t s, const int16_t* dsrc, PairMap pm,
-                         int n_pairs, bool assoc, int* nblk_out, int fuse_it = -1)
+int launch_reduce(youth_icp_ctx* c, hipStream_t s, const int16_t* dsrc, int src0, int tgt0,
+                  int n_pairs, bool assoc, int* nblk_out, int fuse_it)
 {
+    const PairMap pm{src0, tgt0};
     int chunk = 0;
     const int nb = reduce_geometry(c, n_pairs, &chunk);
     int rc = ensure_partials(c, (size_t)nb * n_pairs * kNeq);
@@ -2999,7 +2253,7 @@ static int launch_reduce(youth_icp_ctx* c, hipStream_t s, const int16_t* dsrc, P
 // MI355X_MICROARCH.md); ties go to the larger npx (fewer partials to sum).
 static size_t coop_lds(int npx, int threads) { return (size_t)3 * npx * threads * sizeof(float); }
 
-static bool coop_plan(const youth_icp_ctx* c, int n_pairs, int* npx_out, int* G_out)
+bool coop_plan(const youth_icp_ctx* c, int n_pairs, int* npx_out, int* G_out)
 {
     if (!c->coop || n_pairs > c->coop_max_pairs || n_pairs > kCoopMaxPairs) return false;
     const int v = variant(c) * 2 + (c->fast ? 1 : 0);
@@ -3047,20 +2301,6 @@ static const void* coop_kernel(int var, bool fast, int threads, bool tall = fals
     }
 }
 
-// Target frames to turn into records before (or, for the tracker, beside)
-// the iterations: depth frames [depth, depth + n N) -> record frames
-// [out0, out0 + n); wait: the iterations gather exactly these records.
-struct PrepJob {
-    const int16_t* depth;
-    int n, out0;
-    bool wait;
-    // tracker micro-batch (k_icp_coop only; CoopState.chain): pair p preps
-    // its source frame into record frame prep_slot[p] and gathers record
-    // frame tgt_slot[p]; results to the pinned slots res[p]
-    bool chain = false;
-    int tgt_slot[kCoopMaxChain] = {}, prep_slot[kCoopMaxChain] = {};
-    double* res[kCoopMaxChain] = {};
-};
 
 // k_icp_coop's workgroups poll each other, so all n_pairs x G of them must be
 // resident together.  The planner sizes the grid to the co-resident capacity
@@ -3240,13 +2480,21 @@ static IcpKernel icp_kernel(int var)
     return tab[var & (4 * kVariants - 1)];
 }
 
-// All ICP iterations of n_pairs pairs.  *exported is set when the kernel
-// also wrote the fp32 4x4 poses to d_T_out (k_icp_coop); otherwise the
-// caller runs export_poses.
-static int run_iterations(youth_icp_ctx* c, hipStream_t s, const int16_t* dsrc, PairMap pm,
-                          int n_pairs, const double* T_init_host, float* d_T_out = nullptr,
-                          bool* exported = nullptr, const PrepJob* job = nullptr)
+int launch_init(youth_icp_ctx* c, hipStream_t s, const double* dTi, int n_pairs, int iters,
+                bool persistent)
 {
+    hipLaunchKernelGGL(k_init, dim3((n_pairs + 63) / 64), dim3(64), 0, s, dTi, n_pairs, c->d_T64,
+                       c->d_T32, c->d_status, persistent ? c->d_epoch : (unsigned*)nullptr,
+                       persistent ? c->d_arr_it : (unsigned*)nullptr, iters, c->d_head);
+    HIP_TRY(hipGetLastError());
+    return YOUTH_OK;
+}
+
+int run_iterations(youth_icp_ctx* c, hipStream_t s, const int16_t* dsrc, int src0, int tgt0,
+                   int n_pairs, const double* T_init_host, float* d_T_out, bool* exported,
+                   const PrepJob* job)
+{
+    const PairMap pm{src0, tgt0};
     const int iters = c->prm.iters;
     if (exported) *exported = false;
     // k_icp_coop fuses the prep job (one pair of workgroups per target);
@@ -3307,18 +2555,15 @@ static int run_iterations(youth_icp_ctx* c, hipStream_t s, const int16_t* dsrc, 
         // k_prep also sets the per-call state (k_init folded in)
         const InitArgs ia{dTi,         n_pairs,    c->d_T64, c->d_T32, c->d_status,
                           c->d_epoch,  c->d_arr_it, iters,   c->d_head};
-        rc = launch_prep(c, s, job->depth, job->n, job->out0, false, &ia);
+        rc = launch_prep_with(c, s, job->depth, job->n, job->out0, false, &ia);
         if (rc) return rc;
     } else {
         if (job) {
             rc = launch_prep(c, s, job->depth, job->n, job->out0, false);
             if (rc) return rc;
         }
-        hipLaunchKernelGGL(k_init, dim3((n_pairs + 63) / 64), dim3(64), 0, s, dTi, n_pairs,
-                           c->d_T64, c->d_T32, c->d_status,
-                           persistent ? c->d_epoch : (unsigned*)nullptr,
-                           persistent ? c->d_arr_it : (unsigned*)nullptr, iters, c->d_head);
-        HIP_TRY(hipGetLastError());
+        rc = launch_init(c, s, dTi, n_pairs, iters, persistent);
+        if (rc) return rc;
     }
     if (persistent) {
         int chunk = 0;
@@ -3358,7 +2603,7 @@ static int run_iterations(youth_icp_ctx* c, hipStream_t s, const int16_t* dsrc, 
         HIP_TRY(hipMemsetAsync(c->d_arrivals, 0, (size_t)c->max_frames * sizeof(unsigned), s));
         for (int it = 0; it < iters; ++it) {
             int nb = 0;
-            rc = launch_reduce(c, s, dsrc, pm, n_pairs, false, &nb, it);  // + fused solve
+            rc = launch_reduce(c, s, dsrc, src0, tgt0, n_pairs, false, &nb, it);  // + fused solve
             if (rc) return rc;
         }
     }
@@ -3368,61 +2613,17 @@ static int run_iterations(youth_icp_ctx* c, hipStream_t s, const int16_t* dsrc, 
     return YOUTH_OK;
 }
 
-static int export_poses(youth_icp_ctx* c, hipStream_t s, int n_pairs, float* d_T_out)
+int export_poses(youth_icp_ctx* c, hipStream_t s, int n_pairs, float* d_T_out, bool timeout)
 {
     hipLaunchKernelGGL(k_finish, dim3((n_pairs * 16 + 255) / 256), dim3(256), 0, s, c->d_T64,
-                       n_pairs, d_T_out, c->d_status, (const unsigned*)(c->d_head + kQError));
+                       n_pairs, d_T_out, c->d_status,
+                       timeout ? (const unsigned*)(c->d_head + kQError) : (const unsigned*)nullptr);
     HIP_TRY(hipGetLastError());
     return YOUTH_OK;
 }
 
-static hipStream_t pick_stream(youth_icp_ctx* c, void* stream)
-{
-    return stream ? (hipStream_t)stream : c->stream;
-}
-
-static int bind_device(youth_icp_ctx* c)
-{
-    HIP_TRY(hipSetDevice(c->device));
-    return YOUTH_OK;
-}
-
-// FastK of the intrinsics: h = RN(1/y), l = RN((1 - y h) / y) with the
-// residual 1 - y h exact (fma) and the quotient rounded once from fp64 (any
-// l is safe: k_verify_fastdiv decides whether the pair is used).
-static FastK fast_consts(const youth_intrinsics& K)
-{
-    auto hl = [](float y, float& h, float& l) {
-        h = 1.0f / y;
-        l = (float)((double)std::fma(-y, h, 1.0f) / (double)y);
-    };
-    FastK F;
-    hl(K.fx, F.hfx, F.lfx);
-    hl(K.fy, F.hfy, F.lfy);
-    hl(K.depth_scale, F.hds, F.lds);
-    return F;
-}
-
-// Whether k_icp's aligned pixel loop may form a lane's centred column
-// coordinates by additions: ((float)(u & ~3) - cx) + (u & 3) must equal the
-// spec's (float)u - cx for every column.  It does when cx is near the frame's
-// centre (the difference then keeps cx's ulp); a principal point far to one
-// side (e.g. cx = 20.9316 at W = 640: 9 columns) can make the difference
-// round, and such intrinsics take the unaligned loop, which converts every
-// column (tests/test_gpu_reduce.py::test_off_centre_principal_point).
-static bool centred_exact(float cx, int W)
-{
-    for (int u = 0; u < W; ++u) {
-        volatile float a = (float)u - cx;
-        volatile float b0 = (float)(u & ~3) - cx;
-        volatile float b = b0 + (float)(u & 3);
-        if (a != b) return false;
-    }
-    return true;
-}
-
 // Decide the division path for these intrinsics (k_verify_fastdiv).
-static int verify_fastdiv(youth_icp_ctx* c)
+int verify_fastdiv(youth_icp_ctx* c)
 {
     c->fast = false;
     const char* off = getenv("YOUTH_ICP_NO_FASTDIV");
@@ -3438,1548 +2639,100 @@ static int verify_fastdiv(youth_icp_ctx* c)
     return YOUTH_OK;
 }
 
-extern "C" {
-
-youth_intrinsics youth_default_intrinsics(int width, int height)
+hipError_t fill_occupancy(youth_icp_ctx* c, const char** what)
 {
-    youth_intrinsics K;
-    K.fx = 570.3f;  // viewerModule.c:344-345, astra_orb_slam3_rgbd.yaml:9-10
-    K.fy = 570.3f;
-    K.cx = (float)(width / 2);  // integer W/2 as in viewerModule.c:344
-    K.cy = (float)(height / 2);
-    K.depth_scale = 1000.0f;  // astra_orb_slam3_rgbd.yaml:35
-    return K;
-}
-
-youth_icp_params youth_default_params(void)
-{
-    youth_icp_params p;
-    p.iters = 10;
-    p.dist_thresh = 0.10f;
-    return p;
-}
-
-const char* youth_icp_last_error(void) { return g_last_error.c_str(); }
-
-int youth_icp_device_count(void)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-int youth_icp_fastdiv_enabled(youth_icp_ctx* c) { return c && c->fast ? 1 : 0; }
-
-int youth_icp_set_spec(youth_icp_ctx* c, int spec)
-{
-    if (!c || (spec != YOUTH_SPEC_FMA && spec != YOUTH_SPEC_SURVEY))
-        return set_error(YOUTH_EINVAL, "set_spec: bad arguments (%d)", spec);
-    const int old = c->spec;
-    c->spec = spec;
-    return old;
-}
-
-int youth_icp_set_reduce(youth_icp_ctx* c, int mode)
-{
-    if (!c || (mode != YOUTH_REDUCE_EXACT && mode != YOUTH_REDUCE_LANE32))
-        return set_error(YOUTH_EINVAL, "set_reduce: bad arguments (%d)", mode);
-    const int old = c->reduce;
-    c->reduce = mode;
-    return old;
-}
-
-int youth_icp_get_reduce(const youth_icp_ctx* c)
-{
-    return c ? c->reduce : set_error(YOUTH_EINVAL, "get_reduce: null context");
-}
-
-int youth_icp_get_lanes(const youth_icp_ctx* c, youth_lanes* out)
-{
-    if (!c || !out) return set_error(YOUTH_EINVAL, "get_lanes: bad arguments");
-    if (!c->has_lanes) return set_error(YOUTH_EINVAL, "get_lanes: no align has run");
-    if (c->lanes_mixed)
-        return set_error(YOUTH_EINVAL, "get_lanes: the last call ran launches of more than one "
-                                       "lane partition");
-    *out = c->lanes;
-    return YOUTH_OK;
-}
-
-int youth_icp_set_concurrency(youth_icp_ctx* c, int contexts)
-{
-    if (!c || contexts < 1 || contexts > YOUTH_ICP_MAX_CONCURRENCY)
-        return set_error(YOUTH_EINVAL, "set_concurrency: bad arguments (%d)", contexts);
-    const int old = c->share;
-    c->share = contexts;
-    return old;
-}
-
-int youth_icp_get_spec(const youth_icp_ctx* c)
-{
-    return c ? c->spec : set_error(YOUTH_EINVAL, "get_spec: null context");
-}
-
-void youth_icp_destroy(youth_icp_ctx* c)
-{
-    if (!c) return;
-    // best-effort teardown: errors here cannot be reported to anyone useful
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto* v : {&c->ev_live, &c->ev_free})
-        for (auto& e : *v) {
-            (void)hipEventDestroy(e.a);
-            (void)hipEventDestroy(e.b);
-        }
-    if (c->xfer) (void)hipStreamSynchronize(c->xfer);
-    for (hipEvent_t e : c->xfer_ev) (void)hipEventDestroy(e);
-    for (auto& q : c->trk) {
-        if (q.pinned) (void)hipHostFree(q.pinned);
-        if (q.res) (void)hipHostFree(q.res);
-        if (q.h2d) (void)hipEventDestroy(q.h2d);
-        if (q.done) (void)hipEventDestroy(q.done);
-        if (q.done_nf) (void)hipEventDestroy(q.done_nf);
-    }
-    void* bufs[] = {c->d_depth, c->d_rec,   c->d_xyz,      c->d_T64, c->d_T32,   c->d_status,
-                    c->d_Tinit, c->d_stats, c->d_partials, c->d_neq, c->d_assoc, c->d_Tout,
-                    c->d_flag,  c->d_arrivals, c->d_arr_it, c->d_epoch, c->d_head,
-                    c->d_coop,  c->d_status_out, c->d_coop_part, c->d_raw};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (c->device >= 0 && c->device < 64) {
-        // the device's coop ordering must not take a later stream that reuses
-        // this handle for the same stream (its work is complete: synchronised
-        // above, and every earlier coop launch ran before it)
-        CoopOrder& o = g_coop_order[c->device];
-        std::lock_guard<std::mutex> lk(o.mu);
-        if (o.any && o.last == c->stream) {
-            o.any = false;
-            o.last = nullptr;
-        }
-    }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->xfer) (void)hipStreamDestroy(c->xfer);
-    delete c;
-}
-
-static bool filter_params_ok(const youth_filter_params* p)
-{
-    return p->t0 >= 1 && p->t0 <= 255 && p->t2 >= 0 && p->t2 <= 1000;
-}
-
-youth_icp_ctx* youth_icp_create(int device, int W, int H, int max_frames,
-                                const youth_intrinsics* K, const youth_icp_params* P)
-{
-    // W, H <= 16384 and W*H <= 2^26: pixel indices fit the pixel loop's 24-bit
-    // multiply and a target frame's records (16 B/px) its 32-bit buffer offsets
-    if (W < 3 || H < 3 || W > 16384 || H > 16384 || max_frames < 2 ||
-        (long long)W * H > (1LL << 26)) {
-        set_error(YOUTH_EINVAL,
-                  "youth_icp_create: bad size %dx%d / max_frames %d (need 3 <= W, H <= 16384, "
-                  "W*H <= 2^26, max_frames >= 2)",
-                  W, H, max_frames);
-        return nullptr;
-    }
-    const int ndev = youth_icp_device_count();
-    if (ndev <= 0 || device < 0 || device >= ndev) {
-        set_error(YOUTH_ENODEV, "youth_icp_create: no HIP device %d", device);
-        return nullptr;
-    }
-    auto* c = new youth_icp_ctx();
-    for (int& d : c->trk_dslot_last) d = -1;
-    c->device = device;
-    c->W = W;
-    c->H = H;
-    c->N = W * H;
-    c->P = ((size_t)c->N + 4 + 255) / 256 * 256;
-    c->max_frames = max_frames;
-    const youth_intrinsics Kd = K ? *K : youth_default_intrinsics(W, H);
-    c->K = Intr{Kd.fx, Kd.fy, Kd.cx, Kd.cy, Kd.depth_scale};
-    c->F = fast_consts(Kd);
-    c->centred_exact = centred_exact(Kd.cx, W);
-    c->prm = P ? *P : youth_default_params();
-    auto fail = [&](const char* what, hipError_t e) -> youth_icp_ctx* {
-        set_error(YOUTH_EHIP, "youth_icp_create: %s (%d)", what, (int)e);
-        youth_icp_destroy(c);
-        return nullptr;
-    };
     hipError_t e;
-    if ((e = hipSetDevice(device)) != hipSuccess) return fail("hipSetDevice", e);
-    if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess)
-        return fail("hipStreamCreate", e);
-    const size_t MF = (size_t)max_frames;
-    const size_t rec_bytes = c->P * sizeof(float4) * MF;
-    if ((e = hipMalloc(&c->d_depth, MF * c->N * sizeof(int16_t))) != hipSuccess)
-        return fail("hipMalloc depth", e);
-    if ((e = hipMalloc(&c->d_rec, rec_bytes)) != hipSuccess) return fail("hipMalloc rec", e);
-    // the pad beyond N of every frame must read as an invalid point (z = 0)
-    if ((e = hipMemset(c->d_rec, 0, rec_bytes)) != hipSuccess) return fail("memset rec", e);
-    if ((e = hipMalloc(&c->d_T64, MF * 16 * sizeof(double))) != hipSuccess)
-        return fail("hipMalloc T64", e);
-    if ((e = hipMalloc(&c->d_T32, MF * 12 * sizeof(float))) != hipSuccess)
-        return fail("hipMalloc T32", e);
-    if ((e = hipMalloc(&c->d_status, MF * sizeof(int32_t))) != hipSuccess)
-        return fail("hipMalloc status", e);
-    if ((e = hipMalloc(&c->d_Tinit, MF * 16 * sizeof(double))) != hipSuccess)
-        return fail("hipMalloc Tinit", e);
-    if ((e = hipMalloc(&c->d_neq, MF * kNeq * sizeof(double))) != hipSuccess)
-        return fail("hipMalloc neq", e);
-    if ((e = hipMalloc(&c->d_Tout, MF * 16 * sizeof(float))) != hipSuccess)
-        return fail("hipMalloc Tout", e);
-    if ((e = hipMalloc(&c->d_flag, 16)) != hipSuccess) return fail("hipMalloc flag", e);
-    if ((e = hipMalloc(&c->d_epoch, MF * sizeof(unsigned))) != hipSuccess)
-        return fail("hipMalloc epoch", e);
-    if ((e = hipMalloc(&c->d_head, kQWords * 4)) != hipSuccess) return fail("hipMalloc head", e);
-    if ((e = hipMemset(c->d_head, 0, kQWords * 4)) != hipSuccess) return fail("memset head", e);
-    {
-        hipDeviceProp_t prop;
-        if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess)
-            return fail("hipGetDeviceProperties", e);
-        c->n_cu = prop.multiProcessorCount;
-        for (int v = 0; v < 4 * kVariants; ++v) {
-            int nb = 0;
-            if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                     &nb, (const void*)icp_kernel(v), kRedThreads, 0)) != hipSuccess)
-                return fail("occupancy", e);
-            c->icp_blocks_per_cu[v] = nb > 0 ? nb : 1;
-        }
-        const char* np = getenv("YOUTH_ICP_NO_PERSISTENT");
-        c->persistent = !(np && *np && *np != '0');
-        const char* cth = getenv("YOUTH_ICP_COOP_THREADS");
-        if (cth && atoi(cth) == 256) c->coop_threads = 256;
-        for (int ti = 0; ti < 2; ++ti)
-            for (int v = 0; v < 2 * kVariants; ++v)
-                for (int npx = 1; npx <= kCoopMaxPx; ++npx) {
-                    const int th = ti ? 256 : 512;
-                    int nb = 0;
-                    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                             &nb, coop_kernel(v >> 1, (v & 1) != 0, th), th, coop_lds(npx, th))) !=
-                        hipSuccess)
-                        return fail("occupancy coop", e);
-                    c->coop_bpc[ti][v][npx] = nb;
-                }
-        for (int v = 0; v < 2 * kVariants; ++v) {
-            int nb = 0;
-            const int npx = kTileW * kCoopTileHTall / 512;
-            if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                     &nb, coop_kernel(v >> 1, (v & 1) != 0, 512, true), 512,
-                     coop_lds(npx, 512))) != hipSuccess)
-                return fail("occupancy coop tall", e);
-            c->coop_bpc_tall[v] = nb;
-        }
-        const char* nc = getenv("YOUTH_ICP_NO_COOP");
-        c->coop = !(nc && *nc && *nc != '0');
-        const char* cpd = getenv("YOUTH_ICP_COOP_POLL_DELAY");  // tuning knob
-        if (cpd && atoi(cpd) >= 0) c->coop_poll_delay = atoi(cpd);
-        const char* cpx = getenv("YOUTH_ICP_COOP_PX");
-        if (cpx && atoi(cpx) >= 1 && atoi(cpx) <= kCoopMaxPx) c->coop_px = atoi(cpx);
-        c->coop_px_env = c->coop_px;
-        const char* cl = getenv("YOUTH_ICP_COOP_LAUNCH");
-        c->coop_launch = !cl ? 0 : strcmp(cl, "runtime") == 0 ? 1 : strcmp(cl, "plain") == 0 ? 2 : 0;
-        const char* tcp = getenv("YOUTH_ICP_TRACK_COPY");
-        c->trk_copy_compute = tcp && strcmp(tcp, "compute") == 0;
-        c->trk_copy_sdma = tcp && (strcmp(tcp, "sdma") == 0 || c->trk_copy_compute);
-        const char* pwg = getenv("YOUTH_ICP_PULL_WG");
-        c->trk_pull_wg = pwg && atoi(pwg) > 0 ? std::min(atoi(pwg), 1024) : 0;
-        const char* plds = getenv("YOUTH_ICP_PULL_LDS");
-        if (plds && atoi(plds) >= 0) c->trk_pull_lds = std::min(atoi(plds), 64 << 10);
-        const char* pres = getenv("YOUTH_ICP_PULL_RESERVE_CU");
-        if (pres && atoi(pres) >= 0) c->trk_pull_reserve = atoi(pres);
-        const char* cpt = getenv("YOUTH_ICP_COPY_THREADS");
-        if (cpt && atoi(cpt) >= 0) c->trk_copy_helpers = std::min(atoi(cpt), 15);
-        // test hooks (tests/): YOUTH_ICP_TEST_COOP_STALL=<chunk>[:<launches>]
-        // makes the context's first <launches> (default 1) cooperative
-        // launches lose chunk <chunk>'s iteration-1 row of pair 0, so they
-        // time out (the tracker's realign path); YOUTH_ICP_TEST_REFUSE_COOP=1
-        // refuses every cooperative launch as the runtime would (the
-        // persistent fallback of run_iterations).  Either one is announced on
-        // stderr: a stray variable must not pass for a device fault
-        const char* cst = getenv("YOUTH_ICP_TEST_COOP_STALL");
-        if (cst && atoi(cst) >= 0) {
-            c->coop_stall_once = atoi(cst);
-            const char* colon = strchr(cst, ':');
-            c->coop_stall_left = colon && atoi(colon + 1) > 0 ? atoi(colon + 1) : 1;
-            fprintf(stderr, "youth_icp: TEST HOOK YOUTH_ICP_TEST_COOP_STALL=%s active: the first %d "
-                            "cooperative launch(es) of this context time out\n",
-                    cst, c->coop_stall_left);
-        }
-        const char* sit = getenv("YOUTH_ICP_TEST_COOP_STALL_ITER");
-        if (sit && atoi(sit) >= 0) c->coop_stall_iter = atoi(sit);
-        const char* rst = getenv("YOUTH_ICP_TEST_REALIGN_STALL");
-        c->realign_stall = rst && *rst && *rst != '0';
-        if (c->realign_stall)
-            fprintf(stderr, "youth_icp: TEST HOOK YOUTH_ICP_TEST_REALIGN_STALL active: the "
-                            "cooperative launch of every youth_icp_track_realign times out\n");
-        const char* crf = getenv("YOUTH_ICP_TEST_REFUSE_COOP");
-        c->coop_refuse = crf && *crf && *crf != '0';
-        if (c->coop_refuse)
-            fprintf(stderr, "youth_icp: TEST HOOK YOUTH_ICP_TEST_REFUSE_COOP active: cooperative "
-                            "launches of this context are refused\n");
-        const char* nqs = getenv("YOUTH_ICP_QUEUES");
-        if (nqs && atoi(nqs) >= 1 && atoi(nqs) <= kMaxQueues) c->queues = atoi(nqs);
-        const char* pxm = getenv("YOUTH_ICP_PREP_XCD_MAP");
-        if (pxm && (*pxm == '1' || *pxm == '2')) c->prep_xcd_map = *pxm - '0';
-        const char* cts = getenv("YOUTH_ICP_COOP_TILE_SRC");
-        if (cts && *cts == '0') c->coop_tile_src = false;
-        const char* cmp = getenv("YOUTH_ICP_COOP_MAX_PAIRS");
-        if (cmp && atoi(cmp) >= 0) c->coop_max_pairs = atoi(cmp);
-        // spec a7/a8 arithmetic: "survey" (SURVEY §8a literally) or "fma"
-        const char* sp = getenv("YOUTH_ICP_SPEC");
-        if (sp && strcmp(sp, "survey") == 0) c->spec = kSpecSurvey;
-        if (sp && strcmp(sp, "fma") == 0) c->spec = kSpecFma;
-        // spec a9 reduction: "lane32" (SURVEY §8a a9 as worded) or "exact"
-        const char* rd = getenv("YOUTH_ICP_REDUCE");
-        if (rd && strcmp(rd, "lane32") == 0) c->reduce = YOUTH_REDUCE_LANE32;
-        if (rd && strcmp(rd, "exact") == 0) c->reduce = YOUTH_REDUCE_EXACT;
-        // the tracker's depth filter: "1" (defaults), "t0,t2", unset / "0" (off)
-        const char* df = getenv("YOUTH_ICP_DEPTH_FILTER");
-        if (df && *df && strcmp(df, "0") != 0) {
-            youth_filter_params fp{8, 96};
-            char tail = 0;
-            const bool ok = strcmp(df, "1") == 0 ||
-                            (sscanf(df, "%d,%d%c", &fp.t0, &fp.t2, &tail) == 2 &&
-                             filter_params_ok(&fp));
-            if (ok) {
-                c->flt = fp;
-                c->flt_on = true;   // the raw staging comes with the first tracked frame
-            } else {
-                fprintf(stderr, "youth_icp: YOUTH_ICP_DEPTH_FILTER=%s ignored (want 1, 0 or t0,t2 "
-                                "with 1 <= t0 <= 255, 0 <= t2 <= 1000): the depth filter stays off\n",
-                        df);
+    *what = "occupancy";
+    for (int v = 0; v < 4 * kVariants; ++v) {
+        int nb = 0;
+        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)icp_kernel(v),
+                                                              kRedThreads, 0)) != hipSuccess)
+            return e;
+        c->icp_blocks_per_cu[v] = nb > 0 ? nb : 1;
+    }
+    *what = "occupancy coop";
+    for (int ti = 0; ti < 2; ++ti)
+        for (int v = 0; v < 2 * kVariants; ++v)
+            for (int npx = 1; npx <= kCoopMaxPx; ++npx) {
+                const int th = ti ? 256 : 512;
+                int nb = 0;
+                if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                         &nb, coop_kernel(v >> 1, (v & 1) != 0, th), th, coop_lds(npx, th))) !=
+                    hipSuccess)
+                    return e;
+                c->coop_bpc[ti][v][npx] = nb;
             }
-        }
+    *what = "occupancy coop tall";
+    for (int v = 0; v < 2 * kVariants; ++v) {
+        int nb = 0;
+        const int npx = kTileW * kCoopTileHTall / 512;
+        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                 &nb, coop_kernel(v >> 1, (v & 1) != 0, 512, true), 512, coop_lds(npx, 512))) !=
+            hipSuccess)
+            return e;
+        c->coop_bpc_tall[v] = nb;
     }
-    if ((e = hipMalloc(&c->d_coop, 2 * kCoopSetWords * sizeof(unsigned))) != hipSuccess)
-        return fail("hipMalloc coop", e);
-    if ((e = hipMemset(c->d_coop, 0, 2 * kCoopSetWords * sizeof(unsigned))) != hipSuccess)
-        return fail("memset coop", e);
-    const size_t arr_bytes = (MF * sizeof(unsigned) + 15) / 16 * 16;
-    if ((e = hipMalloc(&c->d_arrivals, arr_bytes)) != hipSuccess)
-        return fail("hipMalloc arrivals", e);
-    if ((e = hipMemset(c->d_arrivals, 0, arr_bytes)) != hipSuccess)
-        return fail("memset arrivals", e);
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return fail("sync", e);
-    if (ensure_stats(c, c->prm.iters > 0 ? c->prm.iters : 1) != YOUTH_OK ||
-        verify_fastdiv(c) != YOUTH_OK) {
-        youth_icp_destroy(c);
-        return nullptr;
+    return hipSuccess;
+}
+
+void coop_forget_stream(youth_icp_ctx* c)
+{
+    if (c->device < 0 || c->device >= 64) return;
+    // the device's coop ordering must not take a later stream that reuses
+    // this handle for the same stream (its work is complete: synchronised
+    // by the caller, and every earlier coop launch ran before it)
+    CoopOrder& o = g_coop_order[c->device];
+    std::lock_guard<std::mutex> lk(o.mu);
+    if (o.any && o.last == c->stream) {
+        o.any = false;
+        o.last = nullptr;
     }
-    return c;
 }
 
-int youth_icp_align_pairs_device(youth_icp_ctx* c, const int16_t* d_src, const int16_t* d_dst,
-                                 int n_pairs, const double* T_init, float* d_T_out,
-                                 void* stream)
+int launch_solve_sums(youth_icp_ctx* c, hipStream_t s, int nblk)
 {
-    if (!c || !d_src || !d_dst || n_pairs <= 0 || n_pairs > c->max_frames)
-        return set_error(YOUTH_EINVAL, "align_pairs: bad arguments %d", n_pairs);
-    int rc = bind_device(c);
-    if (rc) return rc;
-    hipStream_t s = pick_stream(c, stream);
-    // targets -> records [0, n); sources are read straight from d_src
-    const PrepJob job{d_dst, n_pairs, 0, true};
-    bool exported = false;
-    rc = run_iterations(c, s, d_src, PairMap{0, 0}, n_pairs, T_init, d_T_out, &exported, &job);
-    if (rc) return rc;
-    return exported ? YOUTH_OK : export_poses(c, s, n_pairs, d_T_out);
-}
-
-int youth_icp_align_sequence_device(youth_icp_ctx* c, const int16_t* d_frames, int n_frames,
-                                    float* d_T_out, void* stream)
-{
-    if (!c || !d_frames || n_frames < 2 || n_frames - 1 > c->max_frames)
-        return set_error(YOUTH_EINVAL, "align_sequence: bad arguments %d", n_frames);
-    int rc = bind_device(c);
-    if (rc) return rc;
-    hipStream_t s = pick_stream(c, stream);
-    // every frame but the last is a target: one record set per frame, reused;
-    // pair k: source depth frame k+1, target record frame k
-    const PrepJob job{d_frames, n_frames - 1, 0, true};
-    bool exported = false;
-    rc = run_iterations(c, s, d_frames, PairMap{1, 0}, n_frames - 1, nullptr, d_T_out, &exported,
-                        &job);
-    if (rc) return rc;
-    return exported ? YOUTH_OK : export_poses(c, s, n_frames - 1, d_T_out);
-}
-
-int youth_icp_sync(youth_icp_ctx* c, void* stream)
-{
-    if (!c) return set_error(YOUTH_EINVAL, "sync: null context");
-    int rc = bind_device(c);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(pick_stream(c, stream)));
-    return YOUTH_OK;
-}
-
-int youth_icp_get_poses(youth_icp_ctx* c, int n, double* T64, float* T32, int32_t* status)
-{
-    if (!c || n < 0 || n > c->max_frames)
-        return set_error(YOUTH_EINVAL, "get_poses: bad arguments %d", n);
-    int rc = bind_device(c);
-    if (rc) return rc;
-    hipStream_t s = c->last_stream ? c->last_stream : c->stream;
-    if (T64)
-        HIP_TRY(hipMemcpyAsync(T64, c->d_T64, (size_t)n * 16 * sizeof(double),
-                               hipMemcpyDeviceToHost, s));
-    if (T32) {
-        rc = export_poses(c, s, n, c->d_Tout);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(T32, c->d_Tout, (size_t)n * 16 * sizeof(float),
-                               hipMemcpyDeviceToHost, s));
-    }
-    unsigned err = 0;
-    if (status) {
-        HIP_TRY(hipMemcpyAsync(status, c->d_status, (size_t)n * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, s));
-        // a timed-out launch (either kernel path) marks every pair
-        HIP_TRY(hipMemcpyAsync(&err, c->d_head + kQError, sizeof(unsigned),
-                               hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    if (status && err)
-        for (int i = 0; i < n; ++i) status[i] |= YOUTH_STATUS_TIMEOUT;
-    return YOUTH_OK;
-}
-
-int youth_icp_get_stats(youth_icp_ctx* c, int n, int iters, double* count, double* sum_r2)
-{
-    if (!c || n < 0 || n > c->max_frames || iters != c->last_iters || iters > c->stats_iters)
-        return set_error(YOUTH_EINVAL, "get_stats: bad arguments %d", iters);
-    int rc = bind_device(c);
-    if (rc) return rc;
-    std::vector<double> st((size_t)n * iters * 2);
-    hipStream_t s = c->last_stream ? c->last_stream : c->stream;
-    HIP_TRY(hipMemcpyAsync(st.data(), c->d_stats, st.size() * sizeof(double),
-                           hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (size_t i = 0; i < (size_t)n * iters; ++i) {
-        if (count) count[i] = st[2 * i];
-        if (sum_r2) sum_r2[i] = st[2 * i + 1];
-    }
-    return YOUTH_OK;
-}
-
-int youth_icp_set_timing(youth_icp_ctx* c, int enable)
-{
-    if (!c) return set_error(YOUTH_EINVAL, "set_timing: null context");
-    int rc = bind_device(c);
-    if (rc) return rc;
-    rc = ev_harvest(c);
-    if (rc) return rc;
-    c->timing = enable != 0;
-    c->timing_iter_only = enable == 2;
-    for (int k = 0; k < 3; ++k) {
-        c->t_ms[k] = 0.0;
-        c->t_n[k] = 0;
-    }
-    return YOUTH_OK;
-}
-
-int youth_icp_selftest_projdiv(int device, long long n, unsigned long long seed,
-                               long long* bit_mismatches, long long* proj_mismatches)
-{
-    if (n < 0) return set_error(YOUTH_EINVAL, "selftest_projdiv: n < 0");
-    const int ndev = youth_icp_device_count();
-    if (ndev <= 0 || device < 0 || device >= ndev)
-        return set_error(YOUTH_ENODEV, "selftest_projdiv: no HIP device %d", device);
-    HIP_TRY(hipSetDevice(device));
-    unsigned long long* d_bad = nullptr;
-    HIP_TRY(hipMalloc(&d_bad, 2 * sizeof(unsigned long long)));
-    unsigned long long h[2] = {0, 0};
-    hipError_t e = hipMemset(d_bad, 0, sizeof(h));
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_selftest_projdiv, dim3(4096), dim3(256), 0, 0,
-                           (unsigned long long)n, seed, d_bad);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(h, d_bad, sizeof(h), hipMemcpyDeviceToHost);
-    (void)hipFree(d_bad);
-    if (e != hipSuccess) return set_error(YOUTH_EHIP, "selftest_projdiv: %s", hipGetErrorString(e));
-    if (bit_mismatches) *bit_mismatches = (long long)h[0];
-    if (proj_mismatches) *proj_mismatches = (long long)h[1];
-    return YOUTH_OK;
-}
-
-int youth_icp_selftest_projquot(int device, long long n, unsigned long long seed,
-                                long long* quot_mismatches, long long* proj_mismatches,
-                                long long* floor_mismatches)
-{
-    if (n < 0) return set_error(YOUTH_EINVAL, "selftest_projquot: n < 0");
-    const int ndev = youth_icp_device_count();
-    if (ndev <= 0 || device < 0 || device >= ndev)
-        return set_error(YOUTH_ENODEV, "selftest_projquot: no HIP device %d", device);
-    HIP_TRY(hipSetDevice(device));
-    unsigned long long* d_bad = nullptr;
-    HIP_TRY(hipMalloc(&d_bad, 3 * sizeof(unsigned long long)));
-    unsigned long long h[3] = {0, 0, 0};
-    hipError_t e = hipMemset(d_bad, 0, sizeof(h));
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_selftest_projquot, dim3(4096), dim3(256), 0, 0,
-                           (unsigned long long)n, seed, d_bad);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(h, d_bad, sizeof(h), hipMemcpyDeviceToHost);
-    (void)hipFree(d_bad);
-    if (e != hipSuccess) return set_error(YOUTH_EHIP, "selftest_projquot: %s", hipGetErrorString(e));
-    if (quot_mismatches) *quot_mismatches = (long long)h[0];
-    if (proj_mismatches) *proj_mismatches = (long long)h[1];
-    if (floor_mismatches) *floor_mismatches = (long long)h[2];
-    return YOUTH_OK;
-}
-
-int youth_icp_selftest_normalize(int device, long long n, unsigned long long seed,
-                                 long long* sqrt_mismatches, long long* quot_mismatches,
-                                 long long* fast_cases)
-{
-    if (n < 0) return set_error(YOUTH_EINVAL, "selftest_normalize: n < 0");
-    const int ndev = youth_icp_device_count();
-    if (ndev <= 0 || device < 0 || device >= ndev)
-        return set_error(YOUTH_ENODEV, "selftest_normalize: no HIP device %d", device);
-    HIP_TRY(hipSetDevice(device));
-    unsigned long long* d_bad = nullptr;
-    HIP_TRY(hipMalloc(&d_bad, 3 * sizeof(unsigned long long)));
-    unsigned long long h[3] = {0, 0, 0};
-    hipError_t e = hipMemset(d_bad, 0, sizeof(h));
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_selftest_normalize, dim3(8192), dim3(256), 0, 0,
-                           (unsigned long long)n, seed, d_bad);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(h, d_bad, sizeof(h), hipMemcpyDeviceToHost);
-    (void)hipFree(d_bad);
-    if (e != hipSuccess)
-        return set_error(YOUTH_EHIP, "selftest_normalize: %s", hipGetErrorString(e));
-    if (sqrt_mismatches) *sqrt_mismatches = (long long)h[0];
-    if (quot_mismatches) *quot_mismatches = (long long)h[1];
-    if (fast_cases) *fast_cases = (long long)h[2];
-    return YOUTH_OK;
-}
-
-int youth_icp_get_sched_stats(youth_icp_ctx* c, unsigned* spins, unsigned* waited_items)
-{
-    if (!c) return set_error(YOUTH_EINVAL, "get_sched_stats: null context");
-    int rc = bind_device(c);
-    if (rc) return rc;
-    unsigned h[kQWords];
-    HIP_TRY(hipMemcpyAsync(h, c->d_head, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (spins) *spins = h[kQSpins];
-    if (waited_items) *waited_items = h[kQWaited];
-    return YOUTH_OK;
-}
-
-int youth_icp_get_plan(youth_icp_ctx* c, int* workgroups_per_pair, int* px_per_lane)
-{
-    if (!c) return set_error(YOUTH_EINVAL, "get_plan: null context");
-    if (workgroups_per_pair) *workgroups_per_pair = c->last_coop ? c->last_coop_G : 0;
-    if (px_per_lane) *px_per_lane = c->last_coop ? c->last_coop_px : 0;
-    return c->last_coop ? 1 : c->persistent ? 0 : 2;
-}
-
-int youth_icp_get_timing(youth_icp_ctx* c, int kind, double* total_ms, int* launches)
-{
-    if (!c || kind < 0 || kind > 2) return set_error(YOUTH_EINVAL, "get_timing: bad kind %d", kind);
-    int rc = bind_device(c);
-    if (rc) return rc;
-    rc = ev_harvest(c);
-    if (rc) return rc;
-    if (total_ms) *total_ms = c->t_ms[kind];
-    if (launches) *launches = c->t_n[kind];
-    return YOUTH_OK;
-}
-
-int youth_icp_prepare_host(youth_icp_ctx* c, const int16_t* depth, int n_frames,
-                           int want_normals, float* X, float* Y, float* Z, float* NX,
-                           float* NY, float* NZ)
-{
-    if (!c || !depth || n_frames <= 0 || n_frames > c->max_frames)
-        return set_error(YOUTH_EINVAL, "prepare_host: bad arguments %d", n_frames);
-    int rc = bind_device(c);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    const size_t N = c->N;
-    HIP_TRY(hipMemcpyAsync(c->d_depth, depth, (size_t)n_frames * N * sizeof(int16_t),
-                           hipMemcpyHostToDevice, s));
-    // no X/Y/Z wanted: the align path's record kernel (k_prep without planes)
-    rc = launch_prep(c, s, c->d_depth, n_frames, 0, X || Y || Z);
-    if (rc) return rc;
-    float* outs[6] = {X, Y, Z, NX, NY, NZ};
-    for (int f = 0; f < n_frames; ++f)
-        for (int k = 0; k < 6; ++k) {
-            if (!outs[k] || (k >= 3 && !want_normals)) continue;
-            float* dst = outs[k] + (size_t)f * N;
-            if (k < 3) {
-                const float* base = c->d_xyz + (size_t)f * 3 * c->P + (size_t)k * c->P;
-                HIP_TRY(hipMemcpyAsync(dst, base, N * sizeof(float), hipMemcpyDeviceToHost, s));
-            } else {  // component k-2 of the {z, nx, ny, nz} records
-                const float* base = reinterpret_cast<const float*>(c->d_rec + (size_t)f * c->P) +
-                                    (k - 2);
-                HIP_TRY(hipMemcpy2DAsync(dst, sizeof(float), base, sizeof(float4), sizeof(float),
-                                         N, hipMemcpyDeviceToHost, s));
-            }
-        }
-    HIP_TRY(hipStreamSynchronize(s));
-    return YOUTH_OK;
-}
-
-int youth_icp_reduce_host(youth_icp_ctx* c, const int16_t* src, const int16_t* dst,
-                          const float* T12, int32_t* assoc, double* neq)
-{
-    if (!c || !src || !dst || !T12) return set_error(YOUTH_EINVAL, "reduce_host: bad arguments");
-    int rc = bind_device(c);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    const size_t N = c->N;
-    HIP_TRY(hipMemcpyAsync(c->d_depth, src, N * sizeof(int16_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->d_depth + N, dst, N * sizeof(int16_t), hipMemcpyHostToDevice, s));
-    rc = launch_prep(c, s, c->d_depth + N, 1, 1, false);  // target -> record frame 1
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_T32, T12, 12 * sizeof(float), hipMemcpyHostToDevice, s));
-    int nb = 0;
-    rc = launch_reduce(c, s, c->d_depth, PairMap{0, 1}, 1, assoc != nullptr, &nb);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_solve, dim3(1), dim3(64), 0, s, c->d_partials, nb, 0, 1, c->d_T64,
+    hipLaunchKernelGGL(k_solve, dim3(1), dim3(64), 0, s, c->d_partials, nblk, 0, 1, c->d_T64,
                        c->d_T32, c->d_status, (double*)nullptr, c->d_neq);
     HIP_TRY(hipGetLastError());
-    if (neq)
-        HIP_TRY(hipMemcpyAsync(neq, c->d_neq, kNeq * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (assoc)
-        HIP_TRY(hipMemcpyAsync(assoc, c->d_assoc, N * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
     return YOUTH_OK;
 }
 
-int youth_icp_solve_host(youth_icp_ctx* c, const double* neq, double* T64)
+int launch_solve_neq(youth_icp_ctx* c, hipStream_t s)
 {
-    if (!c || !neq || !T64) return set_error(YOUTH_EINVAL, "solve_host: bad arguments");
-    int rc = bind_device(c);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(c->d_neq, neq, kNeq * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->d_T64, T64, 16 * sizeof(double), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_solve_neq, dim3(1), dim3(64), 0, s, c->d_neq, c->d_T64, c->d_T32,
                        c->d_status);
     HIP_TRY(hipGetLastError());
-    int32_t st = 0;
-    HIP_TRY(hipMemcpyAsync(T64, c->d_T64, 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&st, c->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return st;
-}
-
-// ----------------------------------------------- one-shot host batch API --
-// One cached context per device (guarded by that device's mutex), reused while
-// the frame size, intrinsics and capacity fit.
-static std::mutex g_batch_mu[64];
-static youth_icp_ctx* g_batch_ctx[64] = {};
-
-// Pairs per pipelined chunk of the host-buffer batch API (n_pairs: no
-// pipelining).  YOUTH_ICP_BATCH_CHUNK overrides (0 disables).
-static int batch_chunk(int n_pairs)
-{
-    if (const char* e = getenv("YOUTH_ICP_BATCH_CHUNK")) {
-        const int v = atoi(e);
-        return v <= 0 ? n_pairs : std::min(v, n_pairs);
-    }
-    // 16-pair chunks run the persistent kernel: copy ~ align.  8-pair chunks
-    // (cooperative kernel) ran at 34 K on one box and 20-24 K on another, next to
-    // the in-flight copies (profiles/r01/hostio_sweep.txt)
-    return n_pairs >= 32 ? 16 : n_pairs;
-}
-
-// Workspace for an align of n_pairs whichever kernel path it takes
-// (cooperative, persistent or per-iteration), so that no hipFree/hipMalloc
-// runs while earlier chunks of a pipelined call are in flight.
-static int reserve_for(youth_icp_ctx* c, int n_pairs)
-{
-    int chunk = 0;
-    const int nb = reduce_geometry(c, n_pairs, &chunk);
-    size_t need = (size_t)nb * n_pairs * kPartStride;
-    int npx = 0, G = 0;
-    if (coop_plan(c, n_pairs, &npx, &G))
-        need = std::max(need, (size_t)2 * n_pairs * G * kPartStride);
-    int rc = ensure_partials(c, need);
-    if (rc) return rc;
-    return ensure_stats(c, c->prm.iters > 0 ? c->prm.iters : 1);
-}
-
-// The host batch align of n_pairs pairs on ONE device: H2D of both depth
-// stacks, align, poses (and per-pair status, nullable) back into the
-// caller's rows.  Batches of >= 32 pairs are pipelined in chunks: chunk k's
-// H2D on a transfer stream overlaps the align of chunk k-1 (every chunk has
-// its own device frames, so nothing is reused inside one call).  On any error
-// both streams are drained before returning, so no copy still reads the
-// caller's buffers.  Caller holds g_batch_mu[dev].
-static int batch_on_device(int dev, const int16_t* src, const int16_t* dst, int n_pairs, int W,
-                           int H, const youth_intrinsics& Kd, int iters, float* T_out,
-                           int32_t* status_out, int32_t* assoc_out)
-{
-    youth_icp_params P = youth_default_params();
-    P.iters = iters;
-    youth_icp_ctx*& slot = g_batch_ctx[dev];
-    youth_icp_ctx* c = slot;
-    const bool same = c && c->W == W && c->H == H && c->max_frames >= 2 * n_pairs &&
-                      c->K.fx == Kd.fx && c->K.fy == Kd.fy && c->K.cx == Kd.cx &&
-                      c->K.cy == Kd.cy && c->K.ds == Kd.depth_scale;
-    if (!same) {
-        if (c) youth_icp_destroy(c);
-        slot = nullptr;
-        c = youth_icp_create(dev, W, H, 2 * n_pairs, &Kd, &P);
-        if (!c)
-            return g_last_error.find("no HIP device") != std::string::npos ? YOUTH_ENODEV
-                                                                          : YOUTH_EHIP;
-        slot = c;
-    }
-    c->prm = P;
-    int rc = bind_device(c);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    if (!c->xfer) HIP_TRY(hipStreamCreateWithFlags(&c->xfer, hipStreamNonBlocking));
-    // per-pair status on every call: a timed-out cooperative chunk is realigned below
-    if (!c->d_status_out)
-        HIP_TRY(hipMalloc(&c->d_status_out, (size_t)c->max_frames * sizeof(int32_t)));
-    auto drain = [c, s](int code) {
-        (void)hipStreamSynchronize(c->xfer);
-        (void)hipStreamSynchronize(s);
-        return code;
-    };
-    const size_t N = c->N;
-    int16_t* d_s = c->d_depth;
-    int16_t* d_d = c->d_depth + (size_t)n_pairs * N;
-    const int chunk = assoc_out ? n_pairs : batch_chunk(n_pairs);
-    const int n_chunks = (n_pairs + chunk - 1) / chunk;
-    rc = reserve_for(c, chunk);
-    if (!rc && n_pairs % chunk) rc = reserve_for(c, n_pairs % chunk);
-    if (rc) return rc;
-    while ((int)c->xfer_ev.size() < n_chunks) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        c->xfer_ev.push_back(e);
-    }
-    youth_lanes first_lanes{};
-    bool mixed = false;
-    for (int k = 0; k < n_chunks; ++k) {
-        const size_t p0 = (size_t)k * chunk;
-        const int cnt = (int)std::min<size_t>(chunk, n_pairs - p0);
-        const size_t bytes = (size_t)cnt * N * sizeof(int16_t);
-        hipError_t e = hipMemcpyAsync(d_s + p0 * N, src + p0 * N, bytes, hipMemcpyHostToDevice,
-                                      c->xfer);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(d_d + p0 * N, dst + p0 * N, bytes, hipMemcpyHostToDevice, c->xfer);
-        if (e == hipSuccess) e = hipEventRecord(c->xfer_ev[k], c->xfer);
-        if (e == hipSuccess) e = hipStreamWaitEvent(s, c->xfer_ev[k], 0);
-        if (e != hipSuccess)
-            return drain(set_error(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
-        rc = youth_icp_align_pairs_device(c, d_s + p0 * N, d_d + p0 * N, cnt, nullptr,
-                                          c->d_Tout + p0 * 16, s);
-        if (rc) return drain(rc);
-        // a tail chunk may take another kernel (and lane partition) than the
-        // full chunks: youth_icp_get_lanes then reports the call as mixed
-        if (k == 0)
-            first_lanes = c->lanes;
-        else
-            mixed |= memcmp(&first_lanes, &c->lanes, sizeof(youth_lanes)) != 0;
-        hipLaunchKernelGGL(k_status_out, dim3((cnt + 255) / 256), dim3(256), 0, s,
-                           c->d_status, cnt, (const unsigned*)(c->d_head + kQError),
-                           c->d_status_out + p0);
-        if ((e = hipGetLastError()) != hipSuccess)
-            return drain(set_error(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
-    }
-    // A chunk of <= 16 pairs is one cooperative launch sized to an idle
-    // device; on a GPU shared with other processes its grid may not be
-    // co-resident, and it then times out (kCoopSpinMax polls, ~50 ms) with
-    // partly iterated poses.  Such a chunk is aligned again, synchronously, on
-    // the persistent k_prep + k_icp, which waits only on running workgroups:
-    // the same poses up to fp64 summation order (its depth frames are still
-    // on the device).  The caller never receives a TIMEOUT pose from here.
-    {
-        std::vector<int32_t> st((size_t)n_pairs);
-        hipError_t e = hipMemcpyAsync(st.data(), c->d_status_out, (size_t)n_pairs * sizeof(int32_t),
-                                      hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return drain(set_error(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
-        for (int k = 0; k < n_chunks; ++k) {
-            const size_t p0 = (size_t)k * chunk;
-            const int cnt = (int)std::min<size_t>(chunk, n_pairs - p0);
-            bool to = false;
-            for (int i = 0; i < cnt; ++i) to |= (st[p0 + i] & YOUTH_STATUS_TIMEOUT) != 0;
-            if (!to) continue;
-            fprintf(stderr, "youth_icp: align_batch: a cooperative launch of %d pair(s) timed out "
-                            "(GPU shared with another process?); realigned on the persistent kernel\n",
-                    cnt);
-            const bool coop_was = c->coop;
-            c->coop = false;
-            rc = youth_icp_align_pairs_device(c, d_s + p0 * N, d_d + p0 * N, cnt, nullptr,
-                                              c->d_Tout + p0 * 16, s);
-            c->coop = coop_was;
-            if (rc) return drain(rc);
-            ++c->batch_realigned;
-            mixed = true;  // this chunk's lane partition is the persistent kernel's
-            hipLaunchKernelGGL(k_status_out, dim3((cnt + 255) / 256), dim3(256), 0, s,
-                               c->d_status, cnt, (const unsigned*)(c->d_head + kQError),
-                               c->d_status_out + p0);
-            if ((e = hipGetLastError()) != hipSuccess)
-                return drain(set_error(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
-        }
-    }
-    if (assoc_out) {
-        int nb = 0;
-        const youth_lanes align_lanes = c->lanes;  // youth_icp_get_lanes reports the align's
-        rc = launch_reduce(c, s, d_s, PairMap{0, 0}, n_pairs, true, &nb);
-        c->lanes = align_lanes;
-        if (rc) return drain(rc);
-        hipError_t e = hipMemcpyAsync(assoc_out, c->d_assoc, (size_t)n_pairs * N * sizeof(int32_t),
-                                      hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess)
-            return drain(set_error(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
-    }
-    c->lanes_mixed = mixed;
-    hipError_t e = hipMemcpyAsync(T_out, c->d_Tout, (size_t)n_pairs * 16 * sizeof(float),
-                                  hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && status_out)
-        e = hipMemcpyAsync(status_out, c->d_status_out, (size_t)n_pairs * sizeof(int32_t),
-                           hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return drain(set_error(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
-    HIP_TRY(hipStreamSynchronize(s));
     return YOUTH_OK;
 }
 
-int youth_icp_align_batch(const int16_t* src, const int16_t* dst, int n_pairs, int W, int H,
-                          const youth_intrinsics* K, int iters, float* T_out,
-                          int32_t* assoc_out)
+hipError_t launch_status_out(youth_icp_ctx* c, hipStream_t s, int n, int32_t* out)
 {
-    if (!src || !dst || n_pairs <= 0 || W < 3 || H < 3 || iters < 0 || !T_out)
-        return set_error(YOUTH_EINVAL, "align_batch: bad arguments %d", n_pairs);
-    std::lock_guard<std::mutex> lk(g_batch_mu[0]);
-    const youth_intrinsics Kd = K ? *K : youth_default_intrinsics(W, H);
-    return batch_on_device(0, src, dst, n_pairs, W, H, Kd, iters, T_out, nullptr, assoc_out);
+    hipLaunchKernelGGL(k_status_out, dim3((n + 255) / 256), dim3(256), 0, s, c->d_status, n,
+                       (const unsigned*)(c->d_head + kQError), out);
+    return hipGetLastError();
 }
 
-// Contiguous shard [first, first + count) of n pairs for part r of k (the
-// first n % k parts get one more), as youth_dist.pair_range on the bench side.
-static void shard_range(int n, int k, int r, int* first, int* count)
+int launch_pull_frames(youth_icp_ctx* c, hipStream_t s, const int16_t* const* src, int m,
+                       int16_t* dst, int N, int wg)
 {
-    const int q = n / k, m = n % k;
-    *first = r * q + std::min(r, m);
-    *count = q + (r < m ? 1 : 0);
-}
-
-int youth_icp_shard_range(int n_pairs, int n_parts, int part, int* first, int* count)
-{
-    if (n_pairs < 0 || n_parts <= 0 || part < 0 || part >= n_parts || !first || !count)
-        return set_error(YOUTH_EINVAL, "shard_range: bad arguments");
-    shard_range(n_pairs, n_parts, part, first, count);
+    FramePtrs fp{};
+    for (int i = 0; i < m; ++i) fp.src[i] = src[i];
+    hipLaunchKernelGGL(k_pull_frames, dim3(wg, m), dim3(64), (unsigned)c->trk_pull_lds, s, fp, dst,
+                       N, m);
+    HIP_TRY(hipGetLastError());
     return YOUTH_OK;
 }
 
-int youth_icp_align_batch_multi(const int16_t* src, const int16_t* dst, int n_pairs, int W,
-                                int H, const youth_intrinsics* K, int iters, const int* devices,
-                                int n_devices, float* T_out, int32_t* status_out)
+hipError_t launch_selftest(int which, unsigned long long n, unsigned long long seed,
+                           unsigned long long* d_bad)
 {
-    if (!src || !dst || n_pairs <= 0 || W < 3 || H < 3 || iters < 0 || !T_out)
-        return set_error(YOUTH_EINVAL, "align_batch_multi: bad arguments %d", n_pairs);
-    const int ndev = youth_icp_device_count();
-    if (ndev <= 0) return set_error(YOUTH_ENODEV, "align_batch_multi: no HIP device");
-    std::vector<int> devs;
-    if (devices && n_devices > 0) {
-        for (int i = 0; i < n_devices; ++i) {
-            if (devices[i] < 0 || devices[i] >= ndev || devices[i] >= 64)
-                return set_error(YOUTH_EINVAL, "align_batch_multi: no HIP device %d", devices[i]);
-            if (std::find(devs.begin(), devs.end(), devices[i]) != devs.end())
-                return set_error(YOUTH_EINVAL, "align_batch_multi: device %d listed twice",
-                                 devices[i]);
-            devs.push_back(devices[i]);
-        }
-    } else {
-        for (int d = 0; d < std::min(ndev, 64); ++d) devs.push_back(d);
-    }
-    const int parts = std::min((int)devs.size(), n_pairs);
-    const youth_intrinsics Kd = K ? *K : youth_default_intrinsics(W, H);
-    const size_t N = (size_t)W * H;
-    std::vector<int> rcs(parts, YOUTH_OK);
-    std::vector<std::string> errs(parts);
-    auto work = [&](int r) {
-        int first = 0, cnt = 0;
-        shard_range(n_pairs, parts, r, &first, &cnt);
-        std::lock_guard<std::mutex> lk(g_batch_mu[devs[r]]);
-        rcs[r] = batch_on_device(devs[r], src + (size_t)first * N, dst + (size_t)first * N, cnt, W,
-                                 H, Kd, iters, T_out + (size_t)first * 16,
-                                 status_out ? status_out + first : nullptr, nullptr);
-        if (rcs[r]) errs[r] = g_last_error;  // thread-local: carried to the caller below
-    };
-    // one host thread per device; shard 0 runs on the calling thread
-    std::vector<std::thread> th;
-    for (int r = 1; r < parts; ++r) th.emplace_back(work, r);
-    work(0);
-    for (auto& t : th) t.join();
-    for (int r = 0; r < parts; ++r)
-        if (rcs[r]) {
-            g_last_error = "device " + std::to_string(devs[r]) + ": " + errs[r];
-            return rcs[r];
-        }
-    return YOUTH_OK;
+    if (which == 0)
+        hipLaunchKernelGGL(k_selftest_projdiv, dim3(4096), dim3(256), 0, 0, n, seed, d_bad);
+    else if (which == 1)
+        hipLaunchKernelGGL(k_selftest_projquot, dim3(4096), dim3(256), 0, 0, n, seed, d_bad);
+    else
+        hipLaunchKernelGGL(k_selftest_normalize, dim3(8192), dim3(256), 0, 0, n, seed, d_bad);
+    return hipGetLastError();
 }
 
-// ------------------------------------------------------ frame tracking --
-// Lazily: the transfer stream and the ring's events.  The pinned staging
-// frame and result slot of a ring entry are allocated when a submission first
-// uses that entry (track_entry_pinned), so a context that keeps at most two
-// frames in flight (the SLAM worker) pins two frames, not the ring's 16
-// (16 x W x H x 2 bytes is 512 MB at 4096 x 4096).
-static int ensure_track(youth_icp_ctx* c)
-{
-    if (c->trk[kTrackDepth - 1].done_nf) return YOUTH_OK;
-    if (!c->xfer) HIP_TRY(hipStreamCreateWithFlags(&c->xfer, hipStreamNonBlocking));
-    for (auto& q : c->trk) {
-        if (!q.h2d) HIP_TRY(hipEventCreateWithFlags(&q.h2d, hipEventDisableTiming));
-        if (!q.done) HIP_TRY(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
-        if (!q.done_nf)
-            HIP_TRY(hipEventCreateWithFlags(&q.done_nf,
-                                            hipEventDisableTiming | hipEventDisableSystemFence));
-    }
-    return YOUTH_OK;
-}
-
-// The ring holds trk_cap entries and grows only when a submission would put
-// more than trk_cap frames in flight: it is rotated so the oldest in-flight
-// entry is entry 0 (indices in trk_dslot_last follow), then extended, so the
-// in-flight entries stay consecutive modulo the new size.
-static void track_grow(youth_icp_ctx* c, int need)
-{
-    if (need <= c->trk_cap) return;
-    const int cap = c->trk_cap, h = c->trk_head;
-    if (h) {
-        youth_icp_ctx::TrackSlot tmp[kTrackDepth];
-        for (int i = 0; i < cap; ++i) tmp[i] = c->trk[(h + i) % cap];
-        for (int i = 0; i < cap; ++i) c->trk[i] = tmp[i];
-        for (int& d : c->trk_dslot_last)
-            if (d >= 0) d = (d - h + cap) % cap;
-        c->trk_head = 0;
-    }
-    c->trk_cap = std::min(kTrackDepth, need);
-}
-
-static int track_entry_pinned(youth_icp_ctx* c, int e, bool staging)
-{
-    auto& q = c->trk[e];
-    if (staging && !q.pinned)
-        HIP_TRY(hipHostMalloc((void**)&q.pinned, (size_t)c->N * sizeof(int16_t),
-                              hipHostMallocDefault));
-    if (!q.res) HIP_TRY(hipHostMalloc((void**)&q.res, 17 * sizeof(double), hipHostMallocCoherent));
-    return YOUTH_OK;
-}
-
-// Depth slots of the tracker (device staging of host frames): two halves of
-// B slots (B = the largest micro-batch the context has room for: a launch
-// takes consecutive slots of one half, the other half stays with the launch
-// before), or 2 (one frame per launch).  Record slots: B + 1 (a micro-batch
-// preps its B new frames beside the reference), at least 2.
-static int trk_half(const youth_icp_ctx* c)
-{
-    return std::max(1, std::min(kCoopMaxChain, c->max_frames / 2));
-}
-static int trk_depth_slots(const youth_icp_ctx* c) { return 2 * trk_half(c); }
-static int trk_record_slots(const youth_icp_ctx* c)
-{
-    return std::max(2, std::min(kCoopMaxChain + 1, c->max_frames));
-}
-
-// Whether m consecutive frames can be aligned as one k_icp_coop micro-batch:
-// every pair on the single-pair plan (bit-identical to track_frame), the m
-// grids co-resident, room for the slots.
-static bool trk_chain_fits(const youth_icp_ctx* c, int m)
-{
-    if (m < 2 || m > kCoopMaxChain || m > trk_half(c) || trk_record_slots(c) < m + 1 ||
-        c->prm.iters <= 0 || c->coop_refuse)
-        return false;
-    int npx = 0, G = 0;
-    if (!coop_plan(c, 1, &npx, &G)) return false;
-    return (long long)m * G <=
-           (long long)c->n_cu *
-               c->coop_bpc[c->coop_threads == 256][variant(c) * 2 + (c->fast ? 1 : 0)][npx];
-}
-
-// m consecutive host frames (m = 1, or a micro-batch that trk_chain_fits):
-// staged into m consecutive depth slots not read by the previous launch,
-// H2D on the transfer stream (after the last launch that read those slots),
-// then ONE launch on the context stream: prep only (no reference yet), the
-// single-pair align with the fused prep of the new frame, or the chained
-// micro-batch (pair i aligns frame i to frame i-1, frame -1 = the
-// reference).  One completion event for the launch, shared by its entries.
-// frames (nullable): the m frames are the caller's page-locked buffers,
-// copied H2D in place (no staging copy; youth_icp_track_submit_pinned).
-// Page-locked buffers handed out by youth_icp_host_alloc, by base address:
-// k_pull_frames reads a caller's frame in place only when it lies inside one
-// of them (youth_icp_track_submit_pinned); any other pointer goes through
-// hipMemcpyAsync, so a pageable buffer passed by mistake is copied by the
-// runtime instead of faulting the GPU.
-static std::mutex g_host_mu;
-static std::map<uintptr_t, size_t> g_host_bufs;  // base -> bytes
-
-static bool host_alloc_covers(const int16_t* p, size_t values)
-{
-    const uintptr_t a = (uintptr_t)p;
-    std::lock_guard<std::mutex> lk(g_host_mu);
-    auto it = g_host_bufs.upper_bound(a);
-    if (it == g_host_bufs.begin()) return false;
-    --it;
-    return a >= it->first && a + values * sizeof(int16_t) <= it->first + it->second;
-}
-
-// the SLAM module's event trace (slam_api.cpp, youth_slam_trace_enable):
-// steps inside a submission, YOUTH_SLAM_EV_SUBMIT_STEP.  Weak: tools that
-// compile this file without slam_api.cpp (tools/coopbench ...) record nothing.
-extern "C" __attribute__((weak)) void youth_slam_trace_hook(int kind, int arg);
-static inline void trace_step(int step)
-{
-    if (youth_slam_trace_hook) youth_slam_trace_hook(YOUTH_SLAM_EV_SUBMIT_STEP, step);
-}
-
-// The depth filter's launcher (depth_filter.hip, youth_filter.h).  Weak: tools
-// that compile this file alone (tools/kbench ...) have no filter to turn on.
-__attribute__((weak)) int youth_depth_filter_device(int device, const int16_t* d_in, int16_t* d_out,
-                                                    int n_frames, int W, int H,
-                                                    const youth_filter_params* P, void* stream);
-__attribute__((weak)) const char* youth_depth_filter_last_error(void);
-
-// Raw staging of the filter: the frames of one launch (the transfer stream
-// pulls, then filters, launch after launch in order), two for a realign.
-static int trk_raw_slots(const youth_icp_ctx* c) { return std::max(2, trk_half(c)); }
-
-static int ensure_raw(youth_icp_ctx* c)
-{
-    if (c->d_raw) return YOUTH_OK;
-    if (!youth_depth_filter_device)
-        return set_error(YOUTH_EINVAL, "depth filter: not part of this build");
-    HIP_TRY(hipMalloc(&c->d_raw, (size_t)trk_raw_slots(c) * c->N * sizeof(int16_t)));
-    return YOUTH_OK;
-}
-
-// d_raw[0 .. n) -> dst[0 .. n) on `stream`
-static int track_filter(youth_icp_ctx* c, int n, int16_t* dst, hipStream_t stream)
-{
-    const int rc = youth_depth_filter_device(c->device, c->d_raw, dst, n, c->W, c->H, &c->flt, stream);
-    if (rc) return set_error(rc, "depth filter: %s", youth_depth_filter_last_error());
-    return YOUTH_OK;
-}
-
-int youth_icp_set_depth_filter(youth_icp_ctx* c, const youth_filter_params* P)
-{
-    if (!c) return set_error(YOUTH_EINVAL, "set_depth_filter: null context");
-    if (P && !filter_params_ok(P))
-        return set_error(YOUTH_EINVAL,
-                         "set_depth_filter: t0 %d, t2 %d (need 1 <= t0 <= 255, 0 <= t2 <= 1000)",
-                         P->t0, P->t2);
-    if (c->trk_n > 0)
-        return set_error(YOUTH_EINVAL, "set_depth_filter: %d frames in flight (collect them first)",
-                         c->trk_n);
-    if (P) {
-        int rc = bind_device(c);
-        if (rc) return rc;
-        rc = ensure_raw(c);
-        if (rc) return rc;
-        c->flt = *P;
-    }
-    c->flt_on = P != nullptr;
-    return YOUTH_OK;
-}
-
-int youth_icp_get_depth_filter(const youth_icp_ctx* c, youth_filter_params* out)
-{
-    if (!c) return set_error(YOUTH_EINVAL, "get_depth_filter: null context");
-    if (c->flt_on && out) *out = c->flt;
-    return c->flt_on ? 1 : 0;
-}
-
-static int track_submit_frames(youth_icp_ctx* c, const int16_t* depth, int m,
-                               const double* T_init, const int16_t* const* frames = nullptr)
-{
-    hipStream_t s = c->stream;
-    const size_t N = c->N;
-    const int nds = trk_depth_slots(c), nrs = trk_record_slots(c);
-    // depth slots: the half the previous launch did not use
-    const int half = nds / 2;
-    const int d0 = c->trk_prev_d0 >= half || c->trk_prev_d0 < 0 ? 0 : half;
-    // record slots for the new frames: the first m that are not the reference
-    const int ref = c->track_ref;
-    int rs[kCoopMaxChain] = {};
-    for (int r = 0, k = 0; r < nrs && k < m; ++r)
-        if (r != ref) rs[k++] = r;
-    int qi[kCoopMaxChain];
-    if (c->flt_on) {   // enabled by the environment: the staging comes with the first frame
-        const int rc = ensure_raw(c);
-        if (rc) return rc;
-    }
-    // where the upload lands: the depth slots, or the filter's raw staging
-    int16_t* const land = c->flt_on ? c->d_raw : c->d_depth + (size_t)d0 * N;
-    track_grow(c, c->trk_n + m);
-    for (int i = 0; i < m; ++i) {
-        qi[i] = (c->trk_head + c->trk_n + i) % c->trk_cap;
-        const int rc = track_entry_pinned(c, qi[i], !frames);  // before anything is enqueued
-        if (rc) return rc;
-    }
-    trace_step(1);
-    auto& ql = c->trk[qi[m - 1]];
-    // the caller's buffers are free on return: copy into the entries' pinned
-    // staging, then H2D after the last launch that read these depth slots
-    // the copies' stream: the transfer stream (overlaps the launch before),
-    // or with YOUTH_ICP_TRACK_COPY=compute the launch stream itself (A/B)
-    hipStream_t xs = c->trk_copy_compute ? s : c->xfer;
-    if (!frames) {
-        const size_t fb = N * sizeof(int16_t);
-        if (c->trk_copy_helpers > 0 && (size_t)m * fb >= c->trk_copy_min) {
-            if (!c->copy_pool) c->copy_pool.reset(new youth::HostCopyPool(c->trk_copy_helpers));
-            youth::HostCopyPool::Seg seg[kCoopMaxChain];
-            for (int i = 0; i < m; ++i) seg[i] = {c->trk[qi[i]].pinned, depth + (size_t)i * N, fb};
-            // ~4 pieces per copier per micro-batch: late wake-ups even out
-            const size_t piece = (size_t)m * fb / (4 * (c->trk_copy_helpers + 1));
-            c->copy_pool->run(seg, m, std::max(piece, (size_t)64 << 10));
-        } else {
-            for (int i = 0; i < m; ++i) memcpy(c->trk[qi[i]].pinned, depth + (size_t)i * N, fb);
-        }
-    }
-    hipEvent_t waited[kCoopMaxChain];
-    int nw = 0;
-    for (int i = 0; i < m; ++i) {
-        const int last = c->trk_dslot_last[d0 + i];
-        if (last < 0 || xs == s) continue;
-        // the slots of one earlier launch share its event: wait once per event
-        hipEvent_t ev = c->trk[last].ev;
-        bool dup = false;
-        for (int k = 0; k < nw; ++k) dup |= waited[k] == ev;
-        if (!dup) {
-            HIP_TRY(hipStreamWaitEvent(xs, ev, 0));
-            waited[nw++] = ev;
-        }
-    }
-    trace_step(2);
-    // the caller's frames are pulled in place only when youth_icp_host_alloc
-    // made them (the staging buffers always are page-locked)
-    bool pull = !c->trk_copy_sdma;
-    for (int i = 0; pull && frames && i < m; ++i) pull = host_alloc_covers(frames[i], N);
-    if (pull) {
-        FramePtrs fp{};
-        for (int i = 0; i < m; ++i) fp.src[i] = frames ? frames[i] : c->trk[qi[i]].pinned;
-        // ~16 workgroups per launch: 2 per frame in a micro-batch of 8 (one
-        // per free CU, profiles/r05/slam_pull_reserve_r5s.txt), 16 for a
-        // single frame (its latency)
-        const int wg = c->trk_pull_wg > 0 ? c->trk_pull_wg : std::max(2, 16 / m);
-        // its LDS reservation (unused) keeps a workgroup off the CUs where a
-        // micro-batch grid's workgroup sits (~143 KB of 160 at 640x480), so
-        // the pull runs on the CUs the plan left free instead of slowing the
-        // grid's barriers (youth_icp_track_set_batch)
-        hipLaunchKernelGGL(k_pull_frames, dim3(wg, m), dim3(64), (unsigned)c->trk_pull_lds, xs, fp,
-                           land, (int)N, m);
-        HIP_TRY(hipGetLastError());
-    } else {
-        for (int i = 0; i < m; ++i)
-            HIP_TRY(hipMemcpyAsync(land + (size_t)i * N,
-                                   frames ? frames[i] : c->trk[qi[i]].pinned, N * sizeof(int16_t),
-                                   hipMemcpyHostToDevice, xs));
-    }
-    if (c->flt_on) {   // raw staging -> depth slots, before the H2D event
-        const int rc = track_filter(c, m, c->d_depth + (size_t)d0 * N, xs);
-        if (rc) return rc;
-    }
-    trace_step(3);
-    if (xs != s) {
-        HIP_TRY(hipEventRecord(ql.h2d, xs));
-        HIP_TRY(hipStreamWaitEvent(s, ql.h2d, 0));
-    }
-    trace_step(4);
-    const int16_t* dsrc = c->d_depth + (size_t)d0 * N;
-    int rc = YOUTH_OK;
-    bool kernel_result = false;  // k_icp_coop stored the result(s) to host memory
-    if (ref < 0) {
-        // first frame of a sequence: prep only (m == 1)
-        rc = launch_prep(c, s, dsrc, 1, rs[0], false);
-    } else if (m == 1) {
-        // source: the new frame's depth; target: ref's records; the new frame
-        // is prepped beside the iterations as the next reference.  k_icp_coop
-        // writes the result into the pinned slot itself; any other kernel path
-        // copies it
-        const PrepJob job{dsrc, 1, rs[0], false};
-        c->coop_res_host = ql.res;
-        rc = run_iterations(c, s, dsrc, PairMap{0, ref}, 1, T_init, nullptr, nullptr, &job);
-        c->coop_res_host = nullptr;
-        kernel_result = c->last_coop;
-        if (rc == YOUTH_OK && !c->last_coop) {
-            HIP_TRY(hipMemcpyAsync(ql.res, c->d_T64, 16 * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(ql.res + 16, c->d_status, sizeof(int32_t),
-                                   hipMemcpyDeviceToHost, s));
-        }
-    } else {
-        PrepJob job{dsrc, m, 0, false};
-        job.chain = true;
-        for (int i = 0; i < m; ++i) {
-            job.tgt_slot[i] = i == 0 ? ref : rs[i - 1];
-            job.prep_slot[i] = rs[i];
-            job.res[i] = c->trk[qi[i]].res;
-        }
-        rc = run_iterations(c, s, dsrc, PairMap{0, 0}, m, nullptr, nullptr, nullptr, &job);
-        kernel_result = true;
-        if (rc == YOUTH_OK) ++c->trk_chained;
-    }
-    trace_step(5);
-    if (rc) {
-        // nothing of these frames is kept; wait for what was enqueued so the
-        // staging buffers and the slots are not in use by dropped frames
-        (void)hipStreamSynchronize(s);
-        (void)hipStreamSynchronize(c->xfer);
-        return rc;
-    }
-    // no result to publish (first frame) or k_icp_coop stored it to host
-    // memory itself: no system-scope fence; else the copies' result needs it
-    hipEvent_t ev = (ref < 0 || kernel_result) ? ql.done_nf : ql.done;
-    HIP_TRY(hipEventRecord(ev, s));
-    for (int i = 0; i < m; ++i) {
-        auto& q = c->trk[qi[i]];
-        q.ev = ev;
-        q.has_ref = (i > 0 || ref >= 0) ? 1 : 0;
-        c->trk_dslot_last[d0 + i] = qi[m - 1];
-    }
-    c->trk_prev_d0 = d0;
-    c->track_ref = rs[m - 1];
-    c->trk_n += m;
-    return YOUTH_OK;
-}
-
-int youth_icp_track_submit(youth_icp_ctx* c, const int16_t* depth, const double* T_init)
-{
-    if (!c || !depth) return set_error(YOUTH_EINVAL, "track_submit: bad arguments");
-    if (c->trk_n >= kTrackDepth)
-        return set_error(YOUTH_EINVAL, "track_submit: %d frames in flight (collect one first)",
-                         kTrackDepth);
-    if (T_init)
-        for (int i = 0; i < 16; ++i)
-            if (!std::isfinite(T_init[i]))
-                return set_error(YOUTH_EINVAL, "T_init: non-finite entry in pair 0");
-    int rc = bind_device(c);
-    if (rc) return rc;
-    rc = ensure_track(c);
-    if (rc) return rc;
-    return track_submit_frames(c, depth, 1, T_init);
-}
-
-// youth_icp_track_submit_batch (depth: n_frames consecutive frames, staged)
-// and youth_icp_track_submit_pinned (frames: the caller's page-locked buffers).
-static int track_submit_many(youth_icp_ctx* c, const int16_t* depth,
-                             const int16_t* const* frames, int n_frames)
-{
-    if (c->trk_n + n_frames > kTrackDepth)
-        return set_error(YOUTH_EINVAL, "track_submit_batch: %d + %d frames in flight (max %d)",
-                         c->trk_n, n_frames, kTrackDepth);
-    int rc = bind_device(c);
-    if (rc) return rc;
-    rc = ensure_track(c);
-    if (rc) return rc;
-    const size_t N = c->N;
-    int done = 0;
-    if (c->track_ref < 0) {  // no reference yet: the first frame is only prepped
-        rc = track_submit_frames(c, depth, 1, nullptr, frames);
-        if (rc) return rc;
-        done = 1;
-    }
-    // the rest in the longest chains that fit, else one launch per frame
-    while (done < n_frames) {
-        int m = n_frames - done;
-        while (m > 1 && !trk_chain_fits(c, m)) --m;
-        rc = track_submit_frames(c, frames ? nullptr : depth + (size_t)done * N, m, nullptr,
-                                 frames ? frames + done : nullptr);
-        if (rc) return rc;
-        if (m > 1) c->trk_chained_frames += m;
-        done += m;
-    }
-    return YOUTH_OK;
-}
-
-int youth_icp_track_submit_batch(youth_icp_ctx* c, const int16_t* depth, int n_frames)
-{
-    if (!c || !depth || n_frames < 1 || n_frames > YOUTH_TRACK_MAX_BATCH)
-        return set_error(YOUTH_EINVAL, "track_submit_batch: bad arguments (%d frames)", n_frames);
-    return track_submit_many(c, depth, nullptr, n_frames);
-}
-
-int youth_icp_track_submit_pinned(youth_icp_ctx* c, const int16_t* const* frames, int n_frames)
-{
-    if (!c || !frames || n_frames < 1 || n_frames > YOUTH_TRACK_MAX_BATCH)
-        return set_error(YOUTH_EINVAL, "track_submit_pinned: bad arguments (%d frames)", n_frames);
-    for (int i = 0; i < n_frames; ++i)
-        if (!frames[i]) return set_error(YOUTH_EINVAL, "track_submit_pinned: frame %d is null", i);
-    return track_submit_many(c, nullptr, frames, n_frames);
-}
-
-int16_t* youth_icp_host_alloc(size_t values)
-{
-    if (!values) return nullptr;
-    int16_t* p = nullptr;
-    if (hipHostMalloc((void**)&p, values * sizeof(int16_t), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    std::lock_guard<std::mutex> lk(g_host_mu);
-    g_host_bufs[(uintptr_t)p] = values * sizeof(int16_t);
-    return p;
-}
-
-void youth_icp_host_free(int16_t* p)
-{
-    if (!p) return;
-    {
-        std::lock_guard<std::mutex> lk(g_host_mu);
-        g_host_bufs.erase((uintptr_t)p);
-    }
-    (void)hipHostFree(p);
-}
-
-// A collect waits for its frame by polling the event for up to 2 ms before
-// the runtime's blocking wait: a sleeping wait's wake-up cost a backlogged
-// SLAM worker up to ~0.6 ms per micro-batch (profiles/r04/slamtrace_r4k.txt).
-// YOUTH_ICP_TRACK_WAIT=sync keeps the blocking wait only (A/B).
-static hipError_t track_wait(hipEvent_t ev)
-{
-    static const bool poll = [] {
-        const char* e = getenv("YOUTH_ICP_TRACK_WAIT");
-        return !(e && strcmp(e, "sync") == 0);
-    }();
-    if (poll) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (;;) {
-            const hipError_t r = hipEventQuery(ev);
-            if (r != hipErrorNotReady) return r;
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-        }
-    }
-    return hipEventSynchronize(ev);
-}
-
-int youth_icp_track_collect(youth_icp_ctx* c, double* T_rel, int* has_ref)
-{
-    if (!c || !T_rel) return set_error(YOUTH_EINVAL, "track_collect: bad arguments");
-    if (c->trk_n == 0) return set_error(YOUTH_EINVAL, "track_collect: no frame in flight");
-    int rc = bind_device(c);
-    if (rc) return rc;
-    auto& q = c->trk[c->trk_head];
-    c->trk_head = (c->trk_head + 1) % c->trk_cap;
-    --c->trk_n;
-    HIP_TRY(track_wait(q.ev));
-    if (has_ref) *has_ref = q.has_ref;
-    if (!q.has_ref) {
-        for (int i = 0; i < 16; ++i) T_rel[i] = (i % 5) == 0 ? 1.0 : 0.0;
-        return 0;
-    }
-    for (int i = 0; i < 12; ++i) T_rel[i] = q.res[i];
-    T_rel[12] = 0.0;
-    T_rel[13] = 0.0;
-    T_rel[14] = 0.0;
-    T_rel[15] = 1.0;
-    int32_t st;
-    memcpy(&st, q.res + 16, sizeof(st));
-    return st;
-}
-
-int youth_icp_track_pending(const youth_icp_ctx* c)
-{
-    return c ? c->trk_n : 0;
-}
-
-// A tracker align that came back with YOUTH_STATUS_TIMEOUT (its cooperative
-// grid was not co-resident: another process held CUs, or the test hook) is
-// aligned again here from host copies of its two frames, synchronously.
-// Everything the tracker has enqueued finishes first, so the depth slots
-// 0 / 1 and a record slot other than the reference's are free to use, and
-// the tracker continues afterwards as if nothing had happened (its reference
-// records are untouched; a timed-out launch still preps every tile of its
-// frames, because its workgroups prep before they wait).
-//   1. the context's own single-pair plan: the cooperative kernel preps the
-//      target and aligns, with the npx / G / tile mapping the tracker's
-//      single-frame and chained launches use, so a successful retry gives the
-//      pose the undisturbed launch would have, bit for bit;
-//   2. if that times out too, the persistent k_prep + k_icp, which waits only
-//      on workgroups that are running (no co-residency assumption): the same
-//      pose up to fp64 summation order (~1e-16 relative).
-int youth_icp_track_realign(youth_icp_ctx* c, const int16_t* ref_depth, const int16_t* depth,
-                            const double* T_init, double* T_rel)
-{
-    if (!c || !ref_depth || !depth || !T_rel)
-        return set_error(YOUTH_EINVAL, "track_realign: bad arguments");
-    if (T_init)
-        for (int i = 0; i < 16; ++i)
-            if (!std::isfinite(T_init[i]))
-                return set_error(YOUTH_EINVAL, "T_init: non-finite entry in pair 0");
-    int rc = bind_device(c);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    HIP_TRY(hipStreamSynchronize(s));
-    if (c->xfer) HIP_TRY(hipStreamSynchronize(c->xfer));
-    const size_t N = c->N;
-    const int rslot = c->track_ref == 0 ? 1 : 0;
-    if (c->flt_on) {
-        rc = ensure_raw(c);
-        if (rc) return rc;
-    }
-    int16_t* const land = c->flt_on ? c->d_raw : c->d_depth;
-    HIP_TRY(hipMemcpyAsync(land, depth, N * sizeof(int16_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(land + N, ref_depth, N * sizeof(int16_t), hipMemcpyHostToDevice, s));
-    if (c->flt_on) {
-        rc = track_filter(c, 2, c->d_depth, s);
-        if (rc) return rc;
-    }
-    const PrepJob job{c->d_depth + N, 1, rslot, true};
-    c->coop_res_host = nullptr;
-    int32_t st = YOUTH_STATUS_TIMEOUT;
-    for (int attempt = 0; attempt < 2 && (st & YOUTH_STATUS_TIMEOUT); ++attempt) {
-        const bool coop_was = c->coop;
-        if (attempt == 1) c->coop = false;  // the persistent kernel
-        if (attempt == 0 && c->realign_stall) {  // test hook: this coop launch loses a row
-            c->coop_stall_once = 0;
-            c->coop_stall_left = 1;
-        }
-        rc = run_iterations(c, s, c->d_depth, PairMap{0, rslot}, 1, T_init, nullptr, nullptr, &job);
-        const bool ran_coop = c->last_coop;
-        if (attempt == 1) c->coop = coop_was;
-        if (rc) return rc;
-        double T[16];
-        unsigned err = 0;
-        HIP_TRY(hipMemcpyAsync(T, c->d_T64, sizeof(T), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&st, c->d_status, sizeof(st), hipMemcpyDeviceToHost, s));
-        if (!ran_coop)  // the persistent kernel's spin bound lands in the queue's error word
-            HIP_TRY(hipMemcpyAsync(&err, c->d_head + kQError, sizeof(err), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (err) st |= YOUTH_STATUS_TIMEOUT;
-        for (int i = 0; i < 12; ++i) T_rel[i] = T[i];
-        T_rel[12] = T_rel[13] = T_rel[14] = 0.0;
-        T_rel[15] = 1.0;
-        if (!(st & YOUTH_STATUS_TIMEOUT)) ++c->trk_realigned[ran_coop ? 0 : 1];
-        // a refused cooperative launch already ran the persistent path
-        if (!ran_coop) break;
-    }
-    if (st & YOUTH_STATUS_TIMEOUT) ++c->trk_realigned[2];
-    return st;
-}
-
-long long youth_icp_track_realigned(const youth_icp_ctx* c, long long* persistent, long long* failed)
-{
-    if (persistent) *persistent = c ? c->trk_realigned[1] : 0;
-    if (failed) *failed = c ? c->trk_realigned[2] : 0;
-    return c ? c->trk_realigned[0] : 0;
-}
-
-int youth_icp_track_host_sequence(youth_icp_ctx* c, const int16_t* frames, int n_frames,
-                                  double* T_rel, int32_t* status)
-{
-    if (!c || !frames || n_frames < 0 || !T_rel)
-        return set_error(YOUTH_EINVAL, "track_host_sequence: bad arguments");
-    if (c->trk_n) return set_error(YOUTH_EINVAL, "track_host_sequence: submitted frames not collected");
-    const size_t N = c->N;
-    int written = 0, collected = 0;
-    auto collect = [&]() -> int {
-        double T[16];
-        int has = 0;
-        int st = youth_icp_track_collect(c, T, &has);
-        const int f = collected++;  // sequence index of the collected frame
-        if (st < 0) return st;
-        // a timed-out align is aligned again against the frame before it
-        // (frame 0's reference came from an earlier call: its status keeps
-        // the TIMEOUT bit)
-        if (has && (st & YOUTH_STATUS_TIMEOUT) && f >= 1) {
-            const int st2 = youth_icp_track_realign(c, frames + (size_t)(f - 1) * N,
-                                                    frames + (size_t)f * N, nullptr, T);
-            if (st2 < 0) return st2;
-            st = st2;
-        }
-        if (has) {
-            memcpy(T_rel + (size_t)written * 16, T, sizeof(T));
-            if (status) status[written] = st;
-            ++written;
-        }
-        return YOUTH_OK;
-    };
-    // batch: frames per submission (1: one launch per frame, as the SLAM
-    // worker at camera rate; 2: micro-batches of two frames when they fit one
-    // cooperative grid, the pose of each frame bit-identical either way)
-    const int batch = c->trk_batch;
-    for (int f = 0; f < n_frames;) {
-        const int m = std::min(batch, n_frames - f);
-        // keep two submissions in flight: two frames, or two micro-batches
-        while (c->trk_n + m > (batch > 1 ? 2 * batch : 2)) {
-            const int rc = collect();
-            if (rc) {
-                while (c->trk_n) (void)collect();
-                return rc;
-            }
-        }
-        const int rc = m == 1 ? youth_icp_track_submit(c, frames + (size_t)f * N, nullptr)
-                              : youth_icp_track_submit_batch(c, frames + (size_t)f * N, m);
-        if (rc) {
-            while (c->trk_n) (void)collect();
-            return rc;
-        }
-        f += m;
-    }
-    while (c->trk_n) {
-        const int rc = collect();
-        if (rc) {
-            while (c->trk_n) (void)collect();
-            return rc;
-        }
-    }
-    return written;
-}
-
-int youth_icp_track_frame(youth_icp_ctx* c, const int16_t* depth, const double* T_init,
-                          double* T_rel, int* has_ref)
-{
-    if (!c || !depth || !T_rel) return set_error(YOUTH_EINVAL, "track_frame: bad arguments");
-    if (c->trk_n) return set_error(YOUTH_EINVAL, "track_frame: submitted frames not collected");
-    const int rc = youth_icp_track_submit(c, depth, T_init);
-    if (rc) return rc;
-    return youth_icp_track_collect(c, T_rel, has_ref);
-}
-
-int youth_icp_track_set_batch(youth_icp_ctx* c, int frames)
-{
-    if (!c || frames < 1 || frames > YOUTH_TRACK_MAX_BATCH)
-        return set_error(YOUTH_EINVAL, "track_set_batch: bad arguments (%d)", frames);
-    const int old = c->trk_batch;
-    c->trk_batch = frames;
-    // batch mode: the fewest source pixels per lane whose workgroups for
-    // `frames` pairs fit one grid (512-thread workgroups at 221 VGPRs are one
-    // per CU: 256 per grid; 640x480: 5 px per lane, 120 workgroups per pair),
-    // for every coop launch of the context, so batched and per-frame
-    // submissions stay bit-identical
-    c->coop_px = c->coop_px_env;
-    if (frames > 1) {
-        const int v = variant(c) * 2 + (c->fast ? 1 : 0);
-        // the plan leaves trk_pull_reserve CUs free for the next micro-batch's
-        // k_pull_frames (the co-residency limit itself stays the whole chip);
-        // the same plan on either copy path, so their poses are bit-identical
-        const int free_cu = std::min(c->trk_pull_reserve, c->n_cu / 2);
-        for (int npx = 1; npx <= kCoopMaxPx; ++npx) {
-            const long long G = (c->N + (long long)npx * c->coop_threads - 1) /
-                                ((long long)npx * c->coop_threads);
-            if (frames * G <= (long long)(c->n_cu - free_cu) * c->coop_bpc[c->coop_threads == 256][v][npx]) {
-                c->coop_px = npx;
-                break;
-            }
-        }
-    }
-    return old;
-}
-
-long long youth_icp_track_chained(const youth_icp_ctx* c) { return c ? c->trk_chained : 0; }
-
-long long youth_icp_track_chained_frames(const youth_icp_ctx* c)
-{
-    return c ? c->trk_chained_frames : 0;
-}
-
-void youth_icp_track_reset(youth_icp_ctx* c)
-{
-    if (c) c->track_ref = -1;
-}
-
-}  // extern "C"
-
-// The RGB-D alignment (include/youth_rgbd.h): k_rgbd_prep,
-// k_rgbd_reduce and their host side, on this file's device code and context.
-#include "youth_rgbd.h"
-#include "rgbd_align.inc"
+}  // namespace youth_icp

@@ -1,8 +1,9 @@
-// rgbd_align.inc — RGB-D alignment on gfx950 (C-ABI: include/youth_rgbd.h;
-// definition: DESIGN.md §13).  The tail of icp_kernels.hip: it shares that
-// file's device code (back-projection, lane masks, the wave reduce-scatter's
-// stages, the a10 solve) and its context, and leaves every kernel above as it
-// is.
+// rgbd_align.hip — RGB-D alignment on gfx950 (C-ABI: include/youth_rgbd.h;
+// definition: DESIGN.md §13): k_rgbd_prep, k_rgbd_reduce and their host side.
+// A unit of its own on icp_device.h's device code (back-projection, lane
+// masks, the wave reduce-scatter's stages, the a10 solve) and on the ICP
+// context and launch layer of icp_host.h; the depth-only kernels it needs
+// (k_prep, k_init, k_finish) run through that layer.
 //
 //   k_rgbd_prep    once per target frame: RGB -> Y (or a grey copy) and one
 //                  32-bit word per pixel {Y, gx + 255, gy + 255, valid}.  Four
@@ -23,6 +24,20 @@
 //
 // Always the survey arithmetic of a7/a8 (no FMA, IEEE division) and the exact
 // reduction of a9, whatever the ICP context's spec and reduce modes are.
+
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <cmath>
+
+#include "icp_device.h"
+#include "icp_host.h"
+#include "youth_rgbd.h"
+
+using namespace youth_icp;
 
 namespace {
 
@@ -567,10 +582,8 @@ static int rgbd_align(youth_rgbd_ctx* r, hipStream_t s, const int16_t* dsrc, con
     if (rc) return rc;
     rc = rgbd_launch_prep(s, gtgt, 1, n_tgt, c->W, c->H, nullptr, r->d_photo);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_init, dim3((n_pairs + 63) / 64), dim3(64), 0, s, dTi, n_pairs, c->d_T64,
-                       c->d_T32, c->d_status, (unsigned*)nullptr, (unsigned*)nullptr, iters,
-                       c->d_head);
-    HIP_TRY(hipGetLastError());
+    rc = launch_init(c, s, dTi, n_pairs, iters, false);
+    if (rc) return rc;
     HIP_TRY(hipMemsetAsync(c->d_arrivals, 0, (size_t)c->max_frames * sizeof(unsigned), s));
     for (int it = 0; it < iters; ++it) {
         rc = rgbd_launch_reduce(r, s, dsrc, gsrc, pm, n_pairs, it, nullptr);
@@ -580,10 +593,7 @@ static int rgbd_align(youth_rgbd_ctx* r, hipStream_t s, const int16_t* dsrc, con
     r->last_iters = iters;
     r->last_stream = s;
     if (!d_T_out) return YOUTH_OK;
-    hipLaunchKernelGGL(k_finish, dim3((n_pairs * 16 + 255) / 256), dim3(256), 0, s, c->d_T64,
-                       n_pairs, d_T_out, c->d_status, (const unsigned*)nullptr);
-    HIP_TRY(hipGetLastError());
-    return YOUTH_OK;
+    return export_poses(c, s, n_pairs, d_T_out, false);
 }
 
 extern "C" {
@@ -754,9 +764,8 @@ int youth_rgbd_get_poses(youth_rgbd_ctx* r, int n, double* T64, float* T32, int3
         HIP_TRY(hipMemcpyAsync(T64, c->d_T64, (size_t)n * 16 * sizeof(double),
                                hipMemcpyDeviceToHost, s));
     if (T32) {
-        hipLaunchKernelGGL(k_finish, dim3((n * 16 + 255) / 256), dim3(256), 0, s, c->d_T64, n,
-                           c->d_Tout, c->d_status, (const unsigned*)nullptr);
-        HIP_TRY(hipGetLastError());
+        rc = export_poses(c, s, n, c->d_Tout, false);
+        if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(T32, c->d_Tout, (size_t)n * 16 * sizeof(float),
                                hipMemcpyDeviceToHost, s));
     }

@@ -1069,7 +1069,7 @@ int youth_slam_map_render(const struct youth_map_view* view, const youth_intrins
     return mh->render(view, &Kd, T_world ? T_world : g_traj.back().T, depth, rgb);
 }
 
-// recorded from inside the tracker (icp_kernels.hip: a submission's steps)
+// recorded from inside the tracker (icp_track.cpp: a submission's steps)
 void youth_slam_trace_hook(int kind, int arg) { trace(kind, arg); }
 
 // enable / read are serialised against each other (the writers never take it)

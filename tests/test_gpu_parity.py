@@ -711,7 +711,7 @@ def test_algorithm_module_thread_entry(monkeypatch):
 
 # ------------------------------------------------ division path / alignment --
 def test_projection_reciprocal_matches_ieee():
-    """The projection reciprocal (icp_kernels.hip proj_rcp_rn) equals IEEE
+    """The projection reciprocal (icp_device.h proj_rcp_rn) equals IEEE
     1.0f / den bit for bit for EVERY fp32 den in its guarded range [2^-60,
     2^60] (exhaustive), and the projected pixel floor(fma(fx x', rz, cx) + 0.5)
     / in-range decision agrees with the IEEE reciprocal's on 2 x 2^30 random
@@ -722,7 +722,7 @@ def test_projection_reciprocal_matches_ieee():
 
 
 def test_normal_normalisation_matches_ieee():
-    """k_prep's fast normalisation (icp_kernels.hip sqrt_rn_mid / norm_div)
+    """k_prep's fast normalisation (icp_device.h sqrt_rn_mid / norm_div)
     equals sqrtf and c / sqrtf(|c|^2) bit for bit: the sqrt exhaustively over
     [2^-96, 2^118], the quotients on 2 x 2^28 random vectors of mixed
     magnitude with signed zeros (most take the fast path)."""

@@ -2,7 +2,8 @@
 //
 // Build: make -C tools coopbench
 // Run (GPU box): tools/coopbench [pairs] [px_per_lane (0: the plan's)] [W H iters]
-// Includes the production translation unit with YOUTH_COOP_PHASES, so thread
+// Includes the production kernel unit (and icp_api.cpp, for the context) with
+// YOUTH_COOP_PHASES, so thread
 // 0 of every workgroup stamps s_memrealtime (100 MHz) at 8 points of every
 // iteration: 0 start, 1 pixel loop done, 2 workgroup reduction done,
 // 3 partial row stored, 4 = 3 and 5 = 4 (no counter, no barrier since the
@@ -11,6 +12,7 @@
 // workgroup that saw them all).
 #define YOUTH_COOP_PHASES 1
 #include "../slam-rgbd_amd/csrc/icp_kernels.hip"
+#include "../slam-rgbd_amd/csrc/icp_api.cpp"
 
 #include <algorithm>
 

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Make a phase-instrumented copy of icp_kernels.hip (A/B tooling only; the
-product kernel is never built this way).
+product kernel is never built this way).  Written when the C API was part of
+that file: the kernel patterns still apply to csrc/icp_kernels.hip, the last
+three (d_head's allocation, youth_icp_destroy's print) now match
+csrc/icp_api.cpp and need the same treatment there.
 
 Thread 0 of every k_icp workgroup stamps s_memtime at each step of a work
 item and, at exit, adds its per-phase cycle totals into spare words of the

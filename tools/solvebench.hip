@@ -7,7 +7,7 @@
 // i holds row i, six IEEE reciprocals and lane broadcasts); the block form
 // with the translation block eliminated first.
 // Build: make -C tools solvebench        Run (GPU box): tools/solve_probe.sh
-#include "../slam-rgbd_amd/csrc/icp_kernels.hip"
+#include "../slam-rgbd_amd/csrc/icp_device.h"
 #include <cmath>
 #include <cstring>
 #include <vector>
