@@ -1,10 +1,15 @@
 // icp_device.h — the device code that the two kernel units share:
 // icp_kernels.hip (the depth-only ICP kernels) and rgbd_align.hip (the RGB-D
-// alignment).  Layout constants and the structs kernels take by value; the
-// 64-bit lane helpers; fast / IEEE division, the projection quotient and the
-// normalisation; back-projection; lane masks; the small stages of the wave
-// reduce-scatter; the a10 solve and pose update.  The host units include it
-// (through icp_host.h) for the constants and structs alone.
+// alignment).  Layout constants and the structs kernels take by value
+// (PairMap, PoseState); the 64-bit lane helpers; fast / IEEE division, the
+// projection quotient and the normalisation; back-projection, of one pixel
+// and of a lane's four per loop step (backproject4); lane masks; spec a7-a9
+// per pixel (survey_project, xform_project, match_accumulate); the wave
+// reduce-scatter (wave_reduce_scatter<kN>); the fused solve's hand-off
+// between a pair's workgroups (handoff_publish, handoff_sum); the a10 solve
+// and pose update.  One text of the spec's arithmetic and of the summation
+// order for both units.  The host units include it (through icp_host.h) for
+// the constants and structs alone.
 //
 // No __global__ function lives here: a kernel in a shared header would be
 // emitted again by every unit that includes it.
@@ -512,6 +517,19 @@ struct PairMap {
     int src0, tgt0;  // pair p: source depth frame src0 + p, target record frame tgt0 + p
 };
 
+// Per-iteration pose state for the fused solve (k_reduce's kFuse;
+// k_rgbd_reduce's RgbdState derives from it).  T32 is read by every workgroup
+// of pair p at entry and rewritten only by p's LAST workgroup, after all of
+// p's workgroups have arrived (so after they read it).
+struct PoseState {
+    double* T64;          // [pair][16]
+    float* T32;           // [pair][12]
+    int32_t* status;      // [pair]
+    double* stats;        // [pair][iters][2] or null
+    unsigned* arrivals;   // [pair], zero at launch; re-armed by the last arriver
+    int it, iters;
+};
+
 template <bool kAligned>
 __device__ __forceinline__ short4 load_depth4(const int16_t* __restrict__ sD, int i, int end)
 {
@@ -528,6 +546,36 @@ __device__ __forceinline__ short4 load_depth4(const int16_t* __restrict__ sD, in
     return d;
 }
 
+// Source points of a lane's four pixels i .. i + 3 of one loop step, depths
+// dd[0..3], pixel i at column u0 of row v0 (accumulate_chunk, k_rgbd_reduce):
+// point(q, x, y, z) takes each as it is formed (the callers project it at
+// once; statement order matters to the scheduler, as does dd being the
+// caller's array: HISTORY.md).  kAligned: the four share a row, centred
+// coordinates by exact additions (uc0 + q == (float)(u0 + q) - cx, which the
+// host checked for these intrinsics: centred_exact).  Else a pixel past the
+// row's end wraps to the next row, and one at or past `end` back-projects
+// depth 0, an invalid point.
+template <bool kFast, bool kAligned, typename Fn>
+__device__ __forceinline__ void backproject4(const int* dd, int i, int end, int u0, int v0,
+                                             int W, const Intr& K, const FastK& F, Fn&& point)
+{
+    const float uc0 = (float)u0 - K.cx, vc0 = (float)v0 - K.cy;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        float sx, sy, sz;
+        if (kAligned) {
+            backproject_c<kFast>(dd[q], uc0 + (float)q, vc0, K, F, sx, sy, sz);
+        } else {
+            int u = u0 + q, v = v0;
+            const bool wrap = u >= W;
+            u = wrap ? u - W : u;
+            v = wrap ? v + 1 : v;
+            backproject<kFast>((i + q) < end ? dd[q] : 0, u, v, K, F, sx, sy, sz);
+        }
+        point(q, sx, sy, sz);
+    }
+}
+
 // Lane masks (one bit per lane of the wave, bit set only on active lanes):
 // compares go straight to SGPR masks (v_cmp), combine on the scalar unit and
 // feed selects through inverse_ballot, and a wave's match count is one
@@ -541,15 +589,193 @@ __device__ __forceinline__ LaneMask mask_ult(unsigned a, unsigned b) { return __
 __device__ __forceinline__ LaneMask mask_ule(unsigned a, unsigned b) { return __builtin_amdgcn_uicmp(a, b, kIcmpUle); }
 __device__ __forceinline__ bool lane_in(LaneMask m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 
-// Wave sum of the kNeq per-lane accumulators by recursive halving: at lane
+// ------------------------------------------------- spec a7-a9 per pixel --
+// Shared by k_reduce / k_icp (accumulate_chunk), k_icp_coop (coop_group) and
+// k_rgbd_reduce (survey_project and match_accumulate<kSpecSurvey>);
+// oracle/icp_oracle.c assoc_one / oracle_reduce evaluate the same operations
+// with the same roundings (fmaf = one rounding, -ffp-contract=off elsewhere).
+//   a7  P' = R P + t:  P'_i = fma(R_i2, z, fma(R_i1, y, fma(R_i0, x, t_i)))
+//       valid iff z > 0 and P'_z > 0;  rz = RN(1 / P'_z);
+//       u' = floor(fma(fx P'_x, rz, cx + 0.5)), v' likewise; in range of the
+//       target frame.  Unmatched pixels compute on safe values (branch-free)
+//       and gather record 0.
+//   kSpecSurvey: P'_i = ((R_i0 x + R_i1 y) + R_i2 z) + t_i and
+//       u' = floor(((fx P'_x) / P'_z + cx) + 0.5), the
+//       quotient IEEE (proj_quot on the shared correctly rounded reciprocal).
+
+// kSpecSurvey's a7, handing out the sub-pixel coordinates uf = (fx P'x) / P'z
+// + cx and vf as well: the RGB-D photometric term interpolates with them
+// (DESIGN.md §13); xform_project drops them.  Statement order matters to the
+// scheduler: uf, its floor, vf, its floor.
+__device__ __forceinline__ void survey_project(const float* T, float sx, float sy, float sz,
+                                               const Intr& K, int W, int H, float& qx, float& qy,
+                                               float& qz, float& uf, float& vf, float& fu, float& fv,
+                                               LaneMask& inm, int& j)
+{
+    qx = ((T[0] * sx + T[1] * sy) + T[2] * sz) + T[3];
+    qy = ((T[4] * sx + T[5] * sy) + T[6] * sz) + T[7];
+    qz = ((T[8] * sx + T[9] * sy) + T[10] * sz) + T[11];
+    const float nu = K.fx * qx, nv = K.fy * qy;
+    // P'_z in [2^-60, 2^60] (proj_den_ok, which implies P'_z > 0) as ONE
+    // unsigned compare on its bits (negative and NaN bit patterns lie
+    // above 2^60's): every lane takes the fast quotient with den = P'_z;
+    // a valid source whose P'_z is <= 0 or outside the range (never in
+    // practice) redoes it below as the IEEE division of the spec.  The
+    // other lanes' quotients may be inf / NaN; the mask drops them.
+    const LaneMask sok = mask_gt(sz, 0.0f);
+    const LaneMask dok = mask_ule(__float_as_uint(qz) - 0x21800000u, 0x5d800000u - 0x21800000u);
+    const float r = proj_recip(qz);
+    float pu = proj_quot(nu, qz, r);
+    float pv = proj_quot(nv, qz, r);
+    LaneMask vz = sok & dok;
+    const LaneMask slow = sok & ~dok;
+    if (__builtin_expect(slow != 0, 0)) {  // wave-uniform
+        const LaneMask qpos = mask_gt(qz, 0.0f);
+        if (lane_in(slow)) {
+            const float den = lane_in(qpos) ? qz : 1.0f;
+            pu = nu / den;
+            pv = nv / den;
+        }
+        vz |= slow & qpos;
+    }
+    // floor, in-range test and the pixel index without selects: the
+    // coordinates stay finite on every lane (saturated integers), and an
+    // unmatched lane's gather is masked after it (a raw buffer load past
+    // the records returns 0, any index inside them is a real record).
+    // The row test is the records' own: v' outside [0, H) is clamped to
+    // H, whose index lies in the frame's zeroed pad (P >= N + 4) or past
+    // the buffer (returns 0), a record with z = 0, which the match gate
+    // (tz > 0) rejects as it rejects a target without a normal
+    uf = pu + K.cx;
+    const int iu = floor_i32(uf + 0.5f);
+    vf = pv + K.cy;
+    const int iv = floor_i32(vf + 0.5f);
+    const unsigned ivc = min((unsigned)iv, (unsigned)H);
+    inm = vz & mask_ult((unsigned)iu, (unsigned)W);
+    fu = (float)iu;
+    fv = (float)iv;
+    j = (int)(__umul24(ivc, (unsigned)W) + (unsigned)iu);
+}
+
+template <int kSp>
+__device__ __forceinline__ void xform_project(const float* T, float sx, float sy, float sz,
+                                              const Intr& K, int W, int H, float& qx, float& qy,
+                                              float& qz, float& fu, float& fv, LaneMask& inm, int& j)
+{
+    if (sp_survey(kSp)) {
+        float uf, vf;
+        survey_project(T, sx, sy, sz, K, W, H, qx, qy, qz, uf, vf, fu, fv, inm, j);
+    } else {
+        qx = fmaf(T[2], sz, fmaf(T[1], sy, fmaf(T[0], sx, T[3])));
+        qy = fmaf(T[6], sz, fmaf(T[5], sy, fmaf(T[4], sx, T[7])));
+        qz = fmaf(T[10], sz, fmaf(T[9], sy, fmaf(T[8], sx, T[11])));
+        const LaneMask vz = mask_gt(sz, 0.0f) & mask_gt(qz, 0.0f);
+        const float rz = proj_rcp_rn(lane_in(vz) ? qz : 1.0f);
+        const float uu = floorf(fmaf(K.fx * qx, rz, K.cx + 0.5f));
+        const float vv = floorf(fmaf(K.fy * qy, rz, K.cy + 0.5f));
+        // 0 <= u' < W and 0 <= v' < H on the integer values: uu, vv are
+        // finite integral floats (T finite, youth_icp.h), v_cvt_i32_f32
+        // saturates outside the int range, and a negative one wraps to
+        // >= 2^31 unsigned, so the unsigned compares equal the spec's four
+        // float compares
+        const int iu = (int)uu, iv = (int)vv;
+        inm = vz & mask_ult((unsigned)iu, (unsigned)W) & mask_ult((unsigned)iv, (unsigned)H);
+        const bool in = lane_in(inm);
+        fu = in ? uu : 0.0f;
+        fv = in ? vv : 0.0f;
+        // 0 when !in; v', W <= 16384 (youth_icp_create): the 24-bit
+        // multiply-add is exact and full rate
+        j = in ? (int)__umul24((unsigned)iv, (unsigned)W) + iu : 0;
+    }
+}
+
+//   a7  gate: target valid with a normal (k_prep stores z = 0 for a target
+//       without one, so tz > 0 is both tests) and |P' - P_t|^2 < thr^2 with
+//       d2 = fma(dz, dz, fma(dy, dy, dx dx));
+//   a8  r = n.(P' - P_t) = fma(n2, dz, fma(n1, dy, n0 dx));
+//       J = [P' x n, n], (P' x n)_0 = fma(qy, n2, -(qz n1)) etc.;
+//   a9  lane32 (A = float): acc = fma(J_a, J_b, acc) in fp32, one rounding
+//       per product-add; exact (A = double): the 28 products of fp32 values
+//       are exact in fp64, one rounding per add.  Unmatched lanes skip the
+//       update, or add J = 0 and r = +-0, which leaves every sum unchanged
+//       (an accumulator is never -0: it starts at +0 and x + -x is +0).  The target's x, y are recomputed from its z with
+//       k_prep's expression (bit-identical to the stored plane).
+//   kSpecSurvey: d2 = (dx dx + dy dy) + dz dz, r = (n0 dx + n1 dy) + n2 dz,
+//       (P' x n)_0 = qy n2 - qz n1 etc. (no FMA).
+template <int kSp, bool kFast, bool kSkip, typename A>
+__device__ __forceinline__ LaneMask match_accumulate(float qx, float qy, float qz, f4v t, float fu,
+                                                     float fv, LaneMask inm, const Intr& K,
+                                                     const FastK& F, float thr2, A* acc)
+{
+    const float tz = t.x;
+    const float tx = bp_div<kFast>((fu - K.cx) * tz, K.fx, F.hfx, F.lfx);
+    const float ty = bp_div<kFast>((fv - K.cy) * tz, K.fy, F.hfy, F.lfy);
+    const float dx = qx - tx, dy = qy - ty, dz = qz - tz;
+    const float d2 = sp_survey(kSp) ? (dx * dx + dy * dy) + dz * dz
+                                        : fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+    const LaneMask okm = inm & mask_gt(tz, 0.0f) & mask_lt(d2, thr2);
+    // kSkip (the throughput kernels): unmatched lanes leave the sums
+    // unchanged by not running the update (exec-masked; a wave without a
+    // match skips it), k_icp 2 % faster than masking the normal.  Else
+    // (k_icp_coop, latency-bound: the branches cost it 5 %,
+    // profiles/r03/ab_exec_mask.txt) the normal is masked to 0, so J = 0 and
+    // r = +-0 add +0 exactly: the same sums either way
+    const bool ok = lane_in(okm);
+    if (!kSkip || ok) {
+        const float n0 = kSkip || ok ? t.y : 0.0f;
+        const float n1 = kSkip || ok ? t.z : 0.0f;
+        const float n2 = kSkip || ok ? t.w : 0.0f;
+        float r, Jf[6];
+        if (sp_survey(kSp)) {
+            r = (n0 * dx + n1 * dy) + n2 * dz;
+            Jf[0] = qy * n2 - qz * n1;
+            Jf[1] = qz * n0 - qx * n2;
+            Jf[2] = qx * n1 - qy * n0;
+        } else {
+            r = fmaf(n2, dz, fmaf(n1, dy, n0 * dx));
+            Jf[0] = fmaf(qy, n2, -(qz * n1));
+            Jf[1] = fmaf(qz, n0, -(qx * n2));
+            Jf[2] = fmaf(qx, n1, -(qy * n0));
+        }
+        Jf[3] = n0;
+        Jf[4] = n1;
+        Jf[5] = n2;
+        int k = 0;
+        if constexpr (sizeof(A) == sizeof(float)) {
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int bb = a; bb < 6; ++bb) {
+                    acc[k] = fmaf(Jf[a], Jf[bb], acc[k]);
+                    ++k;
+                }
+#pragma unroll
+            for (int a = 0; a < 6; ++a) acc[21 + a] = fmaf(Jf[a], r, acc[21 + a]);
+            acc[27] = fmaf(r, r, acc[27]);
+        } else {
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int bb = a; bb < 6; ++bb) {
+                    acc[k] = fma((double)Jf[a], (double)Jf[bb], acc[k]);
+                    ++k;
+                }
+#pragma unroll
+            for (int a = 0; a < 6; ++a) acc[21 + a] = fma((double)Jf[a], (double)r, acc[21 + a]);
+            acc[27] = fma((double)r, (double)r, acc[27]);
+        }
+    }
+    return okm;
+}
+
+// Wave sum of kN <= 32 per-lane accumulators by recursive halving: at lane
 // mask m = 32, 16, 8, 4, 2 each lane keeps one half of its remaining values
 // (the upper half iff lane & m) and sends the other half to lane ^ m, so the
 // fp64 exchanges number 16 + 8 + 4 + 2 + 1 + 1 = 32 instead of 29 x 6 for a
 // symmetric butterfly.  On exit lane 2q and 2q+1 both hold the wave total of
-// value q (q < kNeq); the summation tree is fixed, so results are
-// deterministic.  Shared by k_reduce, k_icp and k_icp_coop
-// (wave_reduce_scatter) and k_rgbd_reduce (rgbd_wave_reduce_scatter), which
-// run the two large stages themselves and these small ones after them.
+// value q (q < kN); the summation tree is fixed, so results are
+// deterministic.  wave_reduce_scatter: k_reduce, k_icp and k_icp_coop sum
+// kNeq values with it, k_rgbd_reduce the 31 of the joint record.
 //   m = 32, 16: v_permlane32_swap / v_permlane16_swap exchange the upper
 //     half-wave (odd rows) of one register with the lower half (even rows) of
 //     another.  With vdst = v[q] and src = v[q+h], each lane is left holding
@@ -590,6 +816,100 @@ __device__ __forceinline__ void rs_stage_small(double* v, int lane)
         const double keep = up ? v[q + h] : v[q];
         v[q] = keep + xchg_small<kM>(send);
     }
+}
+
+template <int kN>
+__device__ __forceinline__ void wave_reduce_scatter(const double* acc, int lane, double& total)
+{
+    static_assert(kN <= 32, "one value per lane pair");
+    double v[32];
+#pragma unroll
+    for (int q = 0; q < 32; ++q) v[q] = q < kN ? acc[q] : 0.0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {  // m = 32
+        const auto l = __builtin_amdgcn_permlane32_swap(lo32(v[q]), lo32(v[q + 16]), false, false);
+        const auto h = __builtin_amdgcn_permlane32_swap(hi32(v[q]), hi32(v[q + 16]), false, false);
+        v[q] = join64(l[0], h[0]) + join64(l[1], h[1]);
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {  // m = 16
+        const auto l = __builtin_amdgcn_permlane16_swap(lo32(v[q]), lo32(v[q + 8]), false, false);
+        const auto h = __builtin_amdgcn_permlane16_swap(hi32(v[q]), hi32(v[q + 8]), false, false);
+        v[q] = join64(l[0], h[0]) + join64(l[1], h[1]);
+    }
+    rs_stage_small<8>(v, lane);
+    rs_stage_small<4>(v, lane);
+    rs_stage_small<2>(v, lane);
+    total = v[0] + xchg_small<1>(v[0]);
+}
+
+// ------------------------------------------- the fused solve's hand-off --
+// The in-launch hand-off of k_reduce<..., kFuse> and k_rgbd_reduce
+// (cdna_hip_programming.md G16, MI355X_MICROARCH.md "Valid forms" row 1), in
+// two steps that wave 0 of every workgroup of pair p runs back to back, lane
+// < kN holding the workgroup's sum s of value `lane`:
+//   handoff_publish  write-through (sc1) stores of the workgroup's row
+//                    `mine`, drained by the storing wave, then ONE agent-scope
+//                    atomic per workgroup on ps.arrivals[p].  True only in the
+//                    workgroup whose add returns nblk - 1, the pair's last:
+//                    every other returns from the kernel.
+//   handoff_sum      the last arriver adds the pair's nblk rows (kStride
+//                    doubles apart) in a fixed order (k_solve's: lanes
+//                    0..kN-1 the first half of the rows, lanes 32.. the second
+//                    half, then one add; loads in batches of 8) and leaves the
+//                    kN pair totals in neq, in every lane.
+// No acquire fence between them: every load of the handed-off rows is an sc1
+// load and every store of them was an sc1 store drained before the add (G16:
+// the fence may then be dropped).  What a kernel does with the totals, and
+// re-arming ps.arrivals[p], stays in the kernel.  Two functions and not one
+// so that each kernel keeps the code shape it had with the text written out
+// (the early return and neq in the kernel's own body): as one function the
+// fused k_reduce measured 0.5 % slower at one pair (profiles/share/ab.txt).
+template <int kN>
+__device__ __forceinline__ bool handoff_publish(double* mine, const PoseState& ps, int p, int nblk,
+                                                int lane, double s)
+{
+    if (lane < kN)
+        __hip_atomic_store(reinterpret_cast<unsigned long long*>(mine) + lane,
+                           (unsigned long long)__double_as_longlong(s), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    unsigned ticket = 0;
+    if (lane == 0)
+        ticket = __hip_atomic_fetch_add(ps.arrivals + p, 1u, __ATOMIC_RELAXED,
+                                        __HIP_MEMORY_SCOPE_AGENT);
+    ticket = __shfl(ticket, 0, 64);
+    return ticket == (unsigned)nblk - 1;
+}
+
+template <int kN, int kStride>
+__device__ __forceinline__ void handoff_sum(const double* partials, int p, int nblk, int lane,
+                                            double* neq)
+{
+    static_assert(kN <= 32 && kN <= kStride, "one value per lane of a half-wave");
+    const unsigned long long* base =
+        reinterpret_cast<const unsigned long long*>(partials + (size_t)p * nblk * kStride);
+    const int half = (nblk + 1) >> 1;
+    const int k = lane & 31;
+    double t = 0.0;
+    if (k < kN) {
+        const int b0 = lane < 32 ? 0 : half;
+        const int b1 = lane < 32 ? half : nblk;
+        for (int bb = b0; bb < b1; bb += 8) {
+            double v[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                v[q] = bb + q < b1 ? __longlong_as_double((long long)__hip_atomic_load(
+                                         base + (size_t)(bb + q) * kStride + k, __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT))
+                                   : 0.0;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) t += v[q];
+        }
+    }
+    t += __shfl_down(t, 32, 64);
+#pragma unroll
+    for (int q = 0; q < kN; ++q) neq[q] = __shfl(t, q, 64);
 }
 
 // ------------------------------------------------------- k_icp_coop layout --

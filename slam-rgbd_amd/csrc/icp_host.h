@@ -227,11 +227,40 @@ int verify_fastdiv(youth_icp_ctx* c);
 // youth_icp_destroy's part: the device's coop ordering forgets c->stream.
 void coop_forget_stream(youth_icp_ctx* c);
 
+// Grow the device buffer *buf to hold at least `want` units of `per` elements;
+// *cap is its capacity in units.  A failure leaves it empty: the pointer is
+// nulled and the capacity zeroed before the new allocation.
+template <typename T, typename N>
+int grow_device_buffer(T** buf, N* cap, N want, size_t per = 1)
+{
+    if (want <= *cap) return YOUTH_OK;
+    if (*buf) HIP_TRY(hipFree(*buf));
+    *buf = nullptr;
+    *cap = 0;
+    HIP_TRY(hipMalloc(buf, (size_t)want * per * sizeof(T)));
+    *cap = want;
+    return YOUTH_OK;
+}
+
 int ensure_stats(youth_icp_ctx* c, int iters);
 int ensure_partials(youth_icp_ctx* c, size_t doubles);
 int ev_harvest(youth_icp_ctx* c);
 // chunks per pair and pixels per chunk of one iteration's launch
 int reduce_geometry(const youth_icp_ctx* c, int n_pairs, int* chunk_out);
+// N pixels in about nb chunks: the chunk rounded up to whole workgroup steps
+// (kRedStep), the chunk count recomputed from it.
+inline int round_chunks(int N, int nb, int* chunk_out)
+{
+    const int chunk = ((N + nb - 1) / nb + kRedStep - 1) / kRedStep * kRedStep;
+    *chunk_out = chunk;
+    return (N + chunk - 1) / chunk;
+}
+// Caller-given initial poses [n_pairs][16], checked finite (which keeps every
+// projected coordinate finite: the kernels' integer in-range test relies on
+// it, xform_project), on their way to d_Tinit; *dTi: d_Tinit, or null when
+// T_init_host is (identity).
+int upload_T_init(youth_icp_ctx* c, hipStream_t s, const double* T_init_host, int n_pairs,
+                  const double** dTi);
 // Whether n_pairs pairs run as one k_icp_coop grid, and its plan.
 bool coop_plan(const youth_icp_ctx* c, int n_pairs, int* npx_out, int* G_out);
 

@@ -662,182 +662,9 @@ __global__ void k_init(const double* __restrict__ T_init, int n, double* T64, fl
 // four fetches issue back to back.  Accumulators are fp64 fed with exact
 // fp32 products: the result equals the oracle's row-major fp64 sum up to
 // fp64 summation order.  (tools/kbench: 205 us for the first SoA version ->
-// 107 us for this one at 64 pairs, partial sums unchanged.)
-
-// Per-iteration pose state for the fused solve (kFuse).  T32 is read by
-// every workgroup of pair p at entry and rewritten only by p's LAST
-// workgroup, after all of p's workgroups have arrived (so after they read it).
-struct PoseState {
-    double* T64;          // [pair][16]
-    float* T32;           // [pair][12]
-    int32_t* status;      // [pair]
-    double* stats;        // [pair][iters][2] or null
-    unsigned* arrivals;   // [pair], zero at launch; re-armed by the last arriver
-    int it, iters;
-};
-
-// ------------------------------------------------- spec a7-a9 per pixel --
-// Shared by k_reduce / k_icp (accumulate_chunk) and k_icp_coop (coop_group);
-// oracle/icp_oracle.c assoc_one / oracle_reduce evaluate the same operations
-// with the same roundings (fmaf = one rounding, -ffp-contract=off elsewhere).
-//   a7  P' = R P + t:  P'_i = fma(R_i2, z, fma(R_i1, y, fma(R_i0, x, t_i)))
-//       valid iff z > 0 and P'_z > 0;  rz = RN(1 / P'_z);
-//       u' = floor(fma(fx P'_x, rz, cx + 0.5)), v' likewise; in range of the
-//       target frame.  Unmatched pixels compute on safe values (branch-free)
-//       and gather record 0.
-//   kSpecSurvey: P'_i = ((R_i0 x + R_i1 y) + R_i2 z) + t_i and
-//       u' = floor(((fx P'_x) / P'_z + cx) + 0.5), the
-//       quotient IEEE (proj_quot on the shared correctly rounded reciprocal).
-
-template <int kSp>
-__device__ __forceinline__ void xform_project(const float* T, float sx, float sy, float sz,
-                                              const Intr& K, int W, int H, float& qx, float& qy,
-                                              float& qz, float& fu, float& fv, LaneMask& inm, int& j)
-{
-    if (sp_survey(kSp)) {
-        qx = ((T[0] * sx + T[1] * sy) + T[2] * sz) + T[3];
-        qy = ((T[4] * sx + T[5] * sy) + T[6] * sz) + T[7];
-        qz = ((T[8] * sx + T[9] * sy) + T[10] * sz) + T[11];
-        const float nu = K.fx * qx, nv = K.fy * qy;
-        // P'_z in [2^-60, 2^60] (proj_den_ok, which implies P'_z > 0) as ONE
-        // unsigned compare on its bits (negative and NaN bit patterns lie
-        // above 2^60's): every lane takes the fast quotient with den = P'_z;
-        // a valid source whose P'_z is <= 0 or outside the range (never in
-        // practice) redoes it below as the IEEE division of the spec.  The
-        // other lanes' quotients may be inf / NaN; the mask drops them.
-        const LaneMask sok = mask_gt(sz, 0.0f);
-        const LaneMask dok = mask_ule(__float_as_uint(qz) - 0x21800000u, 0x5d800000u - 0x21800000u);
-        const float r = proj_recip(qz);
-        float pu = proj_quot(nu, qz, r);
-        float pv = proj_quot(nv, qz, r);
-        LaneMask vz = sok & dok;
-        const LaneMask slow = sok & ~dok;
-        if (__builtin_expect(slow != 0, 0)) {  // wave-uniform
-            const LaneMask qpos = mask_gt(qz, 0.0f);
-            if (lane_in(slow)) {
-                const float den = lane_in(qpos) ? qz : 1.0f;
-                pu = nu / den;
-                pv = nv / den;
-            }
-            vz |= slow & qpos;
-        }
-        // floor, in-range test and the pixel index without selects: the
-        // coordinates stay finite on every lane (saturated integers), and an
-        // unmatched lane's gather is masked after it (a raw buffer load past
-        // the records returns 0, any index inside them is a real record).
-        // The row test is the records' own: v' outside [0, H) is clamped to
-        // H, whose index lies in the frame's zeroed pad (P >= N + 4) or past
-        // the buffer (returns 0), a record with z = 0, which the match gate
-        // (tz > 0) rejects as it rejects a target without a normal
-        const int iu = floor_i32((pu + K.cx) + 0.5f);
-        const int iv = floor_i32((pv + K.cy) + 0.5f);
-        const unsigned ivc = min((unsigned)iv, (unsigned)H);
-        inm = vz & mask_ult((unsigned)iu, (unsigned)W);
-        fu = (float)iu;
-        fv = (float)iv;
-        j = (int)(__umul24(ivc, (unsigned)W) + (unsigned)iu);
-    } else {
-        qx = fmaf(T[2], sz, fmaf(T[1], sy, fmaf(T[0], sx, T[3])));
-        qy = fmaf(T[6], sz, fmaf(T[5], sy, fmaf(T[4], sx, T[7])));
-        qz = fmaf(T[10], sz, fmaf(T[9], sy, fmaf(T[8], sx, T[11])));
-        const LaneMask vz = mask_gt(sz, 0.0f) & mask_gt(qz, 0.0f);
-        const float rz = proj_rcp_rn(lane_in(vz) ? qz : 1.0f);
-        const float uu = floorf(fmaf(K.fx * qx, rz, K.cx + 0.5f));
-        const float vv = floorf(fmaf(K.fy * qy, rz, K.cy + 0.5f));
-        // 0 <= u' < W and 0 <= v' < H on the integer values: uu, vv are
-        // finite integral floats (T finite, youth_icp.h), v_cvt_i32_f32
-        // saturates outside the int range, and a negative one wraps to
-        // >= 2^31 unsigned, so the unsigned compares equal the spec's four
-        // float compares
-        const int iu = (int)uu, iv = (int)vv;
-        inm = vz & mask_ult((unsigned)iu, (unsigned)W) & mask_ult((unsigned)iv, (unsigned)H);
-        const bool in = lane_in(inm);
-        fu = in ? uu : 0.0f;
-        fv = in ? vv : 0.0f;
-        // 0 when !in; v', W <= 16384 (youth_icp_create): the 24-bit
-        // multiply-add is exact and full rate
-        j = in ? (int)__umul24((unsigned)iv, (unsigned)W) + iu : 0;
-    }
-}
-
-//   a7  gate: target valid with a normal (k_prep stores z = 0 for a target
-//       without one, so tz > 0 is both tests) and |P' - P_t|^2 < thr^2 with
-//       d2 = fma(dz, dz, fma(dy, dy, dx dx));
-//   a8  r = n.(P' - P_t) = fma(n2, dz, fma(n1, dy, n0 dx));
-//       J = [P' x n, n], (P' x n)_0 = fma(qy, n2, -(qz n1)) etc.;
-//   a9  lane32 (A = float): acc = fma(J_a, J_b, acc) in fp32, one rounding
-//       per product-add; exact (A = double): the 28 products of fp32 values
-//       are exact in fp64, one rounding per add.  Unmatched lanes skip the
-//       update, or add J = 0 and r = +-0, which leaves every sum unchanged
-//       (an accumulator is never -0: it starts at +0 and x + -x is +0).  The target's x, y are recomputed from its z with
-//       k_prep's expression (bit-identical to the stored plane).
-//   kSpecSurvey: d2 = (dx dx + dy dy) + dz dz, r = (n0 dx + n1 dy) + n2 dz,
-//       (P' x n)_0 = qy n2 - qz n1 etc. (no FMA).
-template <int kSp, bool kFast, bool kSkip, typename A>
-__device__ __forceinline__ LaneMask match_accumulate(float qx, float qy, float qz, f4v t, float fu,
-                                                     float fv, LaneMask inm, const Intr& K,
-                                                     const FastK& F, float thr2, A* acc)
-{
-    const float tz = t.x;
-    const float tx = bp_div<kFast>((fu - K.cx) * tz, K.fx, F.hfx, F.lfx);
-    const float ty = bp_div<kFast>((fv - K.cy) * tz, K.fy, F.hfy, F.lfy);
-    const float dx = qx - tx, dy = qy - ty, dz = qz - tz;
-    const float d2 = sp_survey(kSp) ? (dx * dx + dy * dy) + dz * dz
-                                        : fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-    const LaneMask okm = inm & mask_gt(tz, 0.0f) & mask_lt(d2, thr2);
-    // kSkip (the throughput kernels): unmatched lanes leave the sums
-    // unchanged by not running the update (exec-masked; a wave without a
-    // match skips it), k_icp 2 % faster than masking the normal.  Else
-    // (k_icp_coop, latency-bound: the branches cost it 5 %,
-    // profiles/r03/ab_exec_mask.txt) the normal is masked to 0, so J = 0 and
-    // r = +-0 add +0 exactly: the same sums either way
-    const bool ok = lane_in(okm);
-    if (!kSkip || ok) {
-        const float n0 = kSkip || ok ? t.y : 0.0f;
-        const float n1 = kSkip || ok ? t.z : 0.0f;
-        const float n2 = kSkip || ok ? t.w : 0.0f;
-        float r, Jf[6];
-        if (sp_survey(kSp)) {
-            r = (n0 * dx + n1 * dy) + n2 * dz;
-            Jf[0] = qy * n2 - qz * n1;
-            Jf[1] = qz * n0 - qx * n2;
-            Jf[2] = qx * n1 - qy * n0;
-        } else {
-            r = fmaf(n2, dz, fmaf(n1, dy, n0 * dx));
-            Jf[0] = fmaf(qy, n2, -(qz * n1));
-            Jf[1] = fmaf(qz, n0, -(qx * n2));
-            Jf[2] = fmaf(qx, n1, -(qy * n0));
-        }
-        Jf[3] = n0;
-        Jf[4] = n1;
-        Jf[5] = n2;
-        int k = 0;
-        if constexpr (sizeof(A) == sizeof(float)) {
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int bb = a; bb < 6; ++bb) {
-                    acc[k] = fmaf(Jf[a], Jf[bb], acc[k]);
-                    ++k;
-                }
-#pragma unroll
-            for (int a = 0; a < 6; ++a) acc[21 + a] = fmaf(Jf[a], r, acc[21 + a]);
-            acc[27] = fmaf(r, r, acc[27]);
-        } else {
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int bb = a; bb < 6; ++bb) {
-                    acc[k] = fma((double)Jf[a], (double)Jf[bb], acc[k]);
-                    ++k;
-                }
-#pragma unroll
-            for (int a = 0; a < 6; ++a) acc[21 + a] = fma((double)Jf[a], (double)r, acc[21 + a]);
-            acc[27] = fma((double)r, (double)r, acc[27]);
-        }
-    }
-    return okm;
-}
+// 107 us for this one at 64 pairs, partial sums unchanged.)  The per-pixel
+// code (xform_project, match_accumulate), the wave reduce-scatter and the
+// fused solve's hand-off are icp_device.h's, shared with k_rgbd_reduce.
 
 // Accumulate source pixels [start, end) of one pair into acc (spec a7-a9).
 template <int kSp, bool kAssoc, bool kFast, bool kAligned>
@@ -884,25 +711,12 @@ __device__ __forceinline__ void accumulate_chunk(const int16_t* __restrict__ sD,
         float qx[4], qy[4], qz[4], fu[4], fv[4];
         LaneMask in[4];
         int j[4];
-        // a lane's four pixels share one row when kAligned: centred
-        // coordinates by exact additions (uc0 + q == (float)(u0 + q) - cx,
-        // which the host checked for these intrinsics: centred_exact)
-        const float uc0 = (float)u0 - K.cx, vc0 = (float)v0 - K.cy;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            float sx, sy, sz;
-            if (kAligned) {
-                backproject_c<kFast>(dd[q], uc0 + (float)q, vc0, K, F, sx, sy, sz);
-            } else {
-                int u = u0 + q, v = v0;
-                const bool wrap = u >= W;
-                u = wrap ? u - W : u;
-                v = wrap ? v + 1 : v;
-                backproject<kFast>((i + q) < end ? dd[q] : 0, u, v, K, F, sx, sy, sz);
-            }
-            xform_project<kSp>(T, sx, sy, sz, K, W, H, qx[q], qy[q], qz[q], fu[q], fv[q], in[q],
-                               j[q]);
-        }
+        backproject4<kFast, kAligned>(
+            dd, i, end, u0, v0, W, K, F,
+            [&](int q, float sx, float sy, float sz) __attribute__((always_inline)) {
+                xform_project<kSp>(T, sx, sy, sz, K, W, H, qx[q], qy[q], qz[q], fu[q], fv[q],
+                                   in[q], j[q]);
+            });
         u0 += stepU;
         v0 += stepV;
         if (u0 >= W) {
@@ -945,29 +759,6 @@ __device__ __forceinline__ void accumulate_chunk(const int16_t* __restrict__ sD,
     acc[28] += (threadIdx.x & 63) == 0 ? (double)cnt : 0.0;
 }
 
-// The wave reduce-scatter of the kNeq sums (stages and order: icp_device.h).
-__device__ __forceinline__ void wave_reduce_scatter(const double* acc, int lane, double& total)
-{
-    double v[32];
-#pragma unroll
-    for (int q = 0; q < 32; ++q) v[q] = q < kNeq ? acc[q] : 0.0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {  // m = 32
-        const auto l = __builtin_amdgcn_permlane32_swap(lo32(v[q]), lo32(v[q + 16]), false, false);
-        const auto h = __builtin_amdgcn_permlane32_swap(hi32(v[q]), hi32(v[q + 16]), false, false);
-        v[q] = join64(l[0], h[0]) + join64(l[1], h[1]);
-    }
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {  // m = 16
-        const auto l = __builtin_amdgcn_permlane16_swap(lo32(v[q]), lo32(v[q + 8]), false, false);
-        const auto h = __builtin_amdgcn_permlane16_swap(hi32(v[q]), hi32(v[q + 8]), false, false);
-        v[q] = join64(l[0], h[0]) + join64(l[1], h[1]);
-    }
-    rs_stage_small<8>(v, lane);
-    rs_stage_small<4>(v, lane);
-    rs_stage_small<2>(v, lane);
-    total = v[0] + xchg_small<1>(v[0]);
-}
 
 template <int kSp, bool kAssoc, bool kFast, bool kAligned, bool kFuse>
 __global__ __launch_bounds__(kRedThreads) void k_reduce(
@@ -999,7 +790,7 @@ __global__ __launch_bounds__(kRedThreads) void k_reduce(
     {
         const int ln = threadIdx.x & 63;
         double tot;
-        wave_reduce_scatter(acc, ln, tot);
+        wave_reduce_scatter<kNeq>(acc, ln, tot);
         if (!(ln & 1) && (ln >> 1) < kNeq) red[wave][ln >> 1] = tot;
     }
     __syncthreads();
@@ -1016,50 +807,10 @@ __global__ __launch_bounds__(kRedThreads) void k_reduce(
         if (lane < kNeq) mine[lane] = s;
         return;
     }
-    // In-launch hand-off (cdna_hip_programming.md G16, MI355X_MICROARCH.md
-    // "Valid forms" row 1): write-through (sc1) partial stores, the storing
-    // wave drains them, then ONE agent-scope atomic per workgroup; the
-    // workgroup whose add returns nblk-1 is last and reads every partial of
-    // pair p with sc1 loads only.
-    if (lane < kNeq)
-        __hip_atomic_store(reinterpret_cast<unsigned long long*>(mine) + lane,
-                           (unsigned long long)__double_as_longlong(s), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    unsigned ticket = 0;
-    if (lane == 0)
-        ticket = __hip_atomic_fetch_add(ps.arrivals + p, 1u, __ATOMIC_RELAXED,
-                                        __HIP_MEMORY_SCOPE_AGENT);
-    ticket = __shfl(ticket, 0, 64);
-    if (ticket != (unsigned)nblk - 1) return;
-    // No acquire fence: every load of the handed-off partials below is an
-    // sc1 load and every store of them was an sc1 store drained before the
-    // add (G16: the fence may then be dropped).  Fixed-order sum of pair p's
-    // partials (same order as k_solve), loads issued in batches of 8.
-    const unsigned long long* base =
-        reinterpret_cast<const unsigned long long*>(partials + (size_t)p * nblk * kNeq);
-    const int half = (nblk + 1) >> 1;
-    const int k = lane & 31;
-    double t = 0.0;
-    if (k < kNeq) {
-        const int b0 = lane < 32 ? 0 : half;
-        const int b1 = lane < 32 ? half : nblk;
-        for (int bb = b0; bb < b1; bb += 8) {
-            double v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-                v[q] = bb + q < b1 ? __longlong_as_double((long long)__hip_atomic_load(
-                                         base + (size_t)(bb + q) * kNeq + k, __ATOMIC_RELAXED,
-                                         __HIP_MEMORY_SCOPE_AGENT))
-                                   : 0.0;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) t += v[q];
-        }
-    }
-    t += __shfl_down(t, 32, 64);
+    // the hand-off (icp_device.h): only the pair's last arriver goes on
+    if (!handoff_publish<kNeq>(mine, ps, p, nblk, lane, s)) return;
     double neq[kNeq];
-#pragma unroll
-    for (int q = 0; q < kNeq; ++q) neq[q] = __shfl(t, q, 64);
+    handoff_sum<kNeq, kNeq>(partials, p, nblk, lane, neq);
     if (lane == 0) {
         ps.arrivals[p] = 0;  // re-armed for the next launch (stream order)
         if (ps.stats) {
@@ -1336,7 +1087,7 @@ __global__ __launch_bounds__(kRedThreads, 4) void k_icp(const int16_t* __restric
                                                  K, F, thr2, acc, nullptr);
         {
             double tot;
-            wave_reduce_scatter(acc, lane, tot);
+            wave_reduce_scatter<kNeq>(acc, lane, tot);
             if (!(lane & 1) && (lane >> 1) < kNeq) red[wave][lane >> 1] = tot;
         }
         __syncthreads();
@@ -1851,7 +1602,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_icp_coop(const int16_t* __restr
         if (wave < 4) COOP_MARK_WAVE(k, 11 + wave);  // slots 12-14: waves 1-3 pixel loop done
         {
             double tot;
-            wave_reduce_scatter(acc, lane, tot);
+            wave_reduce_scatter<kNeq>(acc, lane, tot);
             COOP_MARK(k, 11);
             if (!(lane & 1) && (lane >> 1) < kNeq) red[wave][lane >> 1] = tot;
         }
@@ -2036,11 +1787,7 @@ int reduce_geometry(const youth_icp_ctx* c, int n_pairs, int* chunk_out)
     const int max_nb = (c->N + 2 * kRedStep - 1) / (2 * kRedStep);
     if (nb > max_nb) nb = max_nb;
     if (nb < 1) nb = 1;
-    int chunk = (c->N + nb - 1) / nb;
-    chunk = (chunk + kRedStep - 1) / kRedStep * kRedStep;
-    nb = (c->N + chunk - 1) / chunk;
-    *chunk_out = chunk;
-    return nb;
+    return round_chunks(c->N, nb, chunk_out);
 }
 
 // k_icp_coop's partial-row arenas, every row EMPTY (k_icp_coop comment).  A
@@ -2066,26 +1813,19 @@ static int ensure_coop_part(youth_icp_ctx* c, hipStream_t s, int rows)
 
 int ensure_partials(youth_icp_ctx* c, size_t doubles)
 {
-    if (doubles <= c->partials_cap) return YOUTH_OK;
-    if (c->d_partials) HIP_TRY(hipFree(c->d_partials));
-    c->d_partials = nullptr;
-    c->partials_cap = 0;
-    HIP_TRY(hipMalloc(&c->d_partials, doubles * sizeof(double)));
-    c->partials_cap = doubles;
-    return YOUTH_OK;
+    return grow_device_buffer(&c->d_partials, &c->partials_cap, doubles);
 }
 
 int ensure_stats(youth_icp_ctx* c, int iters)
 {
-    if (iters <= c->stats_iters) return YOUTH_OK;
-    if (c->d_stats) HIP_TRY(hipFree(c->d_stats));
-    if (c->d_arr_it) HIP_TRY(hipFree(c->d_arr_it));
-    c->d_stats = nullptr;
-    c->d_arr_it = nullptr;
-    HIP_TRY(hipMalloc(&c->d_stats, (size_t)c->max_frames * iters * 2 * sizeof(double)));
-    HIP_TRY(hipMalloc(&c->d_arr_it, (size_t)c->max_frames * iters * sizeof(unsigned)));
-    c->stats_iters = iters;
-    return YOUTH_OK;
+    // two buffers of one capacity, stats_iters: the tickets grow on a copy of
+    // it, and it is zero unless both hold that many iterations
+    int arr_iters = c->stats_iters;
+    const int rc = grow_device_buffer(&c->d_arr_it, &arr_iters, iters, (size_t)c->max_frames);
+    if (rc == YOUTH_OK)
+        return grow_device_buffer(&c->d_stats, &c->stats_iters, iters, (size_t)c->max_frames * 2);
+    c->stats_iters = 0;
+    return rc;
 }
 
 static int ensure_assoc(youth_icp_ctx* c)
@@ -2490,6 +2230,20 @@ int launch_init(youth_icp_ctx* c, hipStream_t s, const double* dTi, int n_pairs,
     return YOUTH_OK;
 }
 
+int upload_T_init(youth_icp_ctx* c, hipStream_t s, const double* T_init_host, int n_pairs,
+                  const double** dTi)
+{
+    *dTi = nullptr;
+    if (!T_init_host) return YOUTH_OK;
+    for (size_t i = 0; i < (size_t)n_pairs * 16; ++i)
+        if (!std::isfinite(T_init_host[i]))
+            return set_error(YOUTH_EINVAL, "T_init: non-finite entry in pair %d", (int)(i / 16));
+    HIP_TRY(hipMemcpyAsync(c->d_Tinit, T_init_host, (size_t)n_pairs * 16 * sizeof(double),
+                           hipMemcpyHostToDevice, s));
+    *dTi = c->d_Tinit;
+    return YOUTH_OK;
+}
+
 int run_iterations(youth_icp_ctx* c, hipStream_t s, const int16_t* dsrc, int src0, int tgt0,
                    int n_pairs, const double* T_init_host, float* d_T_out, bool* exported,
                    const PrepJob* job)
@@ -2521,17 +2275,8 @@ int run_iterations(youth_icp_ctx* c, hipStream_t s, const int16_t* dsrc, int src
     int rc = ensure_stats(c, iters > 0 ? iters : 1);
     if (rc) return rc;
     const double* dTi = nullptr;
-    if (T_init_host) {
-        // finite initial poses keep every projected coordinate finite, which
-        // the kernels' integer in-range test relies on (xform_project)
-        for (size_t i = 0; i < (size_t)n_pairs * 16; ++i)
-            if (!std::isfinite(T_init_host[i]))
-                return set_error(YOUTH_EINVAL, "T_init: non-finite entry in pair %d",
-                                 (int)(i / 16));
-        HIP_TRY(hipMemcpyAsync(c->d_Tinit, T_init_host, (size_t)n_pairs * 16 * sizeof(double),
-                               hipMemcpyHostToDevice, s));
-        dTi = c->d_Tinit;
-    }
+    rc = upload_T_init(c, s, T_init_host, n_pairs, &dTi);
+    if (rc) return rc;
     if (coop) {
         rc = launch_coop(c, s, dsrc, pm, n_pairs, dTi, d_T_out, npx, G, job);
         if (rc == YOUTH_OK) {

@@ -1,9 +1,14 @@
 // rgbd_align.hip — RGB-D alignment on gfx950 (C-ABI: include/youth_rgbd.h;
 // definition: DESIGN.md §13): k_rgbd_prep, k_rgbd_reduce and their host side.
-// A unit of its own on icp_device.h's device code (back-projection, lane
-// masks, the wave reduce-scatter's stages, the a10 solve) and on the ICP
-// context and launch layer of icp_host.h; the depth-only kernels it needs
-// (k_prep, k_init, k_finish) run through that layer.
+// A unit of its own on the ICP context and launch layer of icp_host.h (the
+// depth-only kernels it needs, k_prep, k_init and k_finish, run through that
+// layer) and on icp_device.h's device code.  k_rgbd_reduce shares with
+// k_reduce, as one text: the back-projection of a lane's four pixels
+// (backproject4), a7 (survey_project), a7's gate with a8 and the exact a9
+// (match_accumulate<kSpecSurvey>), the wave reduce-scatter, the hand-off to
+// the pair's last workgroup with its fixed-order sum (handoff_publish,
+// handoff_sum) and the a10 solve.  Its own: the intensity word, §13's
+// photometric term and its two extra sums, the stats layout and neq_out.
 //
 //   k_rgbd_prep    once per target frame: RGB -> Y (or a grey copy) and one
 //                  32-bit word per pixel {Y, gx + 255, gy + 255, valid}.  Four
@@ -11,11 +16,12 @@
 //                  and below and the two columns beside the four are read from
 //                  global memory again and come from cache.  The geometric
 //                  records {z, nx, ny, nz} come from k_prep, unchanged.
-//   k_rgbd_reduce  one launch per iteration, modelled on k_reduce with its
-//                  fused solve: a workgroup takes a chunk of a pair's source
-//                  pixels, four per lane and step, branch-free under lane
-//                  masks; the 16-byte record and the 4-byte photometric word of
-//                  a lane's four pixels are gathered back to back; exact fp64
+//   k_rgbd_reduce  one launch per iteration, k_reduce's fused-solve form
+//                  with the photometric term beside it: a workgroup takes a
+//                  chunk of a pair's source pixels, four per lane and step,
+//                  branch-free under lane masks; the 16-byte record and the
+//                  4-byte photometric word of a lane's four pixels are
+//                  gathered back to back; exact fp64
 //                  products into 29 per-lane sums and two wave counts; wave
 //                  reduce-scatter, one partial row [pair][chunk][31] and an
 //                  arrival ticket; the pair's last workgroup adds the rows in a
@@ -142,47 +148,9 @@ __global__ __launch_bounds__(kRgbdPrepThreads) void k_rgbd_prep(const uint8_t* _
     }
 }
 
-// Spec a7 in the survey arithmetic, as xform_project<kSpecSurvey>, handing out
-// the sub-pixel coordinates uf = (fx P'x) / P'z + cx and vf as well.
-__device__ __forceinline__ void rgbd_project(const float* T, float sx, float sy, float sz,
-                                             const Intr& K, int W, int H, float& qx, float& qy,
-                                             float& qz, float& uf, float& vf, float& fu, float& fv,
-                                             LaneMask& inm, int& j)
-{
-    qx = ((T[0] * sx + T[1] * sy) + T[2] * sz) + T[3];
-    qy = ((T[4] * sx + T[5] * sy) + T[6] * sz) + T[7];
-    qz = ((T[8] * sx + T[9] * sy) + T[10] * sz) + T[11];
-    const float nu = K.fx * qx, nv = K.fy * qy;
-    const LaneMask sok = mask_gt(sz, 0.0f);
-    const LaneMask dok = mask_ule(__float_as_uint(qz) - 0x21800000u, 0x5d800000u - 0x21800000u);
-    const float r = proj_recip(qz);
-    float pu = proj_quot(nu, qz, r);
-    float pv = proj_quot(nv, qz, r);
-    LaneMask vz = sok & dok;
-    const LaneMask slow = sok & ~dok;
-    if (__builtin_expect(slow != 0, 0)) {  // wave-uniform
-        const LaneMask qpos = mask_gt(qz, 0.0f);
-        if (lane_in(slow)) {
-            const float den = lane_in(qpos) ? qz : 1.0f;
-            pu = nu / den;
-            pv = nv / den;
-        }
-        vz |= slow & qpos;
-    }
-    uf = pu + K.cx;
-    vf = pv + K.cy;
-    const int iu = floor_i32(uf + 0.5f);
-    const int iv = floor_i32(vf + 0.5f);
-    const unsigned ivc = min((unsigned)iv, (unsigned)H);
-    inm = vz & mask_ult((unsigned)iu, (unsigned)W);
-    fu = (float)iu;
-    fv = (float)iv;
-    j = (int)(__umul24(ivc, (unsigned)W) + (unsigned)iu);
-}
-
-// a7's gate and a8 as match_accumulate<kSpecSurvey, kFast, true>, then §13's
-// photometric term where the gate accepted the pixel and the target's word is
-// valid.  acc: [0..26] A and b of both terms, [27] sum r^2, [29] sum rp^2.
+// a7's gate, a8 and the exact a9 by icp_device.h's match_accumulate, then
+// §13's photometric term where the gate accepted the pixel and the target's
+// word is valid.  acc: [0..26] A and b of both terms, [27] sum r^2, [29] sum rp^2.
 template <bool kFast>
 __device__ __forceinline__ void rgbd_accumulate(float qx, float qy, float qz, f4v t, unsigned pw,
                                                 float ys, float uf, float vf, float fu, float fv,
@@ -190,29 +158,9 @@ __device__ __forceinline__ void rgbd_accumulate(float qx, float qy, float qz, f4
                                                 float thr2, const PhotoK& pk, double* acc,
                                                 int& cnt_g, int& cnt_p)
 {
-    const float tz = t.x;
-    const float tx = bp_div<kFast>((fu - K.cx) * tz, K.fx, F.hfx, F.lfx);
-    const float ty = bp_div<kFast>((fv - K.cy) * tz, K.fy, F.hfy, F.lfy);
-    const float dx = qx - tx, dy = qy - ty, dz = qz - tz;
-    const float d2 = (dx * dx + dy * dy) + dz * dz;
-    const LaneMask okm = inm & mask_gt(tz, 0.0f) & mask_lt(d2, thr2);
+    const LaneMask okm =
+        match_accumulate<kSpecSurvey, kFast, true>(qx, qy, qz, t, fu, fv, inm, K, F, thr2, acc);
     const LaneMask pvm = okm & mask_ult(~kPhotoValid, pw);
-    if (lane_in(okm)) {
-        const float n0 = t.y, n1 = t.z, n2 = t.w;
-        const float r = (n0 * dx + n1 * dy) + n2 * dz;
-        const float Jf[6] = {qy * n2 - qz * n1, qz * n0 - qx * n2, qx * n1 - qy * n0, n0, n1, n2};
-        int k = 0;
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int bb = a; bb < 6; ++bb) {
-                acc[k] = fma((double)Jf[a], (double)Jf[bb], acc[k]);
-                ++k;
-            }
-#pragma unroll
-        for (int a = 0; a < 6; ++a) acc[21 + a] = fma((double)Jf[a], (double)r, acc[21 + a]);
-        acc[27] = fma((double)r, (double)r, acc[27]);
-    }
     if (lane_in(pvm)) {
         const float yt = (float)(pw & 255u);
         const float gx = (float)((int)((pw >> 8) & 511u) - 255);
@@ -242,42 +190,11 @@ __device__ __forceinline__ void rgbd_accumulate(float qx, float qy, float qz, f4
     cnt_p += __builtin_popcountll(pvm);
 }
 
-// wave_reduce_scatter for the 31 values of the joint record: the same stages,
-// partners and add order; lanes 2q and 2q + 1 end with the wave total of value q.
-__device__ __forceinline__ void rgbd_wave_reduce_scatter(const double* acc, int lane, double& total)
-{
-    double v[32];
-#pragma unroll
-    for (int q = 0; q < 32; ++q) v[q] = q < kRgbdNeq ? acc[q] : 0.0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {  // m = 32
-        const auto l = __builtin_amdgcn_permlane32_swap(lo32(v[q]), lo32(v[q + 16]), false, false);
-        const auto h = __builtin_amdgcn_permlane32_swap(hi32(v[q]), hi32(v[q + 16]), false, false);
-        v[q] = join64(l[0], h[0]) + join64(l[1], h[1]);
-    }
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {  // m = 16
-        const auto l = __builtin_amdgcn_permlane16_swap(lo32(v[q]), lo32(v[q + 8]), false, false);
-        const auto h = __builtin_amdgcn_permlane16_swap(hi32(v[q]), hi32(v[q + 8]), false, false);
-        v[q] = join64(l[0], h[0]) + join64(l[1], h[1]);
-    }
-    rs_stage_small<8>(v, lane);
-    rs_stage_small<4>(v, lane);
-    rs_stage_small<2>(v, lane);
-    total = v[0] + xchg_small<1>(v[0]);
-}
-
-// Per-iteration pose state, as k_reduce's PoseState.  neq_out (stage-level
-// entry point): the pair's last workgroup stores the 31 sums there instead of
-// solving.
-struct RgbdState {
-    double* T64;         // [pair][16]
-    float* T32;          // [pair][12]
-    int32_t* status;     // [pair]
-    double* stats;       // [pair][iters][4] or null
-    unsigned* arrivals;  // [pair], zero at launch; re-armed by the last arriver
-    double* neq_out;     // [pair][31] or null
-    int it, iters;
+// k_reduce's per-iteration pose state (stats: [pair][iters][4] here) and
+// neq_out (stage-level entry point): the pair's last workgroup stores the 31
+// sums there instead of solving.
+struct RgbdState : PoseState {
+    double* neq_out;  // [pair][31] or null
 };
 
 // grid (chunks, pairs).  kAligned: W % 4 == 0, the depth base 8-byte and the
@@ -335,22 +252,12 @@ __global__ __launch_bounds__(kRedThreads) void k_rgbd_reduce(
         float qx[4], qy[4], qz[4], uf[4], vf[4], fu[4], fv[4];
         LaneMask in[4];
         int j[4];
-        const float uc0 = (float)u0 - K.cx, vc0 = (float)v0 - K.cy;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            float sx, sy, sz;
-            if (kAligned) {
-                backproject_c<kFast>(dd[q], uc0 + (float)q, vc0, K, F, sx, sy, sz);
-            } else {
-                int u = u0 + q, v = v0;
-                const bool wrap = u >= W;
-                u = wrap ? u - W : u;
-                v = wrap ? v + 1 : v;
-                backproject<kFast>((i + q) < end ? dd[q] : 0, u, v, K, F, sx, sy, sz);
-            }
-            rgbd_project(T, sx, sy, sz, K, W, H, qx[q], qy[q], qz[q], uf[q], vf[q], fu[q], fv[q],
-                         in[q], j[q]);
-        }
+        backproject4<kFast, kAligned>(
+            dd, i, end, u0, v0, W, K, F,
+            [&](int q, float sx, float sy, float sz) __attribute__((always_inline)) {
+                survey_project(T, sx, sy, sz, K, W, H, qx[q], qy[q], qz[q], uf[q], vf[q], fu[q],
+                               fv[q], in[q], j[q]);
+            });
         u0 += stepU;
         v0 += stepV;
         if (u0 >= W) {
@@ -383,7 +290,7 @@ __global__ __launch_bounds__(kRedThreads) void k_rgbd_reduce(
     const int wave = threadIdx.x >> 6;
     {
         double tot;
-        rgbd_wave_reduce_scatter(acc, ln, tot);
+        wave_reduce_scatter<kRgbdNeq>(acc, ln, tot);
         if (!(ln & 1) && (ln >> 1) < kRgbdNeq) red[wave][ln >> 1] = tot;
     }
     __syncthreads();
@@ -396,47 +303,10 @@ __global__ __launch_bounds__(kRedThreads) void k_rgbd_reduce(
 #pragma unroll
         for (int w = 0; w < kRedThreads / 64; ++w) s += red[w][lane];
     }
-    // the hand-off of k_reduce's fused solve: write-through partial stores,
-    // drained by the storing wave, then one agent-scope atomic per workgroup;
-    // the workgroup whose add returns nblk - 1 reads every partial of pair p
-    // with sc1 loads only
-    if (lane < kRgbdNeq)
-        __hip_atomic_store(reinterpret_cast<unsigned long long*>(mine) + lane,
-                           (unsigned long long)__double_as_longlong(s), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    unsigned ticket = 0;
-    if (lane == 0)
-        ticket = __hip_atomic_fetch_add(ps.arrivals + p, 1u, __ATOMIC_RELAXED,
-                                        __HIP_MEMORY_SCOPE_AGENT);
-    ticket = __shfl(ticket, 0, 64);
-    if (ticket != (unsigned)nblk - 1) return;
-    // fixed order: lanes 0..30 add the first half of the rows, lanes 32..62
-    // the second half, loads in batches of 8; then one add
-    const unsigned long long* base =
-        reinterpret_cast<const unsigned long long*>(partials + (size_t)p * nblk * kRgbdStride);
-    const int half = (nblk + 1) >> 1;
-    const int k = lane & 31;
-    double tsum = 0.0;
-    if (k < kRgbdNeq) {
-        const int b0 = lane < 32 ? 0 : half;
-        const int b1 = lane < 32 ? half : nblk;
-        for (int bb = b0; bb < b1; bb += 8) {
-            double v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-                v[q] = bb + q < b1 ? __longlong_as_double((long long)__hip_atomic_load(
-                                         base + (size_t)(bb + q) * kRgbdStride + k, __ATOMIC_RELAXED,
-                                         __HIP_MEMORY_SCOPE_AGENT))
-                                   : 0.0;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) tsum += v[q];
-        }
-    }
-    tsum += __shfl_down(tsum, 32, 64);
+    // k_reduce's hand-off (icp_device.h): only the pair's last arriver goes on
+    if (!handoff_publish<kRgbdNeq>(mine, ps, p, nblk, lane, s)) return;
     double neq[kRgbdNeq];
-#pragma unroll
-    for (int q = 0; q < kRgbdNeq; ++q) neq[q] = __shfl(tsum, q, 64);
+    handoff_sum<kRgbdNeq, kRgbdStride>(partials, p, nblk, lane, neq);
     if (lane == 0) {
         ps.arrivals[p] = 0;  // re-armed for the next launch (stream order)
         if (ps.stats) {
@@ -509,23 +379,12 @@ static int rgbd_geometry(const youth_rgbd_ctx* r, int n_pairs, int* chunk_out)
 {
     if (!r->chunks) return reduce_geometry(r->icp, n_pairs, chunk_out);
     const int N = r->icp->N;
-    int nb = std::min(r->chunks, (N + kRedStep - 1) / kRedStep);
-    int chunk = (N + nb - 1) / nb;
-    chunk = (chunk + kRedStep - 1) / kRedStep * kRedStep;
-    nb = (N + chunk - 1) / chunk;
-    *chunk_out = chunk;
-    return nb;
+    return round_chunks(N, std::min(r->chunks, (N + kRedStep - 1) / kRedStep), chunk_out);
 }
 
 static int rgbd_ensure_stats(youth_rgbd_ctx* r, int iters)
 {
-    if (iters <= r->stats_iters) return YOUTH_OK;
-    if (r->d_stats) HIP_TRY(hipFree(r->d_stats));
-    r->d_stats = nullptr;
-    r->stats_iters = 0;
-    HIP_TRY(hipMalloc(&r->d_stats, (size_t)r->frames * iters * 4 * sizeof(double)));
-    r->stats_iters = iters;
-    return YOUTH_OK;
+    return grow_device_buffer(&r->d_stats, &r->stats_iters, iters, (size_t)r->frames * 4);
 }
 
 // One k_rgbd_reduce launch over n_pairs pairs: iteration `it` with its fused
@@ -537,20 +396,15 @@ static int rgbd_launch_reduce(youth_rgbd_ctx* r, hipStream_t s, const int16_t* d
     youth_icp_ctx* c = r->icp;
     int chunk = 0;
     const int nb = rgbd_geometry(r, n_pairs, &chunk);
-    const size_t need = (size_t)nb * n_pairs * kRgbdStride;
-    if (need > r->part_cap) {
-        if (r->d_part) HIP_TRY(hipFree(r->d_part));
-        r->d_part = nullptr;
-        r->part_cap = 0;
-        HIP_TRY(hipMalloc(&r->d_part, need * sizeof(double)));
-        r->part_cap = need;
-    }
+    int rc = grow_device_buffer(&r->d_part, &r->part_cap, (size_t)nb * n_pairs * kRgbdStride);
+    if (rc) return rc;
     const float thr2 = r->prm.dist_thresh * r->prm.dist_thresh;
     const bool aligned = (reinterpret_cast<uintptr_t>(dsrc) % 8 == 0) &&
                          (reinterpret_cast<uintptr_t>(gsrc) % 4 == 0) && (c->W % 4 == 0) &&
                          c->centred_exact;
-    const RgbdState ps{c->d_T64, c->d_T32, c->d_status, neq_out ? nullptr : r->d_stats,
-                       c->d_arrivals, neq_out, it, r->prm.iters};
+    const RgbdState ps{{c->d_T64, c->d_T32, c->d_status, neq_out ? nullptr : r->d_stats,
+                        c->d_arrivals, it, r->prm.iters},
+                       neq_out};
     auto kern = c->fast ? (aligned ? k_rgbd_reduce<true, true> : k_rgbd_reduce<true, false>)
                         : (aligned ? k_rgbd_reduce<false, true> : k_rgbd_reduce<false, false>);
     hipLaunchKernelGGL(kern, dim3(nb, n_pairs), dim3(kRedThreads), 0, s, dsrc, gsrc, c->d_rec, c->P,
@@ -567,16 +421,10 @@ static int rgbd_align(youth_rgbd_ctx* r, hipStream_t s, const int16_t* dsrc, con
 {
     youth_icp_ctx* c = r->icp;
     const double* dTi = nullptr;
-    if (T_init_host) {
-        for (size_t i = 0; i < (size_t)n_pairs * 16; ++i)
-            if (!std::isfinite(T_init_host[i]))
-                return set_error(YOUTH_EINVAL, "T_init: non-finite entry in pair %d", (int)(i / 16));
-        HIP_TRY(hipMemcpyAsync(c->d_Tinit, T_init_host, (size_t)n_pairs * 16 * sizeof(double),
-                               hipMemcpyHostToDevice, s));
-        dTi = c->d_Tinit;
-    }
+    int rc = upload_T_init(c, s, T_init_host, n_pairs, &dTi);
+    if (rc) return rc;
     const int iters = r->prm.iters;
-    int rc = rgbd_ensure_stats(r, iters > 0 ? iters : 1);
+    rc = rgbd_ensure_stats(r, iters > 0 ? iters : 1);
     if (rc) return rc;
     rc = launch_prep(c, s, dtgt, n_tgt, 0, false);
     if (rc) return rc;

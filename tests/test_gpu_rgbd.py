@@ -130,6 +130,36 @@ def test_lambda_zero_is_the_depth_only_align(pairs160):
     assert np.array_equal(stats[:, :, 3], cnt_icp) and not stats[:, :, 2].any()
 
 
+@pytest.mark.parametrize("W,H,fastdiv", [(97, 53, True), (160, 120, True), (160, 120, False)],
+                         ids=["97x53_unaligned", "160x120_aligned", "160x120_ieee_division"])
+def test_lambda_zero_equals_the_per_iteration_align_bit_for_bit(W, H, fastdiv, monkeypatch):
+    """k_rgbd_reduce and k_reduce's fused solve run one text of a7-a9, of the
+    wave sum and of the hand-off (csrc/icp_device.h), on the same chunks: at
+    lambda 0 (photometric products of +-0 onto sums that are never -0) the
+    RGB-D align is the depth-only per-iteration align, bit for bit."""
+    src, dst, _, srgb, drgb = youth_synth.pairs_rgb(0, 2, W, H)
+    sg, dg = rgbd_truth.luma(srgb), rgbd_truth.luma(drgb)
+    monkeypatch.setenv("YOUTH_ICP_NO_COOP", "1")
+    monkeypatch.setenv("YOUTH_ICP_NO_PERSISTENT", "1")
+    if not fastdiv:
+        monkeypatch.setenv("YOUTH_ICP_NO_FASTDIV", "1")
+    with youth_icp.IcpContext(W, H, 2) as icp:
+        ds, dd = _dev(src), _dev(dst)
+        icp.align_pairs_device(ds.data_ptr(), dd.data_ptr(), 2)
+        T_icp, _, st_icp = icp.get_poses(2)
+        cnt_icp, r2_icp = icp.get_stats(2, 10)
+        assert "per-iteration" in icp.get_plan()["kernel"]
+        assert fastdiv or not icp.fastdiv
+    with youth_rgbd.RgbdContext(W, H, 2, lam=0.0) as ctx:
+        T, st, stats = _align_pairs(ctx, src, sg, dst, dg)
+    assert cnt_icp.min() > 0
+    assert np.array_equal(np.ascontiguousarray(T[:, :3]).view(np.uint64),
+                          np.ascontiguousarray(T_icp[:, :3]).view(np.uint64))
+    assert np.array_equal(st, st_icp)
+    assert np.array_equal(stats[:, :, 1].copy().view(np.uint64), cnt_icp.view(np.uint64))
+    assert np.array_equal(stats[:, :, 0].copy().view(np.uint64), r2_icp.view(np.uint64))
+
+
 def test_pose_against_truth(pairs160):
     src, sg, dst, dg, truth = pairs160
     with youth_rgbd.RgbdContext(160, 120, 4) as ctx:
