@@ -24,11 +24,9 @@
 // estimate is within 1 of it) and an integer correction.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 
+#include "hip_host.h"
 #include "youth_filter.h"
 
 namespace {
@@ -166,61 +164,32 @@ __global__ __launch_bounds__(kFltThreads) void k_depth_filter(const int16_t* __r
 
 // =============================================================== host side ==
 
-static thread_local std::string g_filter_error;
-
-__attribute__((format(printf, 2, 3))) static int filter_error(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_filter_error = buf;
-    return code;
-}
-
-#define FLT_TRY(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            return filter_error(YOUTH_EHIP, "%s (line %d)", hipGetErrorString(e_), __LINE__); \
-    } while (0)
+// The depth filter's channel (hip_host.h): youth_depth_filter_last_error reads it.
+static thread_local youth::ErrorText g_filter_err;
+#define HIP_ERR g_filter_err
 
 static int filter_check(const char* who, const void* in, const void* out, int n_frames, int W,
                         int H, const youth_filter_params* P, bool may_alias)
 {
-    if (!in || !out) return filter_error(YOUTH_EINVAL, "%s: null buffer", who);
-    if (n_frames < 0 || n_frames > 65535 || W < 3 || H < 3 || W > 16384 || H > 16384 ||
-        (long long)W * H > (1LL << 26))
-        return filter_error(YOUTH_EINVAL,
-                            "%s: %d frames of %dx%d (need 0 <= frames <= 65535, 3 <= W, H <= 16384, "
-                            "W*H <= 2^26)",
-                            who, n_frames, W, H);
+    if (!in || !out) return g_filter_err.set(YOUTH_EINVAL, "%s: null buffer", who);
+    if (n_frames < 0 || n_frames > youth::kMaxFrames || !youth::frame_size_ok(W, H, 3))
+        return g_filter_err.set(YOUTH_EINVAL,
+                                "%s: %d frames of %dx%d (need 0 <= frames <= 65535, 3 <= W, H <= 16384, "
+                                "W*H <= 2^26)",
+                                who, n_frames, W, H);
     if (P && (P->t0 < 1 || P->t0 > 255 || P->t2 < 0 || P->t2 > 1000))
-        return filter_error(YOUTH_EINVAL, "%s: t0 %d, t2 %d (need 1 <= t0 <= 255, 0 <= t2 <= 1000)",
-                            who, P->t0, P->t2);
+        return g_filter_err.set(YOUTH_EINVAL, "%s: t0 %d, t2 %d (need 1 <= t0 <= 255, 0 <= t2 <= 1000)",
+                                who, P->t0, P->t2);
     const size_t bytes = (size_t)n_frames * W * H * sizeof(int16_t);
     const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
     if (!may_alias && a < b + bytes && b < a + bytes)
-        return filter_error(YOUTH_EINVAL, "%s: the output overlaps the input", who);
-    return YOUTH_OK;
-}
-
-static int filter_device_ok(const char* who, int device)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return filter_error(YOUTH_ENODEV, "%s: no HIP device visible", who);
-    }
-    if (device < 0 || device >= ndev)
-        return filter_error(YOUTH_EINVAL, "%s: device %d of %d", who, device, ndev);
+        return g_filter_err.set(YOUTH_EINVAL, "%s: the output overlaps the input", who);
     return YOUTH_OK;
 }
 
 extern "C" {
 
-const char* youth_depth_filter_last_error(void) { return g_filter_error.c_str(); }
+const char* youth_depth_filter_last_error(void) { return g_filter_err.c_str(); }
 
 youth_filter_params youth_depth_filter_default_params(void)
 {
@@ -236,10 +205,10 @@ int youth_depth_filter_device(int device, const int16_t* d_in, int16_t* d_out, i
     static const char* who = "youth_depth_filter_device";
     int rc = filter_check(who, d_in, d_out, n_frames, W, H, P, false);
     if (rc) return rc;
-    rc = filter_device_ok(who, device);
+    rc = youth::check_device(g_filter_err, who, device);
     if (rc) return rc;
     if (n_frames == 0) return YOUTH_OK;
-    FLT_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     const youth_filter_params p = P ? *P : youth_depth_filter_default_params();
     const int tiles_x = (W + kFltTW - 1) / kFltTW, tiles_y = (H + kFltTH - 1) / kFltTH;
     // W % 4 == 0 keeps every frame of the batch as aligned as the first
@@ -247,7 +216,7 @@ int youth_depth_filter_device(int device, const int16_t* d_in, int16_t* d_out, i
     hipLaunchKernelGGL(vec ? k_depth_filter<true> : k_depth_filter<false>,
                        dim3(tiles_x * tiles_y, n_frames), dim3(kFltThreads), 0, (hipStream_t)stream,
                        d_in, d_out, W, H, tiles_x, (unsigned)p.t0, (unsigned)p.t2);
-    FLT_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return YOUTH_OK;
 }
 
@@ -259,13 +228,13 @@ int youth_depth_filter_host(int device, const int16_t* in, int16_t* out, int n_f
     // device buffers
     int rc = filter_check(who, in, out, n_frames, W, H, P, true);
     if (rc) return rc;
-    rc = filter_device_ok(who, device);
+    rc = youth::check_device(g_filter_err, who, device);
     if (rc) return rc;
     if (n_frames == 0) return YOUTH_OK;
-    FLT_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     const size_t bytes = (size_t)n_frames * W * H * sizeof(int16_t);
     int16_t* d = nullptr;
-    FLT_TRY(hipMalloc(&d, 2 * bytes));
+    HIP_TRY(hipMalloc(&d, 2 * bytes));
     int16_t* d_out = d + bytes / sizeof(int16_t);
     hipStream_t s = nullptr;
     hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
@@ -281,7 +250,7 @@ int youth_depth_filter_host(int device, const int16_t* in, int16_t* out, int n_f
     }
     (void)hipFree(d);
     if (rc) return rc;
-    if (e != hipSuccess) return filter_error(YOUTH_EHIP, "%s: %s", who, hipGetErrorString(e));
+    if (e != hipSuccess) return g_filter_err.set(YOUTH_EHIP, "%s: %s", who, hipGetErrorString(e));
     return YOUTH_OK;
 }
 

@@ -7,12 +7,9 @@
 // every rank's rows at its shard's offset.  Both on the caller's stream.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
 
-#include <string>
-
+#include "hip_host.h"
 #include "youth_dist.h"
 #include "youth_icp.h"
 
@@ -33,7 +30,9 @@ struct youth_dist {
     hipEvent_t order = nullptr;
 };
 
-static thread_local std::string g_err;
+// This library's own channel (hip_host.h is header-only: nothing of
+// libyouth_icp.so's is shared): youth_dist_last_error reads it.
+static thread_local youth::ErrorText g_dist_err;
 
 // Row r of a batch of n pairs split over k ranks (youth_icp_shard_range: the
 // first n % k shards hold one row more) is row i of rank q's shard.
@@ -61,28 +60,17 @@ __global__ void k_compact(const float4* __restrict__ scratch, int max_count, int
     out[t] = scratch[((size_t)q * max_count + i) * 4 + (t & 3)];
 }
 
-__attribute__((format(printf, 2, 3))) static int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
 extern "C" {
 
-const char* youth_dist_last_error(void) { return g_err.c_str(); }
+const char* youth_dist_last_error(void) { return g_dist_err.c_str(); }
 
 int youth_dist_unique_id(unsigned char id[YOUTH_DIST_ID_BYTES])
 {
     static_assert(YOUTH_DIST_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "id size");
-    if (!id) return fail(YOUTH_EINVAL, "unique_id: null");
+    if (!id) return g_dist_err.set(YOUTH_EINVAL, "unique_id: null");
     ncclUniqueId u;
     const ncclResult_t r = ncclGetUniqueId(&u);
-    if (r != ncclSuccess) return fail(YOUTH_EHIP, "ncclGetUniqueId: %s", ncclGetErrorString(r));
+    if (r != ncclSuccess) return g_dist_err.set(YOUTH_EHIP, "ncclGetUniqueId: %s", ncclGetErrorString(r));
     memcpy(id, u.internal, NCCL_UNIQUE_ID_BYTES);
     return YOUTH_OK;
 }
@@ -91,16 +79,16 @@ youth_dist* youth_dist_create(int nranks, int rank, int device,
                               const unsigned char id[YOUTH_DIST_ID_BYTES])
 {
     if (nranks < 1 || rank < 0 || rank >= nranks || !id) {
-        fail(YOUTH_EINVAL, "dist_create: bad arguments (nranks %d, rank %d)", nranks, rank);
+        g_dist_err.set(YOUTH_EINVAL, "dist_create: bad arguments (nranks %d, rank %d)", nranks, rank);
         return nullptr;
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        fail(YOUTH_ENODEV, "dist_create: no HIP device %d", device);
+        g_dist_err.set(YOUTH_ENODEV, "dist_create: no HIP device %d", device);
         return nullptr;
     }
     if (hipSetDevice(device) != hipSuccess) {
-        fail(YOUTH_EHIP, "dist_create: hipSetDevice(%d)", device);
+        g_dist_err.set(YOUTH_EHIP, "dist_create: hipSetDevice(%d)", device);
         return nullptr;
     }
     ncclUniqueId u;
@@ -111,7 +99,7 @@ youth_dist* youth_dist_create(int nranks, int rank, int device,
     d->device = device;
     const ncclResult_t r = ncclCommInitRank(&d->comm, nranks, u, rank);
     if (r != ncclSuccess) {
-        fail(YOUTH_EHIP, "ncclCommInitRank: %s", ncclGetErrorString(r));
+        g_dist_err.set(YOUTH_EHIP, "ncclCommInitRank: %s", ncclGetErrorString(r));
         delete d;
         return nullptr;
     }
@@ -121,31 +109,31 @@ youth_dist* youth_dist_create(int nranks, int rank, int device,
 int youth_dist_allgather_poses(youth_dist* d, const float* d_local, int n_pairs, float* d_all,
                                void* stream)
 {
-    if (!d || !d_all || n_pairs < 0) return fail(YOUTH_EINVAL, "allgather_poses: bad arguments");
+    if (!d || !d_all || n_pairs < 0) return g_dist_err.set(YOUTH_EINVAL, "allgather_poses: bad arguments");
     if (n_pairs == 0) return YOUTH_OK;
     int first = 0, count = 0;
     youth_icp_shard_range(n_pairs, d->nranks, d->rank, &first, &count);
     const int max_count = (n_pairs + d->nranks - 1) / d->nranks;  // rank 0's shard
-    if (count > 0 && !d_local) return fail(YOUTH_EINVAL, "allgather_poses: null d_local");
-    if (hipSetDevice(d->device) != hipSuccess) return fail(YOUTH_EHIP, "hipSetDevice");
+    if (count > 0 && !d_local) return g_dist_err.set(YOUTH_EINVAL, "allgather_poses: null d_local");
+    if (hipSetDevice(d->device) != hipSuccess) return g_dist_err.set(YOUTH_EHIP, "hipSetDevice");
     const hipStream_t s = (hipStream_t)stream;
     if (!d->order && hipEventCreateWithFlags(&d->order, hipEventDisableTiming) != hipSuccess)
-        return fail(YOUTH_EHIP, "hipEventCreate");
+        return g_dist_err.set(YOUTH_EHIP, "hipEventCreate");
     // stream switch: wait for the previous gather through the event recorded
     // on ITS stream right after it (below); the previous stream's handle is
     // never used again (the caller may have destroyed it)
     if (d->any && d->last != s && hipStreamWaitEvent(s, d->order, 0) != hipSuccess)
-        return fail(YOUTH_EHIP, "hipStreamWaitEvent");
+        return g_dist_err.set(YOUTH_EHIP, "hipStreamWaitEvent");
     d->last = s;
     const size_t rows = (size_t)d->nranks * max_count;
     if (rows > d->scratch_rows) {
         // a previous gather may still read the old scratch on some stream
         if (d->scratch && (hipDeviceSynchronize() != hipSuccess || hipFree(d->scratch) != hipSuccess))
-            return fail(YOUTH_EHIP, "hipFree scratch");
+            return g_dist_err.set(YOUTH_EHIP, "hipFree scratch");
         d->scratch = nullptr;
         d->scratch_rows = 0;
         if (hipMalloc(&d->scratch, rows * 16 * sizeof(float)) != hipSuccess)
-            return fail(YOUTH_EHIP, "hipMalloc scratch (%zu rows)", rows);
+            return g_dist_err.set(YOUTH_EHIP, "hipMalloc scratch (%zu rows)", rows);
         d->scratch_rows = rows;
     }
     // this rank's rows (padded to max_count) into its slot: the all-gather
@@ -154,14 +142,14 @@ int youth_dist_allgather_poses(youth_dist* d, const float* d_local, int n_pairs,
     if (count > 0 &&
         hipMemcpyAsync(mine, d_local, (size_t)count * 16 * sizeof(float), hipMemcpyDeviceToDevice,
                        s) != hipSuccess)
-        return fail(YOUTH_EHIP, "hipMemcpyAsync local rows");
+        return g_dist_err.set(YOUTH_EHIP, "hipMemcpyAsync local rows");
     const ncclResult_t r = ncclAllGather(mine, d->scratch, (size_t)max_count * 16, ncclFloat32,
                                          d->comm, s);
-    if (r != ncclSuccess) return fail(YOUTH_EHIP, "ncclAllGather: %s", ncclGetErrorString(r));
+    if (r != ncclSuccess) return g_dist_err.set(YOUTH_EHIP, "ncclAllGather: %s", ncclGetErrorString(r));
     hipLaunchKernelGGL(k_compact, dim3((n_pairs * 4 + 255) / 256), dim3(256), 0, s,
                        (const float4*)d->scratch, max_count, n_pairs, d->nranks, (float4*)d_all);
-    if (hipGetLastError() != hipSuccess) return fail(YOUTH_EHIP, "k_compact launch");
-    if (hipEventRecord(d->order, s) != hipSuccess) return fail(YOUTH_EHIP, "hipEventRecord");
+    if (hipGetLastError() != hipSuccess) return g_dist_err.set(YOUTH_EHIP, "k_compact launch");
+    if (hipEventRecord(d->order, s) != hipSuccess) return g_dist_err.set(YOUTH_EHIP, "hipEventRecord");
     d->any = true;
     return YOUTH_OK;
 }
@@ -169,30 +157,30 @@ int youth_dist_allgather_poses(youth_dist* d, const float* d_local, int n_pairs,
 int youth_dist_allgather_poses_host(youth_dist* d, const float* h_local, int n_pairs,
                                     float* h_all)
 {
-    if (!d || !h_all || n_pairs < 0) return fail(YOUTH_EINVAL, "allgather_poses_host: bad arguments");
+    if (!d || !h_all || n_pairs < 0) return g_dist_err.set(YOUTH_EINVAL, "allgather_poses_host: bad arguments");
     if (n_pairs == 0) return YOUTH_OK;
     int first = 0, count = 0;
     youth_icp_shard_range(n_pairs, d->nranks, d->rank, &first, &count);
-    if (count > 0 && !h_local) return fail(YOUTH_EINVAL, "allgather_poses_host: null h_local");
-    if (hipSetDevice(d->device) != hipSuccess) return fail(YOUTH_EHIP, "hipSetDevice");
+    if (count > 0 && !h_local) return g_dist_err.set(YOUTH_EINVAL, "allgather_poses_host: null h_local");
+    if (hipSetDevice(d->device) != hipSuccess) return g_dist_err.set(YOUTH_EHIP, "hipSetDevice");
     if (!d->stream && hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess)
-        return fail(YOUTH_EHIP, "hipStreamCreate");
+        return g_dist_err.set(YOUTH_EHIP, "hipStreamCreate");
     const size_t rows = (size_t)count + n_pairs;
     if (rows > d->staging_rows) {
         if (d->staging && (hipStreamSynchronize(d->stream) != hipSuccess ||
                            hipFree(d->staging) != hipSuccess))
-            return fail(YOUTH_EHIP, "hipFree staging");
+            return g_dist_err.set(YOUTH_EHIP, "hipFree staging");
         d->staging = nullptr;
         d->staging_rows = 0;
         if (hipMalloc(&d->staging, rows * 16 * sizeof(float)) != hipSuccess)
-            return fail(YOUTH_EHIP, "hipMalloc staging (%zu rows)", rows);
+            return g_dist_err.set(YOUTH_EHIP, "hipMalloc staging (%zu rows)", rows);
         d->staging_rows = rows;
     }
     float* d_local = d->staging;
     float* d_all = d->staging + (size_t)count * 16;
     if (count > 0 && hipMemcpyAsync(d_local, h_local, (size_t)count * 16 * sizeof(float),
                                     hipMemcpyHostToDevice, d->stream) != hipSuccess)
-        return fail(YOUTH_EHIP, "hipMemcpyAsync H2D");
+        return g_dist_err.set(YOUTH_EHIP, "hipMemcpyAsync H2D");
     const int rc = youth_dist_allgather_poses(d, d_local, n_pairs, d_all, d->stream);
     if (rc) {
         (void)hipStreamSynchronize(d->stream);
@@ -201,14 +189,14 @@ int youth_dist_allgather_poses_host(youth_dist* d, const float* h_local, int n_p
     if (hipMemcpyAsync(h_all, d_all, (size_t)n_pairs * 16 * sizeof(float), hipMemcpyDeviceToHost,
                        d->stream) != hipSuccess ||
         hipStreamSynchronize(d->stream) != hipSuccess)
-        return fail(YOUTH_EHIP, "D2H / sync");
+        return g_dist_err.set(YOUTH_EHIP, "D2H / sync");
     return YOUTH_OK;
 }
 
 int youth_dist_row_source(int n_pairs, int nranks, int row, int* rank, int* index)
 {
     if (n_pairs < 1 || nranks < 1 || row < 0 || row >= n_pairs || !rank || !index)
-        return fail(YOUTH_EINVAL, "row_source: bad arguments");
+        return g_dist_err.set(YOUTH_EINVAL, "row_source: bad arguments");
     row_source(n_pairs, nranks, row, rank, index);
     return YOUTH_OK;
 }

@@ -3,7 +3,6 @@
 // points and the stage-level host entry points.  Host code only: kernels are
 // reached through the launch layer of icp_kernels.hip (icp_host.h).
 
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -18,18 +17,7 @@ using namespace youth_icp;
 
 namespace youth_icp {
 
-thread_local std::string g_last_error;
-
-int set_error(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
+thread_local youth::ErrorText g_icp_err;
 
 hipStream_t pick_stream(youth_icp_ctx* c, void* stream)
 {
@@ -99,7 +87,7 @@ youth_icp_params youth_default_params(void)
     return p;
 }
 
-const char* youth_icp_last_error(void) { return g_last_error.c_str(); }
+const char* youth_icp_last_error(void) { return g_icp_err.c_str(); }
 
 int youth_icp_device_count(void)
 {
@@ -113,7 +101,7 @@ int youth_icp_fastdiv_enabled(youth_icp_ctx* c) { return c && c->fast ? 1 : 0; }
 int youth_icp_set_spec(youth_icp_ctx* c, int spec)
 {
     if (!c || (spec != YOUTH_SPEC_FMA && spec != YOUTH_SPEC_SURVEY))
-        return set_error(YOUTH_EINVAL, "set_spec: bad arguments (%d)", spec);
+        return g_icp_err.set(YOUTH_EINVAL, "set_spec: bad arguments (%d)", spec);
     const int old = c->spec;
     c->spec = spec;
     return old;
@@ -122,7 +110,7 @@ int youth_icp_set_spec(youth_icp_ctx* c, int spec)
 int youth_icp_set_reduce(youth_icp_ctx* c, int mode)
 {
     if (!c || (mode != YOUTH_REDUCE_EXACT && mode != YOUTH_REDUCE_LANE32))
-        return set_error(YOUTH_EINVAL, "set_reduce: bad arguments (%d)", mode);
+        return g_icp_err.set(YOUTH_EINVAL, "set_reduce: bad arguments (%d)", mode);
     const int old = c->reduce;
     c->reduce = mode;
     return old;
@@ -130,16 +118,16 @@ int youth_icp_set_reduce(youth_icp_ctx* c, int mode)
 
 int youth_icp_get_reduce(const youth_icp_ctx* c)
 {
-    return c ? c->reduce : set_error(YOUTH_EINVAL, "get_reduce: null context");
+    return c ? c->reduce : g_icp_err.set(YOUTH_EINVAL, "get_reduce: null context");
 }
 
 int youth_icp_get_lanes(const youth_icp_ctx* c, youth_lanes* out)
 {
-    if (!c || !out) return set_error(YOUTH_EINVAL, "get_lanes: bad arguments");
-    if (!c->has_lanes) return set_error(YOUTH_EINVAL, "get_lanes: no align has run");
+    if (!c || !out) return g_icp_err.set(YOUTH_EINVAL, "get_lanes: bad arguments");
+    if (!c->has_lanes) return g_icp_err.set(YOUTH_EINVAL, "get_lanes: no align has run");
     if (c->lanes_mixed)
-        return set_error(YOUTH_EINVAL, "get_lanes: the last call ran launches of more than one "
-                                       "lane partition");
+        return g_icp_err.set(YOUTH_EINVAL, "get_lanes: the last call ran launches of more than one "
+                             "lane partition");
     *out = c->lanes;
     return YOUTH_OK;
 }
@@ -147,7 +135,7 @@ int youth_icp_get_lanes(const youth_icp_ctx* c, youth_lanes* out)
 int youth_icp_set_concurrency(youth_icp_ctx* c, int contexts)
 {
     if (!c || contexts < 1 || contexts > YOUTH_ICP_MAX_CONCURRENCY)
-        return set_error(YOUTH_EINVAL, "set_concurrency: bad arguments (%d)", contexts);
+        return g_icp_err.set(YOUTH_EINVAL, "set_concurrency: bad arguments (%d)", contexts);
     const int old = c->share;
     c->share = contexts;
     return old;
@@ -155,7 +143,7 @@ int youth_icp_set_concurrency(youth_icp_ctx* c, int contexts)
 
 int youth_icp_get_spec(const youth_icp_ctx* c)
 {
-    return c ? c->spec : set_error(YOUTH_EINVAL, "get_spec: null context");
+    return c ? c->spec : g_icp_err.set(YOUTH_EINVAL, "get_spec: null context");
 }
 
 void youth_icp_destroy(youth_icp_ctx* c)
@@ -193,19 +181,16 @@ void youth_icp_destroy(youth_icp_ctx* c)
 youth_icp_ctx* youth_icp_create(int device, int W, int H, int max_frames,
                                 const youth_intrinsics* K, const youth_icp_params* P)
 {
-    // W, H <= 16384 and W*H <= 2^26: pixel indices fit the pixel loop's 24-bit
-    // multiply and a target frame's records (16 B/px) its 32-bit buffer offsets
-    if (W < 3 || H < 3 || W > 16384 || H > 16384 || max_frames < 2 ||
-        (long long)W * H > (1LL << 26)) {
-        set_error(YOUTH_EINVAL,
-                  "youth_icp_create: bad size %dx%d / max_frames %d (need 3 <= W, H <= 16384, "
-                  "W*H <= 2^26, max_frames >= 2)",
-                  W, H, max_frames);
+    if (!youth::frame_size_ok(W, H, 3) || max_frames < 2) {
+        g_icp_err.set(YOUTH_EINVAL,
+                      "youth_icp_create: bad size %dx%d / max_frames %d (need 3 <= W, H <= 16384, "
+                      "W*H <= 2^26, max_frames >= 2)",
+                      W, H, max_frames);
         return nullptr;
     }
     const int ndev = youth_icp_device_count();
     if (ndev <= 0 || device < 0 || device >= ndev) {
-        set_error(YOUTH_ENODEV, "youth_icp_create: no HIP device %d", device);
+        g_icp_err.set(YOUTH_ENODEV, "youth_icp_create: no HIP device %d", device);
         return nullptr;
     }
     auto* c = new youth_icp_ctx();
@@ -222,7 +207,7 @@ youth_icp_ctx* youth_icp_create(int device, int W, int H, int max_frames,
     c->centred_exact = centred_exact(Kd.cx, W);
     c->prm = P ? *P : youth_default_params();
     auto fail = [&](const char* what, hipError_t e) -> youth_icp_ctx* {
-        set_error(YOUTH_EHIP, "youth_icp_create: %s (%d)", what, (int)e);
+        g_icp_err.set(YOUTH_EHIP, "youth_icp_create: %s (%d)", what, (int)e);
         youth_icp_destroy(c);
         return nullptr;
     };
@@ -370,7 +355,7 @@ int youth_icp_align_pairs_device(youth_icp_ctx* c, const int16_t* d_src, const i
                                  void* stream)
 {
     if (!c || !d_src || !d_dst || n_pairs <= 0 || n_pairs > c->max_frames)
-        return set_error(YOUTH_EINVAL, "align_pairs: bad arguments %d", n_pairs);
+        return g_icp_err.set(YOUTH_EINVAL, "align_pairs: bad arguments %d", n_pairs);
     int rc = bind_device(c);
     if (rc) return rc;
     hipStream_t s = pick_stream(c, stream);
@@ -386,7 +371,7 @@ int youth_icp_align_sequence_device(youth_icp_ctx* c, const int16_t* d_frames, i
                                     float* d_T_out, void* stream)
 {
     if (!c || !d_frames || n_frames < 2 || n_frames - 1 > c->max_frames)
-        return set_error(YOUTH_EINVAL, "align_sequence: bad arguments %d", n_frames);
+        return g_icp_err.set(YOUTH_EINVAL, "align_sequence: bad arguments %d", n_frames);
     int rc = bind_device(c);
     if (rc) return rc;
     hipStream_t s = pick_stream(c, stream);
@@ -402,7 +387,7 @@ int youth_icp_align_sequence_device(youth_icp_ctx* c, const int16_t* d_frames, i
 
 int youth_icp_sync(youth_icp_ctx* c, void* stream)
 {
-    if (!c) return set_error(YOUTH_EINVAL, "sync: null context");
+    if (!c) return g_icp_err.set(YOUTH_EINVAL, "sync: null context");
     int rc = bind_device(c);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(pick_stream(c, stream)));
@@ -412,7 +397,7 @@ int youth_icp_sync(youth_icp_ctx* c, void* stream)
 int youth_icp_get_poses(youth_icp_ctx* c, int n, double* T64, float* T32, int32_t* status)
 {
     if (!c || n < 0 || n > c->max_frames)
-        return set_error(YOUTH_EINVAL, "get_poses: bad arguments %d", n);
+        return g_icp_err.set(YOUTH_EINVAL, "get_poses: bad arguments %d", n);
     int rc = bind_device(c);
     if (rc) return rc;
     hipStream_t s = c->last_stream ? c->last_stream : c->stream;
@@ -442,7 +427,7 @@ int youth_icp_get_poses(youth_icp_ctx* c, int n, double* T64, float* T32, int32_
 int youth_icp_get_stats(youth_icp_ctx* c, int n, int iters, double* count, double* sum_r2)
 {
     if (!c || n < 0 || n > c->max_frames || iters != c->last_iters || iters > c->stats_iters)
-        return set_error(YOUTH_EINVAL, "get_stats: bad arguments %d", iters);
+        return g_icp_err.set(YOUTH_EINVAL, "get_stats: bad arguments %d", iters);
     int rc = bind_device(c);
     if (rc) return rc;
     std::vector<double> st((size_t)n * iters * 2);
@@ -459,7 +444,7 @@ int youth_icp_get_stats(youth_icp_ctx* c, int n, int iters, double* count, doubl
 
 int youth_icp_set_timing(youth_icp_ctx* c, int enable)
 {
-    if (!c) return set_error(YOUTH_EINVAL, "set_timing: null context");
+    if (!c) return g_icp_err.set(YOUTH_EINVAL, "set_timing: null context");
     int rc = bind_device(c);
     if (rc) return rc;
     rc = ev_harvest(c);
@@ -476,10 +461,10 @@ int youth_icp_set_timing(youth_icp_ctx* c, int enable)
 int youth_icp_selftest_projdiv(int device, long long n, unsigned long long seed,
                                long long* bit_mismatches, long long* proj_mismatches)
 {
-    if (n < 0) return set_error(YOUTH_EINVAL, "selftest_projdiv: n < 0");
+    if (n < 0) return g_icp_err.set(YOUTH_EINVAL, "selftest_projdiv: n < 0");
     const int ndev = youth_icp_device_count();
     if (ndev <= 0 || device < 0 || device >= ndev)
-        return set_error(YOUTH_ENODEV, "selftest_projdiv: no HIP device %d", device);
+        return g_icp_err.set(YOUTH_ENODEV, "selftest_projdiv: no HIP device %d", device);
     HIP_TRY(hipSetDevice(device));
     unsigned long long* d_bad = nullptr;
     HIP_TRY(hipMalloc(&d_bad, 2 * sizeof(unsigned long long)));
@@ -488,7 +473,7 @@ int youth_icp_selftest_projdiv(int device, long long n, unsigned long long seed,
     if (e == hipSuccess) e = launch_selftest(0, (unsigned long long)n, seed, d_bad);
     if (e == hipSuccess) e = hipMemcpy(h, d_bad, sizeof(h), hipMemcpyDeviceToHost);
     (void)hipFree(d_bad);
-    if (e != hipSuccess) return set_error(YOUTH_EHIP, "selftest_projdiv: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return g_icp_err.set(YOUTH_EHIP, "selftest_projdiv: %s", hipGetErrorString(e));
     if (bit_mismatches) *bit_mismatches = (long long)h[0];
     if (proj_mismatches) *proj_mismatches = (long long)h[1];
     return YOUTH_OK;
@@ -498,10 +483,10 @@ int youth_icp_selftest_projquot(int device, long long n, unsigned long long seed
                                 long long* quot_mismatches, long long* proj_mismatches,
                                 long long* floor_mismatches)
 {
-    if (n < 0) return set_error(YOUTH_EINVAL, "selftest_projquot: n < 0");
+    if (n < 0) return g_icp_err.set(YOUTH_EINVAL, "selftest_projquot: n < 0");
     const int ndev = youth_icp_device_count();
     if (ndev <= 0 || device < 0 || device >= ndev)
-        return set_error(YOUTH_ENODEV, "selftest_projquot: no HIP device %d", device);
+        return g_icp_err.set(YOUTH_ENODEV, "selftest_projquot: no HIP device %d", device);
     HIP_TRY(hipSetDevice(device));
     unsigned long long* d_bad = nullptr;
     HIP_TRY(hipMalloc(&d_bad, 3 * sizeof(unsigned long long)));
@@ -510,7 +495,7 @@ int youth_icp_selftest_projquot(int device, long long n, unsigned long long seed
     if (e == hipSuccess) e = launch_selftest(1, (unsigned long long)n, seed, d_bad);
     if (e == hipSuccess) e = hipMemcpy(h, d_bad, sizeof(h), hipMemcpyDeviceToHost);
     (void)hipFree(d_bad);
-    if (e != hipSuccess) return set_error(YOUTH_EHIP, "selftest_projquot: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return g_icp_err.set(YOUTH_EHIP, "selftest_projquot: %s", hipGetErrorString(e));
     if (quot_mismatches) *quot_mismatches = (long long)h[0];
     if (proj_mismatches) *proj_mismatches = (long long)h[1];
     if (floor_mismatches) *floor_mismatches = (long long)h[2];
@@ -521,10 +506,10 @@ int youth_icp_selftest_normalize(int device, long long n, unsigned long long see
                                  long long* sqrt_mismatches, long long* quot_mismatches,
                                  long long* fast_cases)
 {
-    if (n < 0) return set_error(YOUTH_EINVAL, "selftest_normalize: n < 0");
+    if (n < 0) return g_icp_err.set(YOUTH_EINVAL, "selftest_normalize: n < 0");
     const int ndev = youth_icp_device_count();
     if (ndev <= 0 || device < 0 || device >= ndev)
-        return set_error(YOUTH_ENODEV, "selftest_normalize: no HIP device %d", device);
+        return g_icp_err.set(YOUTH_ENODEV, "selftest_normalize: no HIP device %d", device);
     HIP_TRY(hipSetDevice(device));
     unsigned long long* d_bad = nullptr;
     HIP_TRY(hipMalloc(&d_bad, 3 * sizeof(unsigned long long)));
@@ -534,7 +519,7 @@ int youth_icp_selftest_normalize(int device, long long n, unsigned long long see
     if (e == hipSuccess) e = hipMemcpy(h, d_bad, sizeof(h), hipMemcpyDeviceToHost);
     (void)hipFree(d_bad);
     if (e != hipSuccess)
-        return set_error(YOUTH_EHIP, "selftest_normalize: %s", hipGetErrorString(e));
+        return g_icp_err.set(YOUTH_EHIP, "selftest_normalize: %s", hipGetErrorString(e));
     if (sqrt_mismatches) *sqrt_mismatches = (long long)h[0];
     if (quot_mismatches) *quot_mismatches = (long long)h[1];
     if (fast_cases) *fast_cases = (long long)h[2];
@@ -543,7 +528,7 @@ int youth_icp_selftest_normalize(int device, long long n, unsigned long long see
 
 int youth_icp_get_sched_stats(youth_icp_ctx* c, unsigned* spins, unsigned* waited_items)
 {
-    if (!c) return set_error(YOUTH_EINVAL, "get_sched_stats: null context");
+    if (!c) return g_icp_err.set(YOUTH_EINVAL, "get_sched_stats: null context");
     int rc = bind_device(c);
     if (rc) return rc;
     unsigned h[kQWords];
@@ -556,7 +541,7 @@ int youth_icp_get_sched_stats(youth_icp_ctx* c, unsigned* spins, unsigned* waite
 
 int youth_icp_get_plan(youth_icp_ctx* c, int* workgroups_per_pair, int* px_per_lane)
 {
-    if (!c) return set_error(YOUTH_EINVAL, "get_plan: null context");
+    if (!c) return g_icp_err.set(YOUTH_EINVAL, "get_plan: null context");
     if (workgroups_per_pair) *workgroups_per_pair = c->last_coop ? c->last_coop_G : 0;
     if (px_per_lane) *px_per_lane = c->last_coop ? c->last_coop_px : 0;
     return c->last_coop ? 1 : c->persistent ? 0 : 2;
@@ -564,7 +549,7 @@ int youth_icp_get_plan(youth_icp_ctx* c, int* workgroups_per_pair, int* px_per_l
 
 int youth_icp_get_timing(youth_icp_ctx* c, int kind, double* total_ms, int* launches)
 {
-    if (!c || kind < 0 || kind > 2) return set_error(YOUTH_EINVAL, "get_timing: bad kind %d", kind);
+    if (!c || kind < 0 || kind > 2) return g_icp_err.set(YOUTH_EINVAL, "get_timing: bad kind %d", kind);
     int rc = bind_device(c);
     if (rc) return rc;
     rc = ev_harvest(c);
@@ -579,7 +564,7 @@ int youth_icp_prepare_host(youth_icp_ctx* c, const int16_t* depth, int n_frames,
                            float* NY, float* NZ)
 {
     if (!c || !depth || n_frames <= 0 || n_frames > c->max_frames)
-        return set_error(YOUTH_EINVAL, "prepare_host: bad arguments %d", n_frames);
+        return g_icp_err.set(YOUTH_EINVAL, "prepare_host: bad arguments %d", n_frames);
     int rc = bind_device(c);
     if (rc) return rc;
     hipStream_t s = c->stream;
@@ -611,7 +596,7 @@ int youth_icp_prepare_host(youth_icp_ctx* c, const int16_t* depth, int n_frames,
 int youth_icp_reduce_host(youth_icp_ctx* c, const int16_t* src, const int16_t* dst,
                           const float* T12, int32_t* assoc, double* neq)
 {
-    if (!c || !src || !dst || !T12) return set_error(YOUTH_EINVAL, "reduce_host: bad arguments");
+    if (!c || !src || !dst || !T12) return g_icp_err.set(YOUTH_EINVAL, "reduce_host: bad arguments");
     int rc = bind_device(c);
     if (rc) return rc;
     hipStream_t s = c->stream;
@@ -636,7 +621,7 @@ int youth_icp_reduce_host(youth_icp_ctx* c, const int16_t* src, const int16_t* d
 
 int youth_icp_solve_host(youth_icp_ctx* c, const double* neq, double* T64)
 {
-    if (!c || !neq || !T64) return set_error(YOUTH_EINVAL, "solve_host: bad arguments");
+    if (!c || !neq || !T64) return g_icp_err.set(YOUTH_EINVAL, "solve_host: bad arguments");
     int rc = bind_device(c);
     if (rc) return rc;
     hipStream_t s = c->stream;

@@ -75,9 +75,10 @@ static int batch_on_device(int dev, const int16_t* src, const int16_t* dst, int 
         if (c) youth_icp_destroy(c);
         slot = nullptr;
         c = youth_icp_create(dev, W, H, 2 * n_pairs, &Kd, &P);
+        // youth_icp_create's text stands; of its codes only "no HIP device"
+        // is passed on, every other failure (a bad size too) reads YOUTH_EHIP
         if (!c)
-            return g_last_error.find("no HIP device") != std::string::npos ? YOUTH_ENODEV
-                                                                          : YOUTH_EHIP;
+            return g_icp_err.code() == YOUTH_ENODEV ? YOUTH_ENODEV : YOUTH_EHIP;
         slot = c;
     }
     c->prm = P;
@@ -119,7 +120,7 @@ static int batch_on_device(int dev, const int16_t* src, const int16_t* dst, int 
         if (e == hipSuccess) e = hipEventRecord(c->xfer_ev[k], c->xfer);
         if (e == hipSuccess) e = hipStreamWaitEvent(s, c->xfer_ev[k], 0);
         if (e != hipSuccess)
-            return drain(set_error(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
+            return drain(g_icp_err.set(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
         rc = youth_icp_align_pairs_device(c, d_s + p0 * N, d_d + p0 * N, cnt, nullptr,
                                           c->d_Tout + p0 * 16, s);
         if (rc) return drain(rc);
@@ -130,7 +131,7 @@ static int batch_on_device(int dev, const int16_t* src, const int16_t* dst, int 
         else
             mixed |= memcmp(&first_lanes, &c->lanes, sizeof(youth_lanes)) != 0;
         if ((e = launch_status_out(c, s, cnt, c->d_status_out + p0)) != hipSuccess)
-            return drain(set_error(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
+            return drain(g_icp_err.set(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
     }
     // A chunk of <= 16 pairs is one cooperative launch sized to an idle
     // device; on a GPU shared with other processes its grid may not be
@@ -144,7 +145,7 @@ static int batch_on_device(int dev, const int16_t* src, const int16_t* dst, int 
         hipError_t e = hipMemcpyAsync(st.data(), c->d_status_out, (size_t)n_pairs * sizeof(int32_t),
                                       hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return drain(set_error(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return drain(g_icp_err.set(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
         for (int k = 0; k < n_chunks; ++k) {
             const size_t p0 = (size_t)k * chunk;
             const int cnt = (int)std::min<size_t>(chunk, n_pairs - p0);
@@ -163,7 +164,7 @@ static int batch_on_device(int dev, const int16_t* src, const int16_t* dst, int 
             ++c->batch_realigned;
             mixed = true;  // this chunk's lane partition is the persistent kernel's
             if ((e = launch_status_out(c, s, cnt, c->d_status_out + p0)) != hipSuccess)
-                return drain(set_error(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
+                return drain(g_icp_err.set(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
         }
     }
     if (assoc_out) {
@@ -175,7 +176,7 @@ static int batch_on_device(int dev, const int16_t* src, const int16_t* dst, int 
         hipError_t e = hipMemcpyAsync(assoc_out, c->d_assoc, (size_t)n_pairs * N * sizeof(int32_t),
                                       hipMemcpyDeviceToHost, s);
         if (e != hipSuccess)
-            return drain(set_error(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
+            return drain(g_icp_err.set(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
     }
     c->lanes_mixed = mixed;
     hipError_t e = hipMemcpyAsync(T_out, c->d_Tout, (size_t)n_pairs * 16 * sizeof(float),
@@ -183,7 +184,7 @@ static int batch_on_device(int dev, const int16_t* src, const int16_t* dst, int 
     if (e == hipSuccess && status_out)
         e = hipMemcpyAsync(status_out, c->d_status_out, (size_t)n_pairs * sizeof(int32_t),
                            hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return drain(set_error(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return drain(g_icp_err.set(YOUTH_EHIP, "align_batch: %s", hipGetErrorString(e)));
     HIP_TRY(hipStreamSynchronize(s));
     return YOUTH_OK;
 }
@@ -193,7 +194,7 @@ int youth_icp_align_batch(const int16_t* src, const int16_t* dst, int n_pairs, i
                           int32_t* assoc_out)
 {
     if (!src || !dst || n_pairs <= 0 || W < 3 || H < 3 || iters < 0 || !T_out)
-        return set_error(YOUTH_EINVAL, "align_batch: bad arguments %d", n_pairs);
+        return g_icp_err.set(YOUTH_EINVAL, "align_batch: bad arguments %d", n_pairs);
     std::lock_guard<std::mutex> lk(g_batch_mu[0]);
     const youth_intrinsics Kd = K ? *K : youth_default_intrinsics(W, H);
     return batch_on_device(0, src, dst, n_pairs, W, H, Kd, iters, T_out, nullptr, assoc_out);
@@ -211,7 +212,7 @@ static void shard_range(int n, int k, int r, int* first, int* count)
 int youth_icp_shard_range(int n_pairs, int n_parts, int part, int* first, int* count)
 {
     if (n_pairs < 0 || n_parts <= 0 || part < 0 || part >= n_parts || !first || !count)
-        return set_error(YOUTH_EINVAL, "shard_range: bad arguments");
+        return g_icp_err.set(YOUTH_EINVAL, "shard_range: bad arguments");
     shard_range(n_pairs, n_parts, part, first, count);
     return YOUTH_OK;
 }
@@ -221,17 +222,17 @@ int youth_icp_align_batch_multi(const int16_t* src, const int16_t* dst, int n_pa
                                 int n_devices, float* T_out, int32_t* status_out)
 {
     if (!src || !dst || n_pairs <= 0 || W < 3 || H < 3 || iters < 0 || !T_out)
-        return set_error(YOUTH_EINVAL, "align_batch_multi: bad arguments %d", n_pairs);
+        return g_icp_err.set(YOUTH_EINVAL, "align_batch_multi: bad arguments %d", n_pairs);
     const int ndev = youth_icp_device_count();
-    if (ndev <= 0) return set_error(YOUTH_ENODEV, "align_batch_multi: no HIP device");
+    if (ndev <= 0) return g_icp_err.set(YOUTH_ENODEV, "align_batch_multi: no HIP device");
     std::vector<int> devs;
     if (devices && n_devices > 0) {
         for (int i = 0; i < n_devices; ++i) {
             if (devices[i] < 0 || devices[i] >= ndev || devices[i] >= 64)
-                return set_error(YOUTH_EINVAL, "align_batch_multi: no HIP device %d", devices[i]);
+                return g_icp_err.set(YOUTH_EINVAL, "align_batch_multi: no HIP device %d", devices[i]);
             if (std::find(devs.begin(), devs.end(), devices[i]) != devs.end())
-                return set_error(YOUTH_EINVAL, "align_batch_multi: device %d listed twice",
-                                 devices[i]);
+                return g_icp_err.set(YOUTH_EINVAL, "align_batch_multi: device %d listed twice",
+                                     devices[i]);
             devs.push_back(devices[i]);
         }
     } else {
@@ -249,7 +250,7 @@ int youth_icp_align_batch_multi(const int16_t* src, const int16_t* dst, int n_pa
         rcs[r] = batch_on_device(devs[r], src + (size_t)first * N, dst + (size_t)first * N, cnt, W,
                                  H, Kd, iters, T_out + (size_t)first * 16,
                                  status_out ? status_out + first : nullptr, nullptr);
-        if (rcs[r]) errs[r] = g_last_error;  // thread-local: carried to the caller below
+        if (rcs[r]) errs[r] = g_icp_err.c_str();  // thread-local: carried to the caller below
     };
     // one host thread per device; shard 0 runs on the calling thread
     std::vector<std::thread> th;
@@ -258,8 +259,7 @@ int youth_icp_align_batch_multi(const int16_t* src, const int16_t* dst, int n_pa
     for (auto& t : th) t.join();
     for (int r = 0; r < parts; ++r)
         if (rcs[r]) {
-            g_last_error = "device " + std::to_string(devs[r]) + ": " + errs[r];
-            return rcs[r];
+            return g_icp_err.set(rcs[r], "device %d: %s", devs[r], errs[r].c_str());
         }
     return YOUTH_OK;
 }

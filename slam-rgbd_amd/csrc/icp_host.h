@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "hip_host.h"
 #include "host_copy.h"
 #include "icp_device.h"
 #include "youth_icp.h"
@@ -27,22 +28,14 @@
 // Cross-unit functions are hidden: libyouth_icp.so exports the C API only.
 namespace youth_icp __attribute__((visibility("hidden"))) {
 
-// The last error's text, one per thread and library: youth_icp_last_error and
+// The ICP channel (hip_host.h), one per thread: youth_icp_last_error and
 // youth_rgbd_last_error read it.
-extern thread_local std::string g_last_error;
-
-// Sets g_last_error; returns code.
-__attribute__((format(printf, 2, 3))) int set_error(int code, const char* fmt, ...);
+extern thread_local youth::ErrorText g_icp_err;
 
 }  // namespace youth_icp
 
-#define HIP_TRY(expr)                                                                    \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess)                                                            \
-            return youth_icp::set_error(YOUTH_EHIP, "%s (line %d)", hipGetErrorString(e_),  \
-                                        __LINE__);                                       \
-    } while (0)
+// the channel HIP_TRY (hip_host.h) reports to in every unit on this header
+#define HIP_ERR youth_icp::g_icp_err
 
 struct EventPair {
     hipEvent_t a, b;
@@ -226,21 +219,6 @@ hipError_t fill_occupancy(youth_icp_ctx* c, const char** what);
 int verify_fastdiv(youth_icp_ctx* c);
 // youth_icp_destroy's part: the device's coop ordering forgets c->stream.
 void coop_forget_stream(youth_icp_ctx* c);
-
-// Grow the device buffer *buf to hold at least `want` units of `per` elements;
-// *cap is its capacity in units.  A failure leaves it empty: the pointer is
-// nulled and the capacity zeroed before the new allocation.
-template <typename T, typename N>
-int grow_device_buffer(T** buf, N* cap, N want, size_t per = 1)
-{
-    if (want <= *cap) return YOUTH_OK;
-    if (*buf) HIP_TRY(hipFree(*buf));
-    *buf = nullptr;
-    *cap = 0;
-    HIP_TRY(hipMalloc(buf, (size_t)want * per * sizeof(T)));
-    *cap = want;
-    return YOUTH_OK;
-}
 
 int ensure_stats(youth_icp_ctx* c, int iters);
 int ensure_partials(youth_icp_ctx* c, size_t doubles);

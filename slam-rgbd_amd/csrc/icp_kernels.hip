@@ -1813,7 +1813,7 @@ static int ensure_coop_part(youth_icp_ctx* c, hipStream_t s, int rows)
 
 int ensure_partials(youth_icp_ctx* c, size_t doubles)
 {
-    return grow_device_buffer(&c->d_partials, &c->partials_cap, doubles);
+    return grow_device_buffer(g_icp_err, &c->d_partials, &c->partials_cap, doubles);
 }
 
 int ensure_stats(youth_icp_ctx* c, int iters)
@@ -1821,9 +1821,9 @@ int ensure_stats(youth_icp_ctx* c, int iters)
     // two buffers of one capacity, stats_iters: the tickets grow on a copy of
     // it, and it is zero unless both hold that many iterations
     int arr_iters = c->stats_iters;
-    const int rc = grow_device_buffer(&c->d_arr_it, &arr_iters, iters, (size_t)c->max_frames);
+    const int rc = grow_device_buffer(g_icp_err, &c->d_arr_it, &arr_iters, iters, (size_t)c->max_frames);
     if (rc == YOUTH_OK)
-        return grow_device_buffer(&c->d_stats, &c->stats_iters, iters, (size_t)c->max_frames * 2);
+        return grow_device_buffer(g_icp_err, &c->d_stats, &c->stats_iters, iters, (size_t)c->max_frames * 2);
     c->stats_iters = 0;
     return rc;
 }
@@ -1895,7 +1895,7 @@ static int launch_prep_with(youth_icp_ctx* c, hipStream_t s, const int16_t* dept
     const int tiles_x = (c->W + kPrepTW - 1) / kPrepTW, tiles_y = (c->H + kPrepTH - 1) / kPrepTH;
     const long long rows = (long long)tiles_y * n_frames;
     const long long blocks = (long long)tiles_x * (c->prep_xcd_map == 2 ? (rows + 7) / 8 * 8 : rows);
-    if (blocks > 0x7fffffffLL) return set_error(YOUTH_EINVAL, "launch_prep: %lld tiles", blocks);
+    if (blocks > 0x7fffffffLL) return g_icp_err.set(YOUTH_EINVAL, "launch_prep: %lld tiles", blocks);
     EventPair ep{};
     int rc = ev_begin(c, s, &ep, 2);
     if (rc) return rc;
@@ -1969,7 +1969,7 @@ int launch_reduce(youth_icp_ctx* c, hipStream_t s, const int16_t* dsrc, int src0
     const PoseState ps{c->d_T64, c->d_T32, c->d_status, c->d_stats, c->d_arrivals,
                        fuse_it < 0 ? 0 : fuse_it, c->prm.iters};
     const bool fuse = fuse_it >= 0;
-    if (assoc && fuse) return set_error(YOUTH_EINVAL, "launch_reduce: assoc with fused solve");
+    if (assoc && fuse) return g_icp_err.set(YOUTH_EINVAL, "launch_reduce: assoc with fused solve");
     const int sel = (assoc ? 8 : 0) | (fuse ? 4 : 0) | (c->fast ? 2 : 0) | (aligned ? 1 : 0);
     switch (variant(c)) {
     case 0: launch_reduce_sel<0>(c, s, grid, dsrc, pm, thr2, chunk, ps, sel); break;
@@ -2079,7 +2079,7 @@ static int coop_enqueue(youth_icp_ctx* c, hipStream_t s, void** args, int blocks
     const dim3 grid((unsigned)blocks), block(c->coop_threads);
     const unsigned lds = (unsigned)coop_lds(npx, c->coop_threads);
     if (c->coop_refuse)  // test hook: the runtime's refusal, nothing enqueued
-        return set_error(YOUTH_EHIP, "coop_enqueue: cooperative launch refused (test hook)");
+        return g_icp_err.set(YOUTH_EHIP, "coop_enqueue: cooperative launch refused (test hook)");
     if (c->coop_launch == 1) {
         HIP_TRY(hipLaunchCooperativeKernel(kern, grid, block, args, lds, s));
         return YOUTH_OK;
@@ -2109,8 +2109,8 @@ static int coop_enqueue(youth_icp_ctx* c, hipStream_t s, void** args, int blocks
             o.draining = false;
             o.cv.notify_all();
             if (e != hipSuccess)
-                return set_error(YOUTH_EHIP, "coop launch: device drain on the first stream "
-                                             "switch: %s", hipGetErrorString(e));
+                return g_icp_err.set(YOUTH_EHIP, "coop launch: device drain on the first stream "
+                                     "switch: %s", hipGetErrorString(e));
             o.multi = true;
         } else {
             HIP_TRY(hipStreamWaitEvent(s, o.done, 0));
@@ -2237,7 +2237,7 @@ int upload_T_init(youth_icp_ctx* c, hipStream_t s, const double* T_init_host, in
     if (!T_init_host) return YOUTH_OK;
     for (size_t i = 0; i < (size_t)n_pairs * 16; ++i)
         if (!std::isfinite(T_init_host[i]))
-            return set_error(YOUTH_EINVAL, "T_init: non-finite entry in pair %d", (int)(i / 16));
+            return g_icp_err.set(YOUTH_EINVAL, "T_init: non-finite entry in pair %d", (int)(i / 16));
     HIP_TRY(hipMemcpyAsync(c->d_Tinit, T_init_host, (size_t)n_pairs * 16 * sizeof(double),
                            hipMemcpyHostToDevice, s));
     *dTi = c->d_Tinit;
@@ -2264,8 +2264,8 @@ int run_iterations(youth_icp_ctx* c, hipStream_t s, const int16_t* dsrc, int src
             (long long)n_pairs * G >
                 (long long)c->n_cu *
                     c->coop_bpc[c->coop_threads == 256][variant(c) * 2 + (c->fast ? 1 : 0)][npx])
-            return set_error(YOUTH_EINVAL, "track batch: %d pairs do not fit one cooperative grid",
-                             n_pairs);
+            return g_icp_err.set(YOUTH_EINVAL, "track batch: %d pairs do not fit one cooperative grid",
+                                 n_pairs);
         coop = true;
     } else {
         coop = iters > 0 && (!job || job->n == n_pairs || (!job->wait && job->n == 1)) &&

@@ -152,20 +152,20 @@ static int ensure_raw(youth_icp_ctx* c)
 static int track_filter(youth_icp_ctx* c, int n, int16_t* dst, hipStream_t stream)
 {
     const int rc = youth_depth_filter_device(c->device, c->d_raw, dst, n, c->W, c->H, &c->flt, stream);
-    if (rc) return set_error(rc, "depth filter: %s", youth_depth_filter_last_error());
+    if (rc) return g_icp_err.set(rc, "depth filter: %s", youth_depth_filter_last_error());
     return YOUTH_OK;
 }
 
 int youth_icp_set_depth_filter(youth_icp_ctx* c, const youth_filter_params* P)
 {
-    if (!c) return set_error(YOUTH_EINVAL, "set_depth_filter: null context");
+    if (!c) return g_icp_err.set(YOUTH_EINVAL, "set_depth_filter: null context");
     if (P && !filter_params_ok(P))
-        return set_error(YOUTH_EINVAL,
-                         "set_depth_filter: t0 %d, t2 %d (need 1 <= t0 <= 255, 0 <= t2 <= 1000)",
-                         P->t0, P->t2);
+        return g_icp_err.set(YOUTH_EINVAL,
+                             "set_depth_filter: t0 %d, t2 %d (need 1 <= t0 <= 255, 0 <= t2 <= 1000)",
+                             P->t0, P->t2);
     if (c->trk_n > 0)
-        return set_error(YOUTH_EINVAL, "set_depth_filter: %d frames in flight (collect them first)",
-                         c->trk_n);
+        return g_icp_err.set(YOUTH_EINVAL, "set_depth_filter: %d frames in flight (collect them first)",
+                             c->trk_n);
     if (P) {
         int rc = bind_device(c);
         if (rc) return rc;
@@ -179,7 +179,7 @@ int youth_icp_set_depth_filter(youth_icp_ctx* c, const youth_filter_params* P)
 
 int youth_icp_get_depth_filter(const youth_icp_ctx* c, youth_filter_params* out)
 {
-    if (!c) return set_error(YOUTH_EINVAL, "get_depth_filter: null context");
+    if (!c) return g_icp_err.set(YOUTH_EINVAL, "get_depth_filter: null context");
     if (c->flt_on && out) *out = c->flt;
     return c->flt_on ? 1 : 0;
 }
@@ -338,14 +338,14 @@ static int track_submit_frames(youth_icp_ctx* c, const int16_t* depth, int m,
 
 int youth_icp_track_submit(youth_icp_ctx* c, const int16_t* depth, const double* T_init)
 {
-    if (!c || !depth) return set_error(YOUTH_EINVAL, "track_submit: bad arguments");
+    if (!c || !depth) return g_icp_err.set(YOUTH_EINVAL, "track_submit: bad arguments");
     if (c->trk_n >= kTrackDepth)
-        return set_error(YOUTH_EINVAL, "track_submit: %d frames in flight (collect one first)",
-                         kTrackDepth);
+        return g_icp_err.set(YOUTH_EINVAL, "track_submit: %d frames in flight (collect one first)",
+                             kTrackDepth);
     if (T_init)
         for (int i = 0; i < 16; ++i)
             if (!std::isfinite(T_init[i]))
-                return set_error(YOUTH_EINVAL, "T_init: non-finite entry in pair 0");
+                return g_icp_err.set(YOUTH_EINVAL, "T_init: non-finite entry in pair 0");
     int rc = bind_device(c);
     if (rc) return rc;
     rc = ensure_track(c);
@@ -359,8 +359,8 @@ static int track_submit_many(youth_icp_ctx* c, const int16_t* depth,
                              const int16_t* const* frames, int n_frames)
 {
     if (c->trk_n + n_frames > kTrackDepth)
-        return set_error(YOUTH_EINVAL, "track_submit_batch: %d + %d frames in flight (max %d)",
-                         c->trk_n, n_frames, kTrackDepth);
+        return g_icp_err.set(YOUTH_EINVAL, "track_submit_batch: %d + %d frames in flight (max %d)",
+                             c->trk_n, n_frames, kTrackDepth);
     int rc = bind_device(c);
     if (rc) return rc;
     rc = ensure_track(c);
@@ -388,16 +388,16 @@ static int track_submit_many(youth_icp_ctx* c, const int16_t* depth,
 int youth_icp_track_submit_batch(youth_icp_ctx* c, const int16_t* depth, int n_frames)
 {
     if (!c || !depth || n_frames < 1 || n_frames > YOUTH_TRACK_MAX_BATCH)
-        return set_error(YOUTH_EINVAL, "track_submit_batch: bad arguments (%d frames)", n_frames);
+        return g_icp_err.set(YOUTH_EINVAL, "track_submit_batch: bad arguments (%d frames)", n_frames);
     return track_submit_many(c, depth, nullptr, n_frames);
 }
 
 int youth_icp_track_submit_pinned(youth_icp_ctx* c, const int16_t* const* frames, int n_frames)
 {
     if (!c || !frames || n_frames < 1 || n_frames > YOUTH_TRACK_MAX_BATCH)
-        return set_error(YOUTH_EINVAL, "track_submit_pinned: bad arguments (%d frames)", n_frames);
+        return g_icp_err.set(YOUTH_EINVAL, "track_submit_pinned: bad arguments (%d frames)", n_frames);
     for (int i = 0; i < n_frames; ++i)
-        if (!frames[i]) return set_error(YOUTH_EINVAL, "track_submit_pinned: frame %d is null", i);
+        if (!frames[i]) return g_icp_err.set(YOUTH_EINVAL, "track_submit_pinned: frame %d is null", i);
     return track_submit_many(c, nullptr, frames, n_frames);
 }
 
@@ -447,8 +447,8 @@ static hipError_t track_wait(hipEvent_t ev)
 
 int youth_icp_track_collect(youth_icp_ctx* c, double* T_rel, int* has_ref)
 {
-    if (!c || !T_rel) return set_error(YOUTH_EINVAL, "track_collect: bad arguments");
-    if (c->trk_n == 0) return set_error(YOUTH_EINVAL, "track_collect: no frame in flight");
+    if (!c || !T_rel) return g_icp_err.set(YOUTH_EINVAL, "track_collect: bad arguments");
+    if (c->trk_n == 0) return g_icp_err.set(YOUTH_EINVAL, "track_collect: no frame in flight");
     int rc = bind_device(c);
     if (rc) return rc;
     auto& q = c->trk[c->trk_head];
@@ -494,11 +494,11 @@ int youth_icp_track_realign(youth_icp_ctx* c, const int16_t* ref_depth, const in
                             const double* T_init, double* T_rel)
 {
     if (!c || !ref_depth || !depth || !T_rel)
-        return set_error(YOUTH_EINVAL, "track_realign: bad arguments");
+        return g_icp_err.set(YOUTH_EINVAL, "track_realign: bad arguments");
     if (T_init)
         for (int i = 0; i < 16; ++i)
             if (!std::isfinite(T_init[i]))
-                return set_error(YOUTH_EINVAL, "T_init: non-finite entry in pair 0");
+                return g_icp_err.set(YOUTH_EINVAL, "T_init: non-finite entry in pair 0");
     int rc = bind_device(c);
     if (rc) return rc;
     hipStream_t s = c->stream;
@@ -561,8 +561,8 @@ int youth_icp_track_host_sequence(youth_icp_ctx* c, const int16_t* frames, int n
                                   double* T_rel, int32_t* status)
 {
     if (!c || !frames || n_frames < 0 || !T_rel)
-        return set_error(YOUTH_EINVAL, "track_host_sequence: bad arguments");
-    if (c->trk_n) return set_error(YOUTH_EINVAL, "track_host_sequence: submitted frames not collected");
+        return g_icp_err.set(YOUTH_EINVAL, "track_host_sequence: bad arguments");
+    if (c->trk_n) return g_icp_err.set(YOUTH_EINVAL, "track_host_sequence: submitted frames not collected");
     const size_t N = c->N;
     int written = 0, collected = 0;
     auto collect = [&]() -> int {
@@ -622,8 +622,8 @@ int youth_icp_track_host_sequence(youth_icp_ctx* c, const int16_t* frames, int n
 int youth_icp_track_frame(youth_icp_ctx* c, const int16_t* depth, const double* T_init,
                           double* T_rel, int* has_ref)
 {
-    if (!c || !depth || !T_rel) return set_error(YOUTH_EINVAL, "track_frame: bad arguments");
-    if (c->trk_n) return set_error(YOUTH_EINVAL, "track_frame: submitted frames not collected");
+    if (!c || !depth || !T_rel) return g_icp_err.set(YOUTH_EINVAL, "track_frame: bad arguments");
+    if (c->trk_n) return g_icp_err.set(YOUTH_EINVAL, "track_frame: submitted frames not collected");
     const int rc = youth_icp_track_submit(c, depth, T_init);
     if (rc) return rc;
     return youth_icp_track_collect(c, T_rel, has_ref);
@@ -632,7 +632,7 @@ int youth_icp_track_frame(youth_icp_ctx* c, const int16_t* depth, const double* 
 int youth_icp_track_set_batch(youth_icp_ctx* c, int frames)
 {
     if (!c || frames < 1 || frames > YOUTH_TRACK_MAX_BATCH)
-        return set_error(YOUTH_EINVAL, "track_set_batch: bad arguments (%d)", frames);
+        return g_icp_err.set(YOUTH_EINVAL, "track_set_batch: bad arguments (%d)", frames);
     const int old = c->trk_batch;
     c->trk_batch = frames;
     // batch mode: the fewest source pixels per lane whose workgroups for

@@ -302,34 +302,26 @@ __global__ __launch_bounds__(kRThreads) void k_map_render_resolve(
     }
 }
 
-#define RENDER_TRY(expr)                                                                   \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return youth_map_set_error(YOUTH_EHIP, "%s (map_render line %d)",              \
-                                       hipGetErrorString(e_), __LINE__);                   \
-    } while (0)
-
 // The limits of a view (youth_map_render.h); on success the defaults are filled in.
 int check_view(const char* who, const struct youth_map_view* view, const youth_intrinsics* K,
                struct youth_map_view& v)
 {
-    if (!view) return youth_map_set_error(YOUTH_EINVAL, "%s: null view", who);
+    if (!view) return g_map_err.set(YOUTH_EINVAL, "%s: null view", who);
     v = *view;
-    if (v.W < 1 || v.H < 1 || v.W > 16384 || v.H > 16384 || (long long)v.W * v.H > (1LL << 26))
-        return youth_map_set_error(YOUTH_EINVAL,
-                                   "%s: %dx%d view (need 1 <= W,H <= 16384, W*H <= 2^26)", who, v.W,
-                                   v.H);
+    if (!youth::frame_size_ok(v.W, v.H, 1))
+        return g_map_err.set(YOUTH_EINVAL,
+                             "%s: %dx%d view (need 1 <= W,H <= 16384, W*H <= 2^26)", who, v.W,
+                             v.H);
     if (v.max_splat < 0 || v.max_splat > 16)
-        return youth_map_set_error(YOUTH_EINVAL, "%s: max_splat %d (need 0 or 1..16)", who,
-                                   v.max_splat);
+        return g_map_err.set(YOUTH_EINVAL, "%s: max_splat %d (need 0 or 1..16)", who,
+                             v.max_splat);
     if (v.max_splat == 0) v.max_splat = 16;
     if (v.min_count == 0) v.min_count = 1;
     if (K && !(std::isfinite(K->fx) && std::isfinite(K->fy) && std::isfinite(K->cx) &&
                std::isfinite(K->cy) && std::isfinite(K->depth_scale) && K->fx > 0.0f &&
                K->fy > 0.0f && K->depth_scale > 0.0f))
-        return youth_map_set_error(YOUTH_EINVAL,
-                                   "%s: intrinsics must be finite with fx, fy, depth_scale > 0", who);
+        return g_map_err.set(YOUTH_EINVAL,
+                             "%s: intrinsics must be finite with fx, fy, depth_scale > 0", who);
     return YOUTH_OK;
 }
 
@@ -337,12 +329,14 @@ int render_launch(const youth_map_render_res& r, int n_views, const struct youth
                   const youth_intrinsics* K, const float* d_V, int16_t* d_depth, uint8_t* d_rgb,
                   hipStream_t s)
 {
+    // the viewer's default: 570.3, 570.3, (float)(W / 2), (float)(H / 2), 1000
+    const youth_intrinsics Kd = K ? *K : youth_default_intrinsics(v.W, v.H);
     RenderP P;
-    P.fx = K ? K->fx : 570.3f;   // the viewer's default
-    P.fy = K ? K->fy : 570.3f;
-    P.cx = K ? K->cx : (float)(v.W / 2);
-    P.cy = K ? K->cy : (float)(v.H / 2);
-    P.ds = K ? K->depth_scale : 1000.0f;
+    P.fx = Kd.fx;
+    P.fy = Kd.fy;
+    P.cx = Kd.cx;
+    P.cy = Kd.cy;
+    P.ds = Kd.depth_scale;
     P.vpm = r.vpm;
     P.ulim = (float)(v.W + 32);
     P.vlim = (float)(v.H + 32);
@@ -357,7 +351,7 @@ int render_launch(const youth_map_render_res& r, int n_views, const struct youth
         k_map_render_splat<true><<<dim3(tiles, n_views), kRThreads, 0, s>>>(t, P, d_V, r.zbuf);
     else
         k_map_render_splat<false><<<dim3(tiles, n_views), kRThreads, 0, s>>>(t, P, d_V, r.zbuf);
-    RENDER_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     const int N = v.W * v.H;
     const bool vec = (N % kRPx) == 0 && ((uintptr_t)d_depth % 16) == 0 &&
                      (!d_rgb || ((uintptr_t)d_rgb % 8) == 0);
@@ -368,7 +362,7 @@ int render_launch(const youth_map_render_res& r, int n_views, const struct youth
     const int px = kRThreads * kRPx;
     hipLaunchKernelGGL(fn[vec][d_rgb != nullptr], dim3((N + px - 1) / px, n_views),
                        dim3(kRThreads), 0, s, r.zbuf, d_depth, d_rgb, N);
-    RENDER_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return YOUTH_OK;
 }
 
@@ -378,11 +372,11 @@ extern "C" {
 
 int youth_map_view_from_pose(const double T_world[16], float V[12])
 {
-    if (!T_world || !V) return youth_map_set_error(YOUTH_EINVAL, "youth_map_view_from_pose: null argument");
+    if (!T_world || !V) return g_map_err.set(YOUTH_EINVAL, "youth_map_view_from_pose: null argument");
     for (int q = 0; q < 12; ++q)
         if (!std::isfinite(T_world[q]))
-            return youth_map_set_error(YOUTH_EINVAL,
-                                       "youth_map_view_from_pose: pose entry %d is not finite", q);
+            return g_map_err.set(YOUTH_EINVAL,
+                                 "youth_map_view_from_pose: pose entry %d is not finite", q);
     const double* T = T_world;
     float out[12];
     for (int r = 0; r < 3; ++r) {
@@ -392,8 +386,8 @@ int youth_map_view_from_pose(const double T_world[16], float V[12])
     }
     for (int q = 0; q < 12; ++q)
         if (!std::isfinite(out[q]))
-            return youth_map_set_error(YOUTH_EINVAL,
-                                       "youth_map_view_from_pose: entry %d of the view is not finite", q);
+            return g_map_err.set(YOUTH_EINVAL,
+                                 "youth_map_view_from_pose: entry %d of the view is not finite", q);
     memcpy(V, out, sizeof(out));
     return YOUTH_OK;
 }
@@ -403,16 +397,16 @@ int youth_map_render_device(youth_map* m, int n_views, const struct youth_map_vi
                             uint8_t* d_rgb, void* stream)
 {
     if (!m || !d_V || !d_depth)
-        return youth_map_set_error(YOUTH_EINVAL, "youth_map_render_device: null argument");
-    if (n_views < 1 || n_views > 65535)
-        return youth_map_set_error(YOUTH_EINVAL, "youth_map_render_device: %d views (need 1..65535)",
-                                   n_views);
+        return g_map_err.set(YOUTH_EINVAL, "youth_map_render_device: null argument");
+    if (n_views < 1 || n_views > youth::kMaxFrames)
+        return g_map_err.set(YOUTH_EINVAL, "youth_map_render_device: %d views (need 1..65535)",
+                             n_views);
     struct youth_map_view v;
     int rc = check_view("youth_map_render_device", view, K, v);
     if (rc < 0) return rc;
     youth_map_render_res r;
-    rc = youth_map_render_acquire(m, (size_t)n_views * v.W * v.H * sizeof(unsigned long long), 0,
-                                  false, (hipStream_t)stream, &r);
+    rc = youth_map_render_acquire(m, (size_t)n_views * v.W * v.H, 0, false, (hipStream_t)stream,
+                                  &r);
     if (rc < 0) return rc;
     return render_launch(r, n_views, v, K, d_V, d_depth, d_rgb,
                          stream ? (hipStream_t)stream : r.stream);
@@ -421,7 +415,7 @@ int youth_map_render_device(youth_map* m, int n_views, const struct youth_map_vi
 int youth_map_render_host(youth_map* m, const struct youth_map_view* view, const youth_intrinsics* K,
                           const double* T_world, int16_t* depth, uint8_t* rgb)
 {
-    if (!m || !depth) return youth_map_set_error(YOUTH_EINVAL, "youth_map_render_host: null argument");
+    if (!m || !depth) return g_map_err.set(YOUTH_EINVAL, "youth_map_render_host: null argument");
     struct youth_map_view v;
     int rc = check_view("youth_map_render_host", view, K, v);
     if (rc < 0) return rc;
@@ -429,14 +423,14 @@ int youth_map_render_host(youth_map* m, const struct youth_map_view* view, const
     if (T_world && (rc = youth_map_view_from_pose(T_world, V)) < 0) return rc;
     const size_t N = (size_t)v.W * v.H;
     youth_map_render_res r;
-    rc = youth_map_render_acquire(m, N * sizeof(unsigned long long), N, rgb != nullptr, nullptr, &r);
+    rc = youth_map_render_acquire(m, N, N, rgb != nullptr, nullptr, &r);
     if (rc < 0) return rc;
-    RENDER_TRY(hipMemcpyAsync(r.V, V, sizeof(V), hipMemcpyHostToDevice, r.stream));
+    HIP_TRY(hipMemcpyAsync(r.V, V, sizeof(V), hipMemcpyHostToDevice, r.stream));
     rc = render_launch(r, 1, v, K, r.V, r.depth, rgb ? r.rgb : nullptr, r.stream);
     if (rc < 0) return rc;
-    RENDER_TRY(hipMemcpyAsync(depth, r.depth, N * sizeof(int16_t), hipMemcpyDeviceToHost, r.stream));
-    if (rgb) RENDER_TRY(hipMemcpyAsync(rgb, r.rgb, N * 3, hipMemcpyDeviceToHost, r.stream));
-    RENDER_TRY(hipStreamSynchronize(r.stream));
+    HIP_TRY(hipMemcpyAsync(depth, r.depth, N * sizeof(int16_t), hipMemcpyDeviceToHost, r.stream));
+    if (rgb) HIP_TRY(hipMemcpyAsync(rgb, r.rgb, N * 3, hipMemcpyDeviceToHost, r.stream));
+    HIP_TRY(hipStreamSynchronize(r.stream));
     return YOUTH_OK;
 }
 

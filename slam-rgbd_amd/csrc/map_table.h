@@ -10,6 +10,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "hip_host.h"
 #include "youth_map.h"
 
 // Internal linkage on purpose: the table travels to the kernels by value, and
@@ -48,21 +49,22 @@ struct youth_map_render_res {
     const unsigned long long* keys;
     const uint32_t* vals;
     uint32_t mask;
-    unsigned long long* zbuf;   // >= zbuf_bytes, all ones between renders
+    unsigned long long* zbuf;   // >= zbuf_px values, all ones between renders
     int16_t* depth;             // staging of the host API: stage_px pixels
     uint8_t* rgb;               //   stage_px * 3 bytes when asked for
     float* V;                   //   [12]
 };
 
-// Fills `out`; grows the z-buffer to zbuf_bytes (a grown buffer is filled with
-// all ones on `stream`, NULL = the map's) and the staging buffers to stage_px
-// pixels.  YOUTH_OK or a negative code with the error text set.
+// Fills `out`; grows the z-buffer to zbuf_px 64-bit values (a grown buffer is
+// filled with all ones on `stream`, NULL = the map's) and the staging buffers
+// to stage_px pixels.  YOUTH_OK or a negative code with the error text set.
 __attribute__((visibility("hidden"))) int youth_map_render_acquire(
-    youth_map* m, size_t zbuf_bytes, size_t stage_px, bool stage_rgb, hipStream_t stream,
+    youth_map* m, size_t zbuf_px, size_t stage_px, bool stage_rgb, hipStream_t stream,
     youth_map_render_res* out);
 
-// Sets youth_map_last_error's text; returns code.
-__attribute__((visibility("hidden"), format(printf, 2, 3))) int youth_map_set_error(
-    int code, const char* fmt, ...);
+// The map's channel (hip_host.h), defined in voxel_map.hip: youth_map_last_error
+// reads it, and map_render.hip reports through it too.
+__attribute__((visibility("hidden"))) extern thread_local youth::ErrorText g_map_err;
+#define HIP_ERR g_map_err
 
 #endif  // YOUTH_MAP_TABLE_H

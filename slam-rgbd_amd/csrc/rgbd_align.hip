@@ -348,12 +348,11 @@ struct youth_rgbd_ctx {
 
 static int rgbd_size_ok(const char* who, int n, int W, int H)
 {
-    if (n < 0 || n > 65535 || W < 3 || H < 3 || W > 16384 || H > 16384 ||
-        (long long)W * H > (1LL << 26))
-        return set_error(YOUTH_EINVAL,
-                         "%s: %d frames of %dx%d (need 0 <= frames <= 65535, 3 <= W, H <= 16384, "
-                         "W*H <= 2^26)",
-                         who, n, W, H);
+    if (n < 0 || n > youth::kMaxFrames || !youth::frame_size_ok(W, H, 3))
+        return g_icp_err.set(YOUTH_EINVAL,
+                             "%s: %d frames of %dx%d (need 0 <= frames <= 65535, 3 <= W, H <= 16384, "
+                             "W*H <= 2^26)",
+                             who, n, W, H);
     return YOUTH_OK;
 }
 
@@ -384,7 +383,7 @@ static int rgbd_geometry(const youth_rgbd_ctx* r, int n_pairs, int* chunk_out)
 
 static int rgbd_ensure_stats(youth_rgbd_ctx* r, int iters)
 {
-    return grow_device_buffer(&r->d_stats, &r->stats_iters, iters, (size_t)r->frames * 4);
+    return grow_device_buffer(g_icp_err, &r->d_stats, &r->stats_iters, iters, (size_t)r->frames * 4);
 }
 
 // One k_rgbd_reduce launch over n_pairs pairs: iteration `it` with its fused
@@ -396,7 +395,8 @@ static int rgbd_launch_reduce(youth_rgbd_ctx* r, hipStream_t s, const int16_t* d
     youth_icp_ctx* c = r->icp;
     int chunk = 0;
     const int nb = rgbd_geometry(r, n_pairs, &chunk);
-    int rc = grow_device_buffer(&r->d_part, &r->part_cap, (size_t)nb * n_pairs * kRgbdStride);
+    int rc = grow_device_buffer(g_icp_err, &r->d_part, &r->part_cap,
+                                (size_t)nb * n_pairs * kRgbdStride);
     if (rc) return rc;
     const float thr2 = r->prm.dist_thresh * r->prm.dist_thresh;
     const bool aligned = (reinterpret_cast<uintptr_t>(dsrc) % 8 == 0) &&
@@ -446,7 +446,7 @@ static int rgbd_align(youth_rgbd_ctx* r, hipStream_t s, const int16_t* dsrc, con
 
 extern "C" {
 
-const char* youth_rgbd_last_error(void) { return g_last_error.c_str(); }
+const char* youth_rgbd_last_error(void) { return g_icp_err.c_str(); }
 
 youth_rgbd_params youth_rgbd_default_params(void)
 {
@@ -478,18 +478,17 @@ youth_rgbd_ctx* youth_rgbd_create(int device, int W, int H, int max_frames,
     const youth_rgbd_params prm = params ? *params : youth_rgbd_default_params();
     if (prm.iters < 0 || !std::isfinite(prm.dist_thresh) || !(prm.dist_thresh > 0.0f) ||
         !std::isfinite(prm.lambda) || prm.lambda < 0.0f) {
-        set_error(YOUTH_EINVAL,
-                  "youth_rgbd_create: bad parameters: iters %d, dist_thresh %g, lambda %g (need "
-                  "iters >= 0, dist_thresh > 0 and lambda >= 0, both finite)",
-                  prm.iters, (double)prm.dist_thresh, (double)prm.lambda);
+        g_icp_err.set(YOUTH_EINVAL,
+                      "youth_rgbd_create: bad parameters: iters %d, dist_thresh %g, lambda %g (need "
+                      "iters >= 0, dist_thresh > 0 and lambda >= 0, both finite)",
+                      prm.iters, (double)prm.dist_thresh, (double)prm.lambda);
         return nullptr;
     }
-    if (W < 3 || H < 3 || W > 16384 || H > 16384 || max_frames < 2 || max_frames > 65535 ||
-        (long long)W * H > (1LL << 26)) {
-        set_error(YOUTH_EINVAL,
-                  "youth_rgbd_create: bad size %dx%d / max_frames %d (need 3 <= W, H <= 16384, "
-                  "W*H <= 2^26, 2 <= max_frames <= 65535)",
-                  W, H, max_frames);
+    if (!youth::frame_size_ok(W, H, 3) || max_frames < 2 || max_frames > youth::kMaxFrames) {
+        g_icp_err.set(YOUTH_EINVAL,
+                      "youth_rgbd_create: bad size %dx%d / max_frames %d (need 3 <= W, H <= 16384, "
+                      "W*H <= 2^26, 2 <= max_frames <= 65535)",
+                      W, H, max_frames);
         return nullptr;
     }
     const youth_icp_params ip{prm.iters, prm.dist_thresh};
@@ -511,8 +510,8 @@ youth_rgbd_ctx* youth_rgbd_create(int device, int W, int H, int max_frames,
     if ((e = hipMalloc(&r->d_photo, F * N * sizeof(unsigned))) != hipSuccess ||
         (e = hipMalloc(&r->d_gray, F * N)) != hipSuccess ||
         (e = hipMalloc(&r->d_neq, kRgbdNeq * sizeof(double))) != hipSuccess) {
-        set_error(e == hipErrorOutOfMemory ? YOUTH_ENOMEM : YOUTH_EHIP,
-                  "youth_rgbd_create: hipMalloc: %s", hipGetErrorString(e));
+        g_icp_err.set(e == hipErrorOutOfMemory ? YOUTH_ENOMEM : YOUTH_EHIP,
+                      "youth_rgbd_create: hipMalloc: %s", hipGetErrorString(e));
         youth_rgbd_destroy(r);
         return nullptr;
     }
@@ -527,13 +526,11 @@ int youth_rgbd_luma_device(int device, const uint8_t* d_rgb, uint8_t* d_gray, in
                            void* stream)
 {
     static const char* who = "youth_rgbd_luma_device";
-    if (!d_rgb || !d_gray) return set_error(YOUTH_EINVAL, "%s: null buffer", who);
+    if (!d_rgb || !d_gray) return g_icp_err.set(YOUTH_EINVAL, "%s: null buffer", who);
     int rc = rgbd_size_ok(who, n, W, H);
     if (rc) return rc;
-    const int ndev = youth_icp_device_count();
-    if (ndev <= 0) return set_error(YOUTH_ENODEV, "%s: no HIP device visible", who);
-    if (device < 0 || device >= ndev)
-        return set_error(YOUTH_EINVAL, "%s: device %d of %d", who, device, ndev);
+    rc = youth::check_device(g_icp_err, who, device);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(device));
     return rgbd_launch_prep((hipStream_t)stream, d_rgb, 3, n, W, H, d_gray, nullptr);
 }
@@ -542,9 +539,9 @@ int youth_rgbd_prep_device(youth_rgbd_ctx* r, const uint8_t* d_in, int channels,
                            uint8_t* d_gray, uint32_t* d_photo, void* stream)
 {
     static const char* who = "youth_rgbd_prep_device";
-    if (!r || !d_in || (channels != 1 && channels != 3) || n < 0 || n > 65535)
-        return set_error(YOUTH_EINVAL, "%s: bad arguments (channels %d, %d frames)", who, channels,
-                         n);
+    if (!r || !d_in || (channels != 1 && channels != 3) || n < 0 || n > youth::kMaxFrames)
+        return g_icp_err.set(YOUTH_EINVAL, "%s: bad arguments (channels %d, %d frames)", who, channels,
+                             n);
     int rc = bind_device(r->icp);
     if (rc) return rc;
     return rgbd_launch_prep(pick_stream(r->icp, stream), d_in, channels, n, r->icp->W, r->icp->H,
@@ -557,12 +554,12 @@ int youth_rgbd_align_pairs_device(youth_rgbd_ctx* r, const int16_t* d_src_depth,
                                   float* d_T_out, void* stream)
 {
     static const char* who = "youth_rgbd_align_pairs_device";
-    if (!r) return set_error(YOUTH_EINVAL, "%s: null context", who);
+    if (!r) return g_icp_err.set(YOUTH_EINVAL, "%s: null context", who);
     if (!d_src_depth || !d_src_gray || !d_dst_depth || !d_dst_gray)
-        return set_error(YOUTH_EINVAL, "%s: null buffer", who);
+        return g_icp_err.set(YOUTH_EINVAL, "%s: null buffer", who);
     if (n_pairs <= 0 || n_pairs > r->frames - 1)
-        return set_error(YOUTH_EINVAL, "%s: %d pairs (need 1 .. max_frames = %d)", who, n_pairs,
-                         r->frames - 1);
+        return g_icp_err.set(YOUTH_EINVAL, "%s: %d pairs (need 1 .. max_frames = %d)", who, n_pairs,
+                             r->frames - 1);
     int rc = bind_device(r->icp);
     if (rc) return rc;
     return rgbd_align(r, pick_stream(r->icp, stream), d_src_depth, d_src_gray, d_dst_depth,
@@ -574,11 +571,11 @@ int youth_rgbd_align_sequence_device(youth_rgbd_ctx* r, const int16_t* d_depth,
                                      void* stream)
 {
     static const char* who = "youth_rgbd_align_sequence_device";
-    if (!r) return set_error(YOUTH_EINVAL, "%s: null context", who);
-    if (!d_depth || !d_gray) return set_error(YOUTH_EINVAL, "%s: null buffer", who);
+    if (!r) return g_icp_err.set(YOUTH_EINVAL, "%s: null context", who);
+    if (!d_depth || !d_gray) return g_icp_err.set(YOUTH_EINVAL, "%s: null buffer", who);
     if (n_frames < 2 || n_frames > r->frames)
-        return set_error(YOUTH_EINVAL, "%s: %d frames (need 2 .. max_frames + 1 = %d)", who,
-                         n_frames, r->frames);
+        return g_icp_err.set(YOUTH_EINVAL, "%s: %d frames (need 2 .. max_frames + 1 = %d)", who,
+                             n_frames, r->frames);
     int rc = bind_device(r->icp);
     if (rc) return rc;
     // every frame but the last is a target, prepped once; pair k: source frame
@@ -589,7 +586,7 @@ int youth_rgbd_align_sequence_device(youth_rgbd_ctx* r, const int16_t* d_depth,
 
 int youth_rgbd_sync(youth_rgbd_ctx* r, void* stream)
 {
-    if (!r) return set_error(YOUTH_EINVAL, "youth_rgbd_sync: null context");
+    if (!r) return g_icp_err.set(YOUTH_EINVAL, "youth_rgbd_sync: null context");
     int rc = bind_device(r->icp);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(pick_stream(r->icp, stream)));
@@ -599,7 +596,7 @@ int youth_rgbd_sync(youth_rgbd_ctx* r, void* stream)
 int youth_rgbd_get_poses(youth_rgbd_ctx* r, int n, double* T64, float* T32, int32_t* status)
 {
     if (!r || n < 0 || n > r->frames - 1)
-        return set_error(YOUTH_EINVAL, "youth_rgbd_get_poses: bad arguments (%d poses)", n);
+        return g_icp_err.set(YOUTH_EINVAL, "youth_rgbd_get_poses: bad arguments (%d poses)", n);
     youth_icp_ctx* c = r->icp;
     int rc = bind_device(c);
     if (rc) return rc;
@@ -628,8 +625,8 @@ int youth_rgbd_get_stats(youth_rgbd_ctx* r, int n, int iters, double* stats)
 {
     if (!r || !stats || n < 0 || n > r->last_pairs || iters != r->last_iters || iters < 1 ||
         iters > r->stats_iters)
-        return set_error(YOUTH_EINVAL, "youth_rgbd_get_stats: bad arguments (%d pairs, %d iterations)",
-                         n, iters);
+        return g_icp_err.set(YOUTH_EINVAL, "youth_rgbd_get_stats: bad arguments (%d pairs, %d iterations)",
+                             n, iters);
     int rc = bind_device(r->icp);
     if (rc) return rc;
     hipStream_t s = r->last_stream ? r->last_stream : r->icp->stream;
@@ -645,11 +642,11 @@ int youth_rgbd_reduce_host(youth_rgbd_ctx* r, const int16_t* src_depth, const ui
                            double* neq31)
 {
     static const char* who = "youth_rgbd_reduce_host";
-    if (!r) return set_error(YOUTH_EINVAL, "%s: null context", who);
+    if (!r) return g_icp_err.set(YOUTH_EINVAL, "%s: null context", who);
     if (!src_depth || !src_gray || !dst_depth || !dst_gray || !T12 || !neq31)
-        return set_error(YOUTH_EINVAL, "%s: null buffer", who);
+        return g_icp_err.set(YOUTH_EINVAL, "%s: null buffer", who);
     for (int i = 0; i < 12; ++i)
-        if (!std::isfinite(T12[i])) return set_error(YOUTH_EINVAL, "%s: non-finite pose", who);
+        if (!std::isfinite(T12[i])) return g_icp_err.set(YOUTH_EINVAL, "%s: non-finite pose", who);
     youth_icp_ctx* c = r->icp;
     int rc = bind_device(c);
     if (rc) return rc;
@@ -677,11 +674,11 @@ int youth_rgbd_track_host_sequence(youth_rgbd_ctx* r, const int16_t* depth, cons
                                    int n_frames, double* T_rel, int32_t* status)
 {
     static const char* who = "youth_rgbd_track_host_sequence";
-    if (!r) return set_error(YOUTH_EINVAL, "%s: null context", who);
-    if (!depth || !rgb || !T_rel) return set_error(YOUTH_EINVAL, "%s: null buffer", who);
+    if (!r) return g_icp_err.set(YOUTH_EINVAL, "%s: null context", who);
+    if (!depth || !rgb || !T_rel) return g_icp_err.set(YOUTH_EINVAL, "%s: null buffer", who);
     if (n_frames < 2 || n_frames > r->frames)
-        return set_error(YOUTH_EINVAL, "%s: %d frames (need 2 .. max_frames + 1 = %d)", who,
-                         n_frames, r->frames);
+        return g_icp_err.set(YOUTH_EINVAL, "%s: %d frames (need 2 .. max_frames + 1 = %d)", who,
+                             n_frames, r->frames);
     youth_icp_ctx* c = r->icp;
     int rc = bind_device(c);
     if (rc) return rc;

@@ -22,13 +22,11 @@
 // the C oracle (oracle_viewer_cloud).
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
 
 #include "cloud_backproject.h"
+#include "hip_host.h"
 #include "youth_viewer.h"
 
 namespace {
@@ -213,25 +211,9 @@ __global__ __launch_bounds__(kCloudThreads) void k_cloud_emit(
 
 // =============================================================== host side ==
 
-static thread_local std::string g_cloud_error;
-
-__attribute__((format(printf, 2, 3))) static int cloud_error(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_cloud_error = buf;
-    return code;
-}
-
-#define CLOUD_TRY(expr)                                                                   \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess)                                                             \
-            return cloud_error(YOUTH_EHIP, "%s (line %d)", hipGetErrorString(e_), __LINE__); \
-    } while (0)
+// The viewer cloud's channel (hip_host.h): youth_cloud_last_error reads it.
+static thread_local youth::ErrorText g_cloud_err;
+#define HIP_ERR g_cloud_err
 
 struct youth_cloud_ctx {
     int device = 0;
@@ -263,25 +245,16 @@ static void cloud_free(youth_cloud_ctx* c)
 
 extern "C" {
 
-const char* youth_cloud_last_error(void) { return g_cloud_error.c_str(); }
+const char* youth_cloud_last_error(void) { return g_cloud_err.c_str(); }
 
 youth_cloud_ctx* youth_cloud_create(int device, int W, int H, int max_frames)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        cloud_error(YOUTH_ENODEV, "youth_cloud_create: no HIP device visible");
-        return nullptr;
-    }
-    if (device < 0 || device >= ndev) {
-        cloud_error(YOUTH_EINVAL, "youth_cloud_create: device %d of %d", device, ndev);
-        return nullptr;
-    }
-    if (W < 1 || H < 1 || W > 16384 || H > 16384 || (long long)W * H > (1LL << 26) ||
-        max_frames < 1 || max_frames > 65535) {
-        cloud_error(YOUTH_EINVAL,
-                    "youth_cloud_create: %dx%d x %d frames (need 1 <= W,H <= 16384, W*H <= 2^26, "
-                    "1 <= frames <= 65535)",
-                    W, H, max_frames);
+    if (youth::check_device(g_cloud_err, "youth_cloud_create", device) < 0) return nullptr;
+    if (!youth::frame_size_ok(W, H, 1) || max_frames < 1 || max_frames > youth::kMaxFrames) {
+        g_cloud_err.set(YOUTH_EINVAL,
+                        "youth_cloud_create: %dx%d x %d frames (need 1 <= W,H <= 16384, W*H <= 2^26, "
+                        "1 <= frames <= 65535)",
+                        W, H, max_frames);
         return nullptr;
     }
     auto* c = new youth_cloud_ctx;
@@ -301,8 +274,8 @@ youth_cloud_ctx* youth_cloud_create(int device, int W, int H, int max_frames)
         hipMalloc(&c->d_rgb, (size_t)c->N * 3) != hipSuccess ||
         hipMalloc(&c->d_vert, (size_t)c->N * kVF * sizeof(float)) != hipSuccess ||
         hipMalloc(&c->d_count, sizeof(int32_t)) != hipSuccess) {
-        cloud_error(YOUTH_ENOMEM, "youth_cloud_create: device allocation failed (%dx%d x %d)", W,
-                    H, max_frames);
+        g_cloud_err.set(YOUTH_ENOMEM, "youth_cloud_create: device allocation failed (%dx%d x %d)", W,
+                        H, max_frames);
         cloud_free(c);
         return nullptr;
     }
@@ -325,19 +298,20 @@ int youth_cloud_build_device_posed(youth_cloud_ctx* c, const int16_t* d_depth,
                                    float* d_vertices, int32_t* d_counts, void* stream)
 {
     if (!c || !d_depth || !d_vertices || !d_counts)
-        return cloud_error(YOUTH_EINVAL, "youth_cloud_build_device: null argument");
+        return g_cloud_err.set(YOUTH_EINVAL, "youth_cloud_build_device: null argument");
     if (n_frames < 0 || n_frames > c->max_frames || W < 1 || H < 1 || W > c->W || H > c->H ||
         (long long)W * H > c->N)
-        return cloud_error(YOUTH_EINVAL,
-                           "youth_cloud_build_device: %d frames of %dx%d (context: %d of %dx%d)",
-                           n_frames, W, H, c->max_frames, c->W, c->H);
+        return g_cloud_err.set(YOUTH_EINVAL,
+                               "youth_cloud_build_device: %d frames of %dx%d (context: %d of %dx%d)",
+                               n_frames, W, H, c->max_frames, c->W, c->H);
     if (n_frames == 0) return YOUTH_OK;
-    CLOUD_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     const int N = W * H;
     const int tile_px = kCloudThreads * c->px;
     const int tiles = (N + tile_px - 1) / tile_px;
-    CloudK k{570.3f, 570.3f, (float)(W / 2), (float)(H / 2), 1000.0f};   // viewerModule.c:343-345
-    if (K) k = CloudK{K->fx, K->fy, K->cx, K->cy, K->depth_scale};
+    // the default: 570.3, 570.3, (float)(W / 2), (float)(H / 2), 1000 (viewerModule.c:343-345)
+    const youth_intrinsics Kd = K ? *K : youth_default_intrinsics(W, H);
+    const CloudK k{Kd.fx, Kd.fy, Kd.cx, Kd.cy, Kd.depth_scale};
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     // vector loads: every frame base and thread offset aligned for the
     // 2 px-byte depth word and the 3 px-byte colour words
@@ -354,12 +328,12 @@ int youth_cloud_build_device_posed(youth_cloud_ctx* c, const int16_t* d_depth,
     const dim3 grid(tiles, n_frames);
     hipLaunchKernelGGL(count_fn[pi][vec], grid, dim3(kCloudThreads), 0, s, d_depth, N, tiles,
                        c->d_tile_cnt);
-    CLOUD_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     k_cloud_scan<<<n_frames, kCloudThreads, 0, s>>>(c->d_tile_cnt, tiles, c->d_tile_off, d_counts);
-    CLOUD_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(emit_fn[pi][vec], grid, dim3(kCloudThreads), 0, s, d_depth,
                        d_rgb, W, N, tiles, k, (const int32_t*)c->d_tile_off, d_T_world, d_vertices);
-    CLOUD_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return YOUTH_OK;
 }
 
@@ -367,36 +341,36 @@ int youth_cloud_build_host(youth_cloud_ctx* c, const int16_t* depth, const uint8
                            int H, const youth_intrinsics* K, float* vertices, int cap)
 {
     if (!c || !depth || !vertices || cap < 0)
-        return cloud_error(YOUTH_EINVAL, "youth_cloud_build_host: null argument");
+        return g_cloud_err.set(YOUTH_EINVAL, "youth_cloud_build_host: null argument");
     if (W < 1 || H < 1 || W > c->W || H > c->H || (long long)W * H > c->N)
-        return cloud_error(YOUTH_EINVAL, "youth_cloud_build_host: %dx%d frame (context %dx%d)", W,
-                           H, c->W, c->H);
-    CLOUD_TRY(hipSetDevice(c->device));
+        return g_cloud_err.set(YOUTH_EINVAL, "youth_cloud_build_host: %dx%d frame (context %dx%d)", W,
+                               H, c->W, c->H);
+    HIP_TRY(hipSetDevice(c->device));
     const size_t N = (size_t)W * H;
-    CLOUD_TRY(hipMemcpyAsync(c->d_depth, depth, N * sizeof(int16_t), hipMemcpyHostToDevice,
-                             c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_depth, depth, N * sizeof(int16_t), hipMemcpyHostToDevice,
+                           c->stream));
     if (rgb)
-        CLOUD_TRY(hipMemcpyAsync(c->d_rgb, rgb, N * 3, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->d_rgb, rgb, N * 3, hipMemcpyHostToDevice, c->stream));
     const int rc = youth_cloud_build_device(c, c->d_depth, rgb ? c->d_rgb : nullptr, 1, W, H, K,
                                             c->d_vert, c->d_count, c->stream);
     if (rc < 0) return rc;
     int32_t n = 0;
-    CLOUD_TRY(hipMemcpyAsync(&n, c->d_count, sizeof(n), hipMemcpyDeviceToHost, c->stream));
-    CLOUD_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpyAsync(&n, c->d_count, sizeof(n), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     if (n > cap)
-        return cloud_error(YOUTH_EINVAL, "youth_cloud_build_host: %d vertices, room for %d", n,
-                           cap);
+        return g_cloud_err.set(YOUTH_EINVAL, "youth_cloud_build_host: %d vertices, room for %d", n,
+                               cap);
     if (n > 0)
-        CLOUD_TRY(hipMemcpy(vertices, c->d_vert, (size_t)n * kVF * sizeof(float),
-                            hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(vertices, c->d_vert, (size_t)n * kVF * sizeof(float),
+                          hipMemcpyDeviceToHost));
     return n;
 }
 
 int youth_cloud_sync(youth_cloud_ctx* c, void* stream)
 {
-    if (!c) return cloud_error(YOUTH_EINVAL, "youth_cloud_sync: null context");
-    CLOUD_TRY(hipSetDevice(c->device));
-    CLOUD_TRY(hipStreamSynchronize(stream ? (hipStream_t)stream : c->stream));
+    if (!c) return g_cloud_err.set(YOUTH_EINVAL, "youth_cloud_sync: null context");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(stream ? (hipStream_t)stream : c->stream));
     return YOUTH_OK;
 }
 

@@ -35,11 +35,9 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "cloud_backproject.h"
@@ -305,27 +303,7 @@ __global__ __launch_bounds__(kMapThreads) void k_map_extract(MapTable t, youth_v
 
 // =============================================================== host side ==
 
-static thread_local std::string g_map_error;
-
-// (map_table.h: map_render.hip reports its errors through the same text)
-int youth_map_set_error(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_map_error = buf;
-    return code;
-}
-#define map_error youth_map_set_error
-
-#define MAP_TRY(expr)                                                                    \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess)                                                            \
-            return map_error(YOUTH_EHIP, "%s (line %d)", hipGetErrorString(e_), __LINE__); \
-    } while (0)
+thread_local youth::ErrorText g_map_err;   // map_table.h
 
 struct youth_map {
     int device = 0;
@@ -345,7 +323,7 @@ struct youth_map {
     // rendering (map_render.hip): the z-buffer, all ones between renders
     bool render_queue = true;   // YOUTH_MAP_RENDER_QUEUE
     unsigned long long* d_zbuf = nullptr;
-    size_t zbuf_cap = 0;        // bytes
+    size_t zbuf_cap = 0;        // 64-bit values
 };
 
 static void map_free(youth_map* m)
@@ -369,49 +347,34 @@ static void map_free(youth_map* m)
 // stats (host order) after the map's stream has drained
 static int map_read_stats(youth_map* m, unsigned long long* st)
 {
-    MAP_TRY(hipSetDevice(m->device));
-    MAP_TRY(hipMemcpyAsync(st, m->t.stats, kStN * sizeof(unsigned long long),
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipMemcpyAsync(st, m->t.stats, kStN * sizeof(unsigned long long),
                            hipMemcpyDeviceToHost, m->stream));
-    MAP_TRY(hipStreamSynchronize(m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
     return YOUTH_OK;
 }
 
 // the host API's staging buffers, grown to N pixels
 static int map_stage(youth_map* m, size_t N, bool rgb)
 {
-    if (m->depth_cap < N || (rgb && m->rgb_cap < N)) {
-        MAP_TRY(hipStreamSynchronize(m->stream));
-        if (m->depth_cap < N) {
-            (void)hipFree(m->d_depth);
-            m->d_depth = nullptr;
-            m->depth_cap = 0;
-            MAP_TRY(hipMalloc(&m->d_depth, N * sizeof(int16_t)));
-            m->depth_cap = N;
-        }
-        if (rgb && m->rgb_cap < N) {
-            (void)hipFree(m->d_rgb);
-            m->d_rgb = nullptr;
-            m->rgb_cap = 0;
-            MAP_TRY(hipMalloc(&m->d_rgb, N * 3));
-            m->rgb_cap = N;
-        }
-    }
-    return YOUTH_OK;
+    if (m->depth_cap >= N && (!rgb || m->rgb_cap >= N)) return YOUTH_OK;
+    // no copy of an earlier call may still be in flight on the old buffers
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    const int rc = grow_device_buffer(g_map_err, &m->d_depth, &m->depth_cap, N);
+    if (rc < 0 || !rgb) return rc;
+    return grow_device_buffer(g_map_err, &m->d_rgb, &m->rgb_cap, N, 3);
 }
 
 // map_table.h: the renderer's door to a map
-int youth_map_render_acquire(youth_map* m, size_t zbuf_bytes, size_t stage_px, bool stage_rgb,
+int youth_map_render_acquire(youth_map* m, size_t zbuf_px, size_t stage_px, bool stage_rgb,
                              hipStream_t stream, youth_map_render_res* out)
 {
-    MAP_TRY(hipSetDevice(m->device));
-    if (m->zbuf_cap < zbuf_bytes) {
-        // no render may still be reading the old buffer: hipFree waits for the device
-        (void)hipFree(m->d_zbuf);
-        m->d_zbuf = nullptr;
-        m->zbuf_cap = 0;
-        MAP_TRY(hipMalloc(&m->d_zbuf, zbuf_bytes));
-        m->zbuf_cap = zbuf_bytes;
-        MAP_TRY(hipMemsetAsync(m->d_zbuf, 0xff, zbuf_bytes, stream ? stream : m->stream));
+    HIP_TRY(hipSetDevice(m->device));
+    if (m->zbuf_cap < zbuf_px) {
+        const int rc = grow_device_buffer(g_map_err, &m->d_zbuf, &m->zbuf_cap, zbuf_px);
+        if (rc < 0) return rc;
+        HIP_TRY(hipMemsetAsync(m->d_zbuf, 0xff, zbuf_px * sizeof(unsigned long long),
+                               stream ? stream : m->stream));
     }
     if (stage_px) {
         const int rs = map_stage(m, stage_px, stage_rgb);
@@ -438,26 +401,18 @@ static double voxel_axis(int32_t i, uint32_t sum_q, uint32_t count, float vpm)
 
 extern "C" {
 
-const char* youth_map_last_error(void) { return g_map_error.c_str(); }
+const char* youth_map_last_error(void) { return g_map_err.c_str(); }
 
 youth_map* youth_map_create(int device, float vpm, long long capacity_slots)
 {
     if (!std::isfinite(vpm) || !(vpm > 0.0f) || capacity_slots < 1 ||
         capacity_slots > (1LL << 28)) {
-        map_error(YOUTH_EINVAL,
-                  "youth_map_create: vpm %g, %lld slots (need finite vpm > 0, 1 <= slots <= 2^28)",
-                  (double)vpm, capacity_slots);
+        g_map_err.set(YOUTH_EINVAL,
+                      "youth_map_create: vpm %g, %lld slots (need finite vpm > 0, 1 <= slots <= 2^28)",
+                      (double)vpm, capacity_slots);
         return nullptr;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        map_error(YOUTH_ENODEV, "youth_map_create: no HIP device visible");
-        return nullptr;
-    }
-    if (device < 0 || device >= ndev) {
-        map_error(YOUTH_EINVAL, "youth_map_create: device %d of %d", device, ndev);
-        return nullptr;
-    }
+    if (youth::check_device(g_map_err, "youth_map_create", device) < 0) return nullptr;
     auto* m = new youth_map;
     m->device = device;
     m->vpm = vpm;
@@ -472,7 +427,7 @@ youth_map* youth_map_create(int device, float vpm, long long capacity_slots)
         hipMalloc(&m->t.vals, (size_t)m->cap * kValWords * sizeof(uint32_t)) != hipSuccess ||
         hipMalloc(&m->t.stats, kStN * sizeof(unsigned long long)) != hipSuccess ||
         hipMalloc(&m->d_T, 12 * sizeof(float)) != hipSuccess) {
-        map_error(YOUTH_ENOMEM, "youth_map_create: device allocation failed (%lld slots)", m->cap);
+        g_map_err.set(YOUTH_ENOMEM, "youth_map_create: device allocation failed (%lld slots)", m->cap);
         map_free(m);
         return nullptr;
     }
@@ -487,18 +442,18 @@ void youth_map_destroy(youth_map* m) { map_free(m); }
 
 int youth_map_clear(youth_map* m)
 {
-    if (!m) return map_error(YOUTH_EINVAL, "youth_map_clear: null map");
-    MAP_TRY(hipSetDevice(m->device));
-    MAP_TRY(hipMemsetAsync(m->t.keys, 0xff, (size_t)m->cap * sizeof(unsigned long long), m->stream));
-    MAP_TRY(hipMemsetAsync(m->t.vals, 0, (size_t)m->cap * kValWords * sizeof(uint32_t), m->stream));
-    MAP_TRY(hipMemsetAsync(m->t.stats, 0, kStN * sizeof(unsigned long long), m->stream));
+    if (!m) return g_map_err.set(YOUTH_EINVAL, "youth_map_clear: null map");
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipMemsetAsync(m->t.keys, 0xff, (size_t)m->cap * sizeof(unsigned long long), m->stream));
+    HIP_TRY(hipMemsetAsync(m->t.vals, 0, (size_t)m->cap * kValWords * sizeof(uint32_t), m->stream));
+    HIP_TRY(hipMemsetAsync(m->t.stats, 0, kStN * sizeof(unsigned long long), m->stream));
     return YOUTH_OK;
 }
 
 int youth_map_set_max_depth(youth_map* m, int max_depth)
 {
     if (!m || max_depth < 0)
-        return map_error(YOUTH_EINVAL, "youth_map_set_max_depth: null map or negative depth");
+        return g_map_err.set(YOUTH_EINVAL, "youth_map_set_max_depth: null map or negative depth");
     m->max_depth = max_depth;
     return YOUTH_OK;
 }
@@ -507,20 +462,20 @@ int youth_map_integrate_device(youth_map* m, const int16_t* d_depth, const uint8
                                int n_frames, int W, int H, const youth_intrinsics* K,
                                const float* d_T_world, void* stream)
 {
-    if (!m || !d_depth) return map_error(YOUTH_EINVAL, "youth_map_integrate_device: null argument");
-    if (n_frames < 0 || n_frames > 65535 || W < 1 || H < 1 || W > 16384 || H > 16384 ||
-        (long long)W * H > (1LL << 26))
-        return map_error(YOUTH_EINVAL,
-                         "youth_map_integrate_device: %d frames of %dx%d (need 0 <= frames <= 65535, "
-                         "1 <= W,H <= 16384, W*H <= 2^26)",
-                         n_frames, W, H);
+    if (!m || !d_depth) return g_map_err.set(YOUTH_EINVAL, "youth_map_integrate_device: null argument");
+    if (n_frames < 0 || n_frames > youth::kMaxFrames || !youth::frame_size_ok(W, H, 1))
+        return g_map_err.set(YOUTH_EINVAL,
+                             "youth_map_integrate_device: %d frames of %dx%d (need 0 <= frames <= 65535, "
+                             "1 <= W,H <= 16384, W*H <= 2^26)",
+                             n_frames, W, H);
     if (n_frames == 0) return YOUTH_OK;
-    MAP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipSetDevice(m->device));
     const int N = W * H;
     const int tile_px = kMapThreads * kMapPx;
     const int tiles = (N + tile_px - 1) / tile_px;
-    CloudK k{570.3f, 570.3f, (float)(W / 2), (float)(H / 2), 1000.0f};   // the viewer's default
-    if (K) k = CloudK{K->fx, K->fy, K->cx, K->cy, K->depth_scale};
+    // the viewer's default: 570.3, 570.3, (float)(W / 2), (float)(H / 2), 1000
+    const youth_intrinsics Kd = K ? *K : youth_default_intrinsics(W, H);
+    const CloudK k{Kd.fx, Kd.fy, Kd.cx, Kd.cy, Kd.depth_scale};
     hipStream_t s = stream ? (hipStream_t)stream : m->stream;
     // vector loads: every frame base and thread offset aligned for the 16-byte
     // depth word and the 8-byte colour words (as k_cloud_emit)
@@ -535,43 +490,43 @@ int youth_map_integrate_device(youth_map* m, const int16_t* d_depth, const uint8
          {k_map_integrate<true, true, false>, k_map_integrate<true, true, true>}}};
     hipLaunchKernelGGL(fn[vec][m->lds][d_rgb != nullptr], dim3(tiles, n_frames), dim3(kMapThreads),
                        0, s, d_depth, d_rgb, W, N, k, d_T_world, m->vpm, m->max_depth, m->t);
-    MAP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return YOUTH_OK;
 }
 
 int youth_map_integrate_host(youth_map* m, const int16_t* depth, const uint8_t* rgb, int W, int H,
                              const youth_intrinsics* K, const double* T_world)
 {
-    if (!m || !depth) return map_error(YOUTH_EINVAL, "youth_map_integrate_host: null argument");
-    if (W < 1 || H < 1 || W > 16384 || H > 16384 || (long long)W * H > (1LL << 26))
-        return map_error(YOUTH_EINVAL, "youth_map_integrate_host: %dx%d frame", W, H);
+    if (!m || !depth) return g_map_err.set(YOUTH_EINVAL, "youth_map_integrate_host: null argument");
+    if (!youth::frame_size_ok(W, H, 1))
+        return g_map_err.set(YOUTH_EINVAL, "youth_map_integrate_host: %dx%d frame", W, H);
     float T32[12];
     if (T_world) {
         for (int q = 0; q < 12; ++q) {
             T32[q] = (float)T_world[q];
             if (!std::isfinite(T_world[q]) || !std::isfinite(T32[q]))
-                return map_error(YOUTH_EINVAL, "youth_map_integrate_host: pose entry %d is not finite", q);
+                return g_map_err.set(YOUTH_EINVAL, "youth_map_integrate_host: pose entry %d is not finite", q);
         }
     }
-    MAP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipSetDevice(m->device));
     const size_t N = (size_t)W * H;
     const int rs = map_stage(m, N, rgb != nullptr);
     if (rs < 0) return rs;
-    MAP_TRY(hipMemcpyAsync(m->d_depth, depth, N * sizeof(int16_t), hipMemcpyHostToDevice, m->stream));
-    if (rgb) MAP_TRY(hipMemcpyAsync(m->d_rgb, rgb, N * 3, hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(hipMemcpyAsync(m->d_depth, depth, N * sizeof(int16_t), hipMemcpyHostToDevice, m->stream));
+    if (rgb) HIP_TRY(hipMemcpyAsync(m->d_rgb, rgb, N * 3, hipMemcpyHostToDevice, m->stream));
     if (T_world)
-        MAP_TRY(hipMemcpyAsync(m->d_T, T32, sizeof(T32), hipMemcpyHostToDevice, m->stream));
+        HIP_TRY(hipMemcpyAsync(m->d_T, T32, sizeof(T32), hipMemcpyHostToDevice, m->stream));
     const int rc = youth_map_integrate_device(m, m->d_depth, rgb ? m->d_rgb : nullptr, 1, W, H, K,
                                               T_world ? m->d_T : nullptr, m->stream);
     if (rc < 0) return rc;
     // the staging buffers and the caller's frame are free again on return
-    MAP_TRY(hipStreamSynchronize(m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
     return YOUTH_OK;
 }
 
 long long youth_map_voxels(youth_map* m)
 {
-    if (!m) return map_error(YOUTH_EINVAL, "youth_map_voxels: null map");
+    if (!m) return g_map_err.set(YOUTH_EINVAL, "youth_map_voxels: null map");
     unsigned long long st[kStN];
     const int rc = map_read_stats(m, st);
     return rc < 0 ? rc : (long long)st[kStOccupied];
@@ -579,7 +534,7 @@ long long youth_map_voxels(youth_map* m)
 
 int youth_map_stats(youth_map* m, struct youth_map_stats* out)
 {
-    if (!m || !out) return map_error(YOUTH_EINVAL, "youth_map_stats: null argument");
+    if (!m || !out) return g_map_err.set(YOUTH_EINVAL, "youth_map_stats: null argument");
     unsigned long long st[kStN];
     const int rc = map_read_stats(m, st);
     if (rc < 0) return rc;
@@ -595,27 +550,22 @@ int youth_map_stats(youth_map* m, struct youth_map_stats* out)
 int youth_map_extract(youth_map* m, youth_voxel* out, int cap)
 {
     if (!m || cap < 0 || (!out && cap > 0))
-        return map_error(YOUTH_EINVAL, "youth_map_extract: null argument");
+        return g_map_err.set(YOUTH_EINVAL, "youth_map_extract: null argument");
     unsigned long long st[kStN];
     int rc = map_read_stats(m, st);
     if (rc < 0) return rc;
     const size_t n = (size_t)st[kStOccupied];
     if (n > (size_t)cap)
-        return map_error(YOUTH_EINVAL, "youth_map_extract: %zu voxels, room for %d", n, cap);
+        return g_map_err.set(YOUTH_EINVAL, "youth_map_extract: %zu voxels, room for %d", n, cap);
     if (n == 0) return 0;
-    if (m->rec_cap < n) {
-        (void)hipFree(m->d_rec);
-        m->d_rec = nullptr;
-        m->rec_cap = 0;
-        MAP_TRY(hipMalloc(&m->d_rec, n * sizeof(youth_voxel)));
-        m->rec_cap = n;
-    }
-    MAP_TRY(hipMemsetAsync(m->t.stats + kStExtracted, 0, sizeof(unsigned long long), m->stream));
+    rc = grow_device_buffer(g_map_err, &m->d_rec, &m->rec_cap, n);
+    if (rc < 0) return rc;
+    HIP_TRY(hipMemsetAsync(m->t.stats + kStExtracted, 0, sizeof(unsigned long long), m->stream));
     const unsigned blocks = (unsigned)((m->cap + kMapThreads - 1) / kMapThreads);
     k_map_extract<<<blocks, kMapThreads, 0, m->stream>>>(m->t, m->d_rec, (uint32_t)n);
-    MAP_TRY(hipGetLastError());
-    MAP_TRY(hipMemcpyAsync(out, m->d_rec, n * sizeof(youth_voxel), hipMemcpyDeviceToHost, m->stream));
-    MAP_TRY(hipStreamSynchronize(m->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, m->d_rec, n * sizeof(youth_voxel), hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
     // the slot order depends on which wave won an insert: never leaves here
     std::sort(out, out + n, [](const youth_voxel& a, const youth_voxel& b) {
         if (a.iz != b.iz) return a.iz < b.iz;
@@ -627,19 +577,19 @@ int youth_map_extract(youth_map* m, youth_voxel* out, int cap)
 
 int youth_map_sync(youth_map* m, void* stream)
 {
-    if (!m) return map_error(YOUTH_EINVAL, "youth_map_sync: null map");
-    MAP_TRY(hipSetDevice(m->device));
-    MAP_TRY(hipStreamSynchronize(stream ? (hipStream_t)stream : m->stream));
+    if (!m) return g_map_err.set(YOUTH_EINVAL, "youth_map_sync: null map");
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipStreamSynchronize(stream ? (hipStream_t)stream : m->stream));
     return YOUTH_OK;
 }
 
 int youth_map_points(const youth_voxel* vox, int n, float vpm, float* xyzrgb)
 {
     if (n < 0 || (n > 0 && (!vox || !xyzrgb)) || !std::isfinite(vpm) || !(vpm > 0.0f))
-        return map_error(YOUTH_EINVAL, "youth_map_points: bad argument");
+        return g_map_err.set(YOUTH_EINVAL, "youth_map_points: bad argument");
     for (int k = 0; k < n; ++k) {
         const youth_voxel& r = vox[k];
-        if (r.count == 0) return map_error(YOUTH_EINVAL, "youth_map_points: record %d is empty", k);
+        if (r.count == 0) return g_map_err.set(YOUTH_EINVAL, "youth_map_points: record %d is empty", k);
         float* o = xyzrgb + (size_t)k * 6;
         o[0] = (float)voxel_axis(r.ix, r.sum_q[0], r.count, vpm);
         o[1] = (float)voxel_axis(r.iy, r.sum_q[1], r.count, vpm);
@@ -652,12 +602,12 @@ int youth_map_points(const youth_voxel* vox, int n, float vpm, float* xyzrgb)
 int youth_map_write_ply(const char* path, const youth_voxel* vox, int n, float vpm)
 {
     if (!path || n < 0 || (n > 0 && !vox) || !std::isfinite(vpm) || !(vpm > 0.0f))
-        return map_error(YOUTH_EINVAL, "youth_map_write_ply: bad argument");
+        return g_map_err.set(YOUTH_EINVAL, "youth_map_write_ply: bad argument");
     for (int k = 0; k < n; ++k)
         if (vox[k].count == 0)
-            return map_error(YOUTH_EINVAL, "youth_map_write_ply: record %d is empty", k);
+            return g_map_err.set(YOUTH_EINVAL, "youth_map_write_ply: record %d is empty", k);
     FILE* f = fopen(path, "w");
-    if (!f) return map_error(YOUTH_EINVAL, "youth_map_write_ply: cannot open %s", path);
+    if (!f) return g_map_err.set(YOUTH_EINVAL, "youth_map_write_ply: cannot open %s", path);
     fprintf(f,
             "ply\nformat ascii 1.0\ncomment youth_map voxels_per_metre %.9g\n"
             "element vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
@@ -676,7 +626,7 @@ int youth_map_write_ply(const char* path, const youth_voxel* vox, int n, float v
                 r.count);
     }
     const int ok = ferror(f) == 0;
-    if (fclose(f) != 0 || !ok) return map_error(YOUTH_EINVAL, "youth_map_write_ply: write to %s failed", path);
+    if (fclose(f) != 0 || !ok) return g_map_err.set(YOUTH_EINVAL, "youth_map_write_ply: write to %s failed", path);
     return YOUTH_OK;
 }
 

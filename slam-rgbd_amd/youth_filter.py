@@ -18,36 +18,27 @@ from ctypes import POINTER, c_char_p, c_int, c_int16, c_void_p
 import numpy as np
 
 import youth_icp
-from youth_icp import FilterParams, IcpError
+from youth_icp import FilterParams
 
 HEADER_PATH = os.path.join(os.path.dirname(youth_icp.HERE), "include", "youth_filter.h")
 
-_bound = False
+_PP = POINTER(FilterParams)
+_SIGS = {
+    "youth_depth_filter_default_params": (FilterParams, []),
+    "youth_depth_filter_device": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, _PP,
+                                          c_void_p]),
+    "youth_depth_filter_host": (c_int, [c_int, POINTER(c_int16), POINTER(c_int16), c_int, c_int,
+                                        c_int, _PP]),
+    "youth_depth_filter_last_error": (c_char_p, []),
+}
 
 
 def load_library() -> ctypes.CDLL:
-    global _bound
-    lib = youth_icp.load_library()
-    if not _bound:
-        PP = POINTER(FilterParams)
-        lib.youth_depth_filter_default_params.restype = FilterParams
-        lib.youth_depth_filter_default_params.argtypes = []
-        lib.youth_depth_filter_device.restype = c_int
-        lib.youth_depth_filter_device.argtypes = [c_int, c_void_p, c_void_p, c_int, c_int, c_int,
-                                                  PP, c_void_p]
-        lib.youth_depth_filter_host.restype = c_int
-        lib.youth_depth_filter_host.argtypes = [c_int, POINTER(c_int16), POINTER(c_int16), c_int,
-                                                c_int, c_int, PP]
-        lib.youth_depth_filter_last_error.restype = c_char_p
-        lib.youth_depth_filter_last_error.argtypes = []
-        _bound = True
-    return lib
+    return youth_icp.bind(youth_icp.load_library(), _SIGS)
 
 
 def _check(lib, code: int) -> int:
-    if code < 0:
-        raise IcpError(code, (lib.youth_depth_filter_last_error() or b"").decode())
-    return code
+    return youth_icp.check(code, lib.youth_depth_filter_last_error)
 
 
 def default_params() -> tuple[int, int]:

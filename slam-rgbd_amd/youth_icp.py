@@ -76,6 +76,34 @@ class FilterParams(ctypes.Structure):
 
 
 _lib = None
+_bound: list[dict] = []   # the tables bind() has done
+
+
+def bind(lib: ctypes.CDLL, sigs: dict) -> ctypes.CDLL:
+    """Set restype and argtypes of lib's functions from a module's table
+    {name: (restype, argtypes)}, once per table; returns lib.  Under
+    YOUTH_ICP_LIB (tools/ab_*.sh: older builds) a missing name is skipped."""
+    if any(s is sigs for s in _bound):
+        return lib
+    ab_build = bool(os.environ.get("YOUTH_ICP_LIB"))
+    for name, (res, args) in sigs.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            if ab_build:
+                continue
+            raise
+        fn.restype = res
+        fn.argtypes = args
+    _bound.append(sigs)
+    return lib
+
+
+def check(code: int, last_error_fn) -> int:
+    """A negative code raises IcpError with the module's last error text."""
+    if code < 0:
+        raise IcpError(code, (last_error_fn() or b"").decode())
+    return code
 
 
 def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
@@ -183,17 +211,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "youth_slam_get_status": (c_int, [c_int, PI32, POINTER(ctypes.c_longlong),
                                           POINTER(ctypes.c_longlong)]),
     }
-    ab_build = bool(os.environ.get("YOUTH_ICP_LIB"))  # tools/ab_*.sh: older builds
-    for name, (res, args) in sig.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            if ab_build:
-                continue
-            raise
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
+    _lib = bind(lib, sig)
     return lib
 
 
@@ -213,20 +231,13 @@ def _p(arr, ctype):
     return None if arr is None else arr.ctypes.data_as(POINTER(ctype))
 
 
-def _err(code: int) -> IcpError:
-    lib = load_library()
-    return IcpError(code, (lib.youth_icp_last_error() or b"").decode())
-
-
 TRACK_MAX_IN_FLIGHT = 16  # YOUTH_TRACK_MAX_IN_FLIGHT (include/youth_icp.h)
 TRACK_MAX_BATCH = 8       # YOUTH_TRACK_MAX_BATCH
 MAX_CONCURRENCY = 4       # YOUTH_ICP_MAX_CONCURRENCY
 
 
 def _check(code: int) -> int:
-    if code < 0:
-        raise _err(code)
-    return code
+    return check(code, load_library().youth_icp_last_error)
 
 
 def default_intrinsics(width: int, height: int) -> Intrinsics:

@@ -44,69 +44,43 @@ class MapView(ctypes.Structure):
     _fields_ = [("W", c_int), ("H", c_int), ("max_splat", c_int), ("min_count", c_uint32)]
 
 
-_bound = False
+_PI, _PV = POINTER(Intrinsics), POINTER(MapView)
+_SIGS = {
+    "youth_map_create": (c_void_p, [c_int, c_float, c_longlong]),
+    "youth_map_destroy": (None, [c_void_p]),
+    "youth_map_last_error": (c_char_p, []),
+    "youth_map_clear": (c_int, [c_void_p]),
+    "youth_map_set_max_depth": (c_int, [c_void_p, c_int]),
+    "youth_map_integrate_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, _PI,
+                                           c_void_p, c_void_p]),
+    "youth_map_integrate_host": (c_int, [c_void_p, POINTER(c_int16), POINTER(c_uint8), c_int,
+                                         c_int, _PI, POINTER(c_double)]),
+    "youth_map_voxels": (c_longlong, [c_void_p]),
+    "youth_map_extract": (c_int, [c_void_p, c_void_p, c_int]),
+    "youth_map_stats": (c_int, [c_void_p, POINTER(MapStats)]),
+    "youth_map_sync": (c_int, [c_void_p, c_void_p]),
+    "youth_map_points": (c_int, [c_void_p, c_int, c_float, POINTER(c_float)]),
+    "youth_map_write_ply": (c_int, [c_char_p, c_void_p, c_int, c_float]),
+    "youth_slam_map_voxels": (c_longlong, []),
+    "youth_slam_map_extract": (c_int, [c_void_p, c_int]),
+    "youth_slam_map_vpm": (c_float, []),
+    # youth_map_render.h
+    "youth_map_view_from_pose": (c_int, [POINTER(c_double), POINTER(c_float)]),
+    "youth_map_render_device": (c_int, [c_void_p, c_int, _PV, _PI, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
+    "youth_map_render_host": (c_int, [c_void_p, _PV, _PI, POINTER(c_double), POINTER(c_int16),
+                                      POINTER(c_uint8)]),
+    "youth_slam_map_render": (c_int, [_PV, _PI, POINTER(c_double), POINTER(c_int16),
+                                      POINTER(c_uint8)]),
+}
 
 
 def load_library() -> ctypes.CDLL:
-    global _bound
-    lib = youth_icp.load_library()
-    if not _bound:
-        PI = POINTER(Intrinsics)
-        lib.youth_map_create.restype = c_void_p
-        lib.youth_map_create.argtypes = [c_int, c_float, c_longlong]
-        lib.youth_map_destroy.restype = None
-        lib.youth_map_destroy.argtypes = [c_void_p]
-        lib.youth_map_last_error.restype = c_char_p
-        lib.youth_map_last_error.argtypes = []
-        lib.youth_map_clear.restype = c_int
-        lib.youth_map_clear.argtypes = [c_void_p]
-        lib.youth_map_set_max_depth.restype = c_int
-        lib.youth_map_set_max_depth.argtypes = [c_void_p, c_int]
-        lib.youth_map_integrate_device.restype = c_int
-        lib.youth_map_integrate_device.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                                   c_int, PI, c_void_p, c_void_p]
-        lib.youth_map_integrate_host.restype = c_int
-        lib.youth_map_integrate_host.argtypes = [c_void_p, POINTER(c_int16), POINTER(c_uint8),
-                                                 c_int, c_int, PI, POINTER(c_double)]
-        lib.youth_map_voxels.restype = c_longlong
-        lib.youth_map_voxels.argtypes = [c_void_p]
-        lib.youth_map_extract.restype = c_int
-        lib.youth_map_extract.argtypes = [c_void_p, c_void_p, c_int]
-        lib.youth_map_stats.restype = c_int
-        lib.youth_map_stats.argtypes = [c_void_p, POINTER(MapStats)]
-        lib.youth_map_sync.restype = c_int
-        lib.youth_map_sync.argtypes = [c_void_p, c_void_p]
-        lib.youth_map_points.restype = c_int
-        lib.youth_map_points.argtypes = [c_void_p, c_int, c_float, POINTER(c_float)]
-        lib.youth_map_write_ply.restype = c_int
-        lib.youth_map_write_ply.argtypes = [c_char_p, c_void_p, c_int, c_float]
-        lib.youth_slam_map_voxels.restype = c_longlong
-        lib.youth_slam_map_voxels.argtypes = []
-        lib.youth_slam_map_extract.restype = c_int
-        lib.youth_slam_map_extract.argtypes = [c_void_p, c_int]
-        lib.youth_slam_map_vpm.restype = c_float
-        lib.youth_slam_map_vpm.argtypes = []
-        # youth_map_render.h
-        PV = POINTER(MapView)
-        lib.youth_map_view_from_pose.restype = c_int
-        lib.youth_map_view_from_pose.argtypes = [POINTER(c_double), POINTER(c_float)]
-        lib.youth_map_render_device.restype = c_int
-        lib.youth_map_render_device.argtypes = [c_void_p, c_int, PV, PI, c_void_p, c_void_p,
-                                                c_void_p, c_void_p]
-        lib.youth_map_render_host.restype = c_int
-        lib.youth_map_render_host.argtypes = [c_void_p, PV, PI, POINTER(c_double),
-                                              POINTER(c_int16), POINTER(c_uint8)]
-        lib.youth_slam_map_render.restype = c_int
-        lib.youth_slam_map_render.argtypes = [PV, PI, POINTER(c_double), POINTER(c_int16),
-                                              POINTER(c_uint8)]
-        _bound = True
-    return lib
+    return youth_icp.bind(youth_icp.load_library(), _SIGS)
 
 
 def _check(lib, code: int) -> int:
-    if code < 0:
-        raise IcpError(code, (lib.youth_map_last_error() or b"").decode())
-    return code
+    return youth_icp.check(code, lib.youth_map_last_error)
 
 
 def _records(voxels: np.ndarray) -> np.ndarray:

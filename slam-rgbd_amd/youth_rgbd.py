@@ -27,45 +27,36 @@ class RgbdParams(ctypes.Structure):
     _fields_ = [("iters", c_int), ("dist_thresh", c_float), ("lam", c_float)]
 
 
-_bound = False
+_PD = POINTER(c_double)
+_SIGS = {
+    "youth_rgbd_default_params": (RgbdParams, []),
+    "youth_rgbd_last_error": (c_char_p, []),
+    "youth_rgbd_create": (c_void_p, [c_int, c_int, c_int, c_int, POINTER(Intrinsics),
+                                     POINTER(RgbdParams)]),
+    "youth_rgbd_destroy": (None, [c_void_p]),
+    "youth_rgbd_luma_device": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                       c_void_p]),
+    "youth_rgbd_align_pairs_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_int, _PD, c_void_p, c_void_p]),
+    "youth_rgbd_align_sequence_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int,
+                                                 c_void_p, c_void_p]),
+    "youth_rgbd_sync": (c_int, [c_void_p, c_void_p]),
+    "youth_rgbd_get_poses": (c_int, [c_void_p, c_int, _PD, POINTER(c_float),
+                                     POINTER(c_int32)]),
+    "youth_rgbd_get_stats": (c_int, [c_void_p, c_int, c_int, _PD]),
+    "youth_rgbd_prep_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                       c_void_p, c_void_p]),
+    "youth_rgbd_reduce_host": (c_int, [c_void_p, POINTER(c_int16), POINTER(c_uint8),
+                                       POINTER(c_int16), POINTER(c_uint8),
+                                       POINTER(c_float), _PD]),
+    "youth_rgbd_track_host_sequence": (c_int, [c_void_p, POINTER(c_int16),
+                                               POINTER(c_uint8), c_int, _PD,
+                                               POINTER(c_int32)]),
+}
 
 
 def load_library() -> ctypes.CDLL:
-    global _bound
-    lib = youth_icp.load_library()
-    if not _bound:
-        PD = POINTER(c_double)
-        sigs = {
-            "youth_rgbd_default_params": (RgbdParams, []),
-            "youth_rgbd_last_error": (c_char_p, []),
-            "youth_rgbd_create": (c_void_p, [c_int, c_int, c_int, c_int, POINTER(Intrinsics),
-                                             POINTER(RgbdParams)]),
-            "youth_rgbd_destroy": (None, [c_void_p]),
-            "youth_rgbd_luma_device": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int,
-                                               c_void_p]),
-            "youth_rgbd_align_pairs_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p,
-                                                      c_void_p, c_int, PD, c_void_p, c_void_p]),
-            "youth_rgbd_align_sequence_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int,
-                                                         c_void_p, c_void_p]),
-            "youth_rgbd_sync": (c_int, [c_void_p, c_void_p]),
-            "youth_rgbd_get_poses": (c_int, [c_void_p, c_int, PD, POINTER(c_float),
-                                             POINTER(c_int32)]),
-            "youth_rgbd_get_stats": (c_int, [c_void_p, c_int, c_int, PD]),
-            "youth_rgbd_prep_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p,
-                                               c_void_p, c_void_p]),
-            "youth_rgbd_reduce_host": (c_int, [c_void_p, POINTER(c_int16), POINTER(c_uint8),
-                                               POINTER(c_int16), POINTER(c_uint8),
-                                               POINTER(c_float), PD]),
-            "youth_rgbd_track_host_sequence": (c_int, [c_void_p, POINTER(c_int16),
-                                                       POINTER(c_uint8), c_int, PD,
-                                                       POINTER(c_int32)]),
-        }
-        for name, (res, args) in sigs.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _bound = True
-    return lib
+    return youth_icp.bind(youth_icp.load_library(), _SIGS)
 
 
 def _last_error(lib) -> str:
@@ -73,9 +64,7 @@ def _last_error(lib) -> str:
 
 
 def _check(lib, code: int) -> int:
-    if code < 0:
-        raise IcpError(code, _last_error(lib))
-    return code
+    return youth_icp.check(code, lib.youth_rgbd_last_error)
 
 
 def default_params() -> tuple[int, float, float]:

@@ -24,40 +24,27 @@ from youth_icp import YOUTH_EHIP, YOUTH_ENODEV, IcpError, Intrinsics
 HEADER_PATH = os.path.join(os.path.dirname(youth_icp.HERE), "include", "youth_viewer.h")
 FLOATS_PER_VERTEX = 6
 
-_bound = False
+_PI = POINTER(Intrinsics)
+_SIGS = {
+    "youth_cloud_create": (c_void_p, [c_int, c_int, c_int, c_int]),
+    "youth_cloud_destroy": (None, [c_void_p]),
+    "youth_cloud_last_error": (c_char_p, []),
+    "youth_cloud_build_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, _PI,
+                                         c_void_p, c_void_p, c_void_p]),
+    "youth_cloud_build_device_posed": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                               _PI, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "youth_cloud_build_host": (c_int, [c_void_p, POINTER(c_int16), POINTER(c_uint8), c_int, c_int,
+                                       _PI, POINTER(ctypes.c_float), c_int]),
+    "youth_cloud_sync": (c_int, [c_void_p, c_void_p]),
+}
 
 
 def load_library() -> ctypes.CDLL:
-    global _bound
-    lib = youth_icp.load_library()
-    if not _bound:
-        PI = POINTER(Intrinsics)
-        lib.youth_cloud_create.restype = c_void_p
-        lib.youth_cloud_create.argtypes = [c_int, c_int, c_int, c_int]
-        lib.youth_cloud_destroy.restype = None
-        lib.youth_cloud_destroy.argtypes = [c_void_p]
-        lib.youth_cloud_last_error.restype = c_char_p
-        lib.youth_cloud_last_error.argtypes = []
-        lib.youth_cloud_build_device.restype = c_int
-        lib.youth_cloud_build_device.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                                 PI, c_void_p, c_void_p, c_void_p]
-        lib.youth_cloud_build_device_posed.restype = c_int
-        lib.youth_cloud_build_device_posed.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                                       c_int, PI, c_void_p, c_void_p, c_void_p,
-                                                       c_void_p]
-        lib.youth_cloud_build_host.restype = c_int
-        lib.youth_cloud_build_host.argtypes = [c_void_p, POINTER(c_int16), POINTER(c_uint8), c_int,
-                                               c_int, PI, POINTER(ctypes.c_float), c_int]
-        lib.youth_cloud_sync.restype = c_int
-        lib.youth_cloud_sync.argtypes = [c_void_p, c_void_p]
-        _bound = True
-    return lib
+    return youth_icp.bind(youth_icp.load_library(), _SIGS)
 
 
 def _check(lib, code: int) -> int:
-    if code < 0:
-        raise IcpError(code, (lib.youth_cloud_last_error() or b"").decode())
-    return code
+    return youth_icp.check(code, lib.youth_cloud_last_error)
 
 
 class CloudBuilder:

@@ -66,6 +66,26 @@ def test_one_frame_identity_pose_colour():
     assert st["capacity"] == 1 << 20
 
 
+def test_host_staging_and_extract_buffer_grow_and_are_reused():
+    """youth_map_integrate_host's depth and colour staging grow separately (4x3
+    depth only, then 9x7 with colour) and a smaller frame reuses the larger
+    buffers (4x3 with colour); youth_map_extract's record buffer grows between
+    the two extracts."""
+    frames = [(_frame(4, 3, 1)[0], None, None, None), _frame(9, 7, 2) + (None, None),
+              _frame(4, 3, 3) + (None, None)]
+    with youth_map.VoxelMap(100.0, slots=4096) as m:
+        m.integrate(frames[0][0])
+        first = m.extract()
+        m.integrate(*frames[1][:2])
+        second = m.extract()
+        m.integrate(*frames[2][:2])
+        third, st = m.extract(), m.stats()
+    for got, k in ((first, 1), (second, 2), (third, 3)):
+        _same(got, restate_frames(frames[:k], 100.0)[0])
+    assert 0 < first.shape[0] < second.shape[0] < third.shape[0]
+    assert st["dropped"] == 0 and st["out_of_range"] == 0
+
+
 # -------------------------------------------- 2 many frames, every octant --
 def _device_batch(frames, offset=0):
     n, (H, W) = len(frames), frames[0][0].shape

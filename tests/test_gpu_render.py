@@ -137,6 +137,22 @@ def test_hand_made_scene():
         assert areas[0] > areas[1] > areas[2] > 0
 
 
+def test_zbuffer_and_staging_grow_and_are_reused():
+    """youth_map_render_host at 4x4 (depth only), 16x8 with colour, 4x4 with
+    colour on one map: the z-buffer grows and its new words must read all ones,
+    the colour staging grows on its own, and the smaller view then runs on the
+    larger buffers."""
+    with youth_map.VoxelMap(HAND_VPM, slots=1024) as m:
+        for d, c, K, T in hand_frames():
+            m.integrate(d, c, K, T)
+        rec = m.extract()
+        for W, H, rgb in ((4, 4, False), (16, 8, True), (4, 4, True)):
+            K = youth_icp.Intrinsics(float(W), float(W), W / 2.0, H / 2.0, 1000.0)
+            want = render(rec, HAND_VPM, view_from_pose(np.eye(4)), K, W, H)
+            assert (want[0] > 0).sum() > W * H // 4
+            _same(m.render(np.eye(4), W, H, K, want_rgb=rgb), want)
+
+
 # ---------------------------------------------------- 2 random colour frames --
 def _random_map(m, W, H, n=3, seed=0):
     rng = np.random.default_rng(seed)

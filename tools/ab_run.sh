@@ -2,9 +2,11 @@
 # Interleaved A/B of tools/ab/<lib>/libyouth_icp.so builds on one box.
 # Usage: tools/ab_run.sh <rounds> <spec>... ; a spec is <lib> or
 # <label>=<lib>[,VAR=value...] (environment for that run only, e.g.
-# nofuse=cur,YOUTH_ICP_FUSED_PREP=0).  env EXTRA passes bench flags.
+# nofuse=cur,YOUTH_ICP_FUSED_PREP=0).  env EXTRA passes bench flags; env HOST_IO=1
+# keeps the host_io leg (a change of the host side).
 set -euo pipefail
 R=$1; shift
+HOSTIO=--no-host-io; [ -n "${HOST_IO:-}" ] && HOSTIO=
 mkdir -p gpurun_out/ab
 for r in $(seq 1 $R); do
   for spec in "$@"; do
@@ -14,7 +16,7 @@ for r in $(seq 1 $R); do
     envargs=()
     if [ -n "${envs:-}" ]; then IFS=, read -ra envargs <<< "$envs"; fi
     env "${envargs[@]}" YOUTH_ICP_LIB=tools/ab/$lib/libyouth_icp.so timeout -k 10 240 python3 bench.py \
-        --full --steps 30 --warmup 5 --no-cpu-baseline --no-host-io ${EXTRA:-} \
+        --full --steps 30 --warmup 5 --no-cpu-baseline $HOSTIO ${EXTRA:-} \
         > gpurun_out/ab/$label.$r.json 2> gpurun_out/ab/$label.$r.err
     python3 - "$label" "$r" <<'PY'
 import json,sys
