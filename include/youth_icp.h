@@ -324,6 +324,19 @@ int youth_icp_get_sched_stats(youth_icp_ctx* ctx, unsigned* spins,
  * negative on error.  Either pointer may be NULL. */
 int youth_icp_get_plan(youth_icp_ctx* ctx, int* workgroups_per_pair, int* px_per_lane);
 
+/* Form of the first iteration of the last align on this context (reporting).
+ * An align whose poses all start at identity (no T_init), with the exact
+ * reduction, on the persistent path matches each source pixel with the target
+ * record at its own index: no transform, projection or gather.  Returns
+ * 2 when that ran inside the target prep pass (k_prep_ident; the sums are the
+ *   general form's up to fp64 summation order, k_icp runs iterations 1 ..),
+ * 1 when it ran as k_icp's iteration 0 (the prep pass did not form the
+ *   targets, or YOUTH_ICP_IDENT_FIRST=icp; the sums are the general form's
+ *   bit for bit),
+ * 0 for the general form (a T_init, the lane32 reduction, k_icp_coop, the
+ *   per-iteration path, YOUTH_ICP_NO_IDENT_FIRST=1), negative on error. */
+int youth_icp_get_first_iter(youth_icp_ctx* ctx);
+
 /* Validation of the projection reciprocal rz = RN(1 / z') the kernels form
  * from v_rcp_f32 plus correction steps: *bit_mismatches counts bitwise
  * differences from IEEE 1.0f / den over EVERY fp32 den in the guarded range

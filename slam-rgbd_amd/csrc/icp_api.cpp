@@ -66,6 +66,22 @@ static bool centred_exact(float cx, int W)
     return true;
 }
 
+// Whether the identity lemma's bound holds for these intrinsics (icp_device.h
+// ident_accumulate): projecting a back-projected pixel returns
+// its column within ~5 2^-24 |u - cx|, far below the half pixel the floor
+// allows, as long as no operation of the round trip under- or overflows.
+// With the principal point within 2^16 of the frame (|u - cx| < 2^17: 0.03 px)
+// and focal lengths and depth scale in [2^-20, 2^20], every intermediate of
+// (u - cx) z / fx and fx x / z stays a normal number for the depths 1 ..
+// 32767 and z = d / ds stays inside the projection's fast range.  Intrinsics
+// outside (none in practice) keep the general first iteration.
+static bool ident_first_ok(const youth_intrinsics& K)
+{
+    auto mid = [](float v) { return v >= 0x1p-20f && v <= 0x1p20f; };
+    return mid(K.fx) && mid(K.fy) && mid(K.depth_scale) && std::fabs(K.cx) <= 0x1p16f &&
+           std::fabs(K.cy) <= 0x1p16f;
+}
+
 extern "C" {
 
 youth_intrinsics youth_default_intrinsics(int width, int height)
@@ -248,6 +264,13 @@ youth_icp_ctx* youth_icp_create(int device, int W, int H, int max_frames,
         if ((e = fill_occupancy(c, &what)) != hipSuccess) return fail(what, e);
         const char* np = getenv("YOUTH_ICP_NO_PERSISTENT");
         c->persistent = !(np && *np && *np != '0');
+        // A/B and test knob: k_icp's first iteration on the general path
+        const char* nif = getenv("YOUTH_ICP_NO_IDENT_FIRST");
+        c->ident_first = ident_first_ok(Kd) && !(nif && *nif && *nif != '0');
+        const char* ifm = getenv("YOUTH_ICP_IDENT_FIRST");  // "icp": not inside the prep pass
+        c->ident_prep = !(ifm && strcmp(ifm, "icp") == 0);
+        const char* pst = getenv("YOUTH_ICP_PREP_STRIP");   // tuning knob
+        if (pst && atoi(pst) >= 1) c->prep_strip = atoi(pst);
         const char* cth = getenv("YOUTH_ICP_COOP_THREADS");
         if (cth && atoi(cth) == 256) c->coop_threads = 256;
         const char* nc = getenv("YOUTH_ICP_NO_COOP");
@@ -545,6 +568,12 @@ int youth_icp_get_plan(youth_icp_ctx* c, int* workgroups_per_pair, int* px_per_l
     if (workgroups_per_pair) *workgroups_per_pair = c->last_coop ? c->last_coop_G : 0;
     if (px_per_lane) *px_per_lane = c->last_coop ? c->last_coop_px : 0;
     return c->last_coop ? 1 : c->persistent ? 0 : 2;
+}
+
+int youth_icp_get_first_iter(youth_icp_ctx* c)
+{
+    if (!c) return g_icp_err.set(YOUTH_EINVAL, "get_first_iter: null context");
+    return c->last_first_form;
 }
 
 int youth_icp_get_timing(youth_icp_ctx* c, int kind, double* total_ms, int* launches)

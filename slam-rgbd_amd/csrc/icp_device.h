@@ -4,7 +4,8 @@
 // (PairMap, PoseState); the 64-bit lane helpers; fast / IEEE division, the
 // projection quotient and the normalisation; back-projection, of one pixel
 // and of a lane's four per loop step (backproject4); lane masks; spec a7-a9
-// per pixel (survey_project, xform_project, match_accumulate); the wave
+// per pixel (survey_project, xform_project, match_accumulate over
+// gate_accumulate; ident_accumulate, the identity-pose form); the wave
 // reduce-scatter (wave_reduce_scatter<kN>); the fused solve's hand-off
 // between a pair's workgroups (handoff_publish, handoff_sum); the a10 solve
 // and pose update.  One text of the spec's arithmetic and of the summation
@@ -698,18 +699,18 @@ __device__ __forceinline__ void xform_project(const float* T, float sx, float sy
 //       per product-add; exact (A = double): the 28 products of fp32 values
 //       are exact in fp64, one rounding per add.  Unmatched lanes skip the
 //       update, or add J = 0 and r = +-0, which leaves every sum unchanged
-//       (an accumulator is never -0: it starts at +0 and x + -x is +0).  The target's x, y are recomputed from its z with
-//       k_prep's expression (bit-identical to the stored plane).
+//       (an accumulator is never -0: it starts at +0 and x + -x is +0).
 //   kSpecSurvey: d2 = (dx dx + dy dy) + dz dz, r = (n0 dx + n1 dy) + n2 dz,
 //       (P' x n)_0 = qy n2 - qz n1 etc. (no FMA).
-template <int kSp, bool kFast, bool kSkip, typename A>
-__device__ __forceinline__ LaneMask match_accumulate(float qx, float qy, float qz, f4v t, float fu,
-                                                     float fv, LaneMask inm, const Intr& K,
-                                                     const FastK& F, float thr2, A* acc)
+// gate_accumulate takes the target's x, y as given: match_accumulate
+// recomputes them from the record's z with k_prep's expression (bit-identical
+// to the stored plane); the prep pass's identity iteration has them in its
+// LDS planes.
+template <int kSp, bool kSkip, typename A>
+__device__ __forceinline__ LaneMask gate_accumulate(float qx, float qy, float qz, float tx, float ty,
+                                                    f4v t, LaneMask inm, float thr2, A* acc)
 {
     const float tz = t.x;
-    const float tx = bp_div<kFast>((fu - K.cx) * tz, K.fx, F.hfx, F.lfx);
-    const float ty = bp_div<kFast>((fv - K.cy) * tz, K.fy, F.hfy, F.lfy);
     const float dx = qx - tx, dy = qy - ty, dz = qz - tz;
     const float d2 = sp_survey(kSp) ? (dx * dx + dy * dy) + dz * dz
                                         : fmaf(dz, dz, fmaf(dy, dy, dx * dx));
@@ -766,6 +767,49 @@ __device__ __forceinline__ LaneMask match_accumulate(float qx, float qy, float q
         }
     }
     return okm;
+}
+
+template <int kSp, bool kFast, bool kSkip, typename A>
+__device__ __forceinline__ LaneMask match_accumulate(float qx, float qy, float qz, f4v t, float fu,
+                                                     float fv, LaneMask inm, const Intr& K,
+                                                     const FastK& F, float thr2, A* acc)
+{
+    const float tz = t.x;
+    const float tx = bp_div<kFast>((fu - K.cx) * tz, K.fx, F.hfx, F.lfx);
+    const float ty = bp_div<kFast>((fv - K.cy) * tz, K.fy, F.hfy, F.lfy);
+    return gate_accumulate<kSp, kSkip>(qx, qy, qz, tx, ty, t, inm, thr2, acc);
+}
+
+// Spec a7-a9 of one pixel at the IDENTITY pose (the first iteration of an
+// align without T_init; DESIGN.md §2 "the identity lemma").  With R = I and
+// t = 0 both arithmetics return P' = P bit for bit on every valid source
+// pixel: 1 x is exact, 0 y and 0 z are zeros of either sign, and x + (+-0) =
+// x for x != 0, (+0) + (+-0) = +0; a valid pixel (z > 0) never has x or y =
+// -0 ((u - cx) z is +0 or a normal number, and so is its quotient by fx).
+// The projection of P lands on the pixel it was back-projected from: uf =
+// (fx x) / z + cx differs from u by at most 4 roundings of |u - cx| and one
+// of u, under 0.03 px for |u - cx| < 2^17 (the host checks the intrinsics:
+// ident_first_ok), so floor(uf + 0.5) = u and likewise v, in range by
+// construction.  So the pixel is "in" iff its source is valid, the matched
+// record is the record at its own index, and (fu, fv) are its own
+// coordinates: no transform, reciprocal, quotients, floors, index or gather.
+// (sx, sy, sz) as backproject4 forms them, t the target's record at pixel
+// (u, v) = (fu, fv); the gate, r, J and the sums are match_accumulate's own.
+template <int kSp, bool kFast, bool kSkip, typename A>
+__device__ __forceinline__ LaneMask ident_accumulate(float sx, float sy, float sz, f4v t, float fu,
+                                                     float fv, const Intr& K, const FastK& F,
+                                                     float thr2, A* acc)
+{
+    return match_accumulate<kSp, kFast, kSkip>(sx, sy, sz, t, fu, fv, mask_gt(sz, 0.0f), K, F, thr2,
+                                               acc);
+}
+// The same with the target's x, y at hand (k_prep_ident: the prep pass's LDS
+// planes, which hold what match_accumulate recomputes from the record's z).
+template <int kSp, bool kSkip, typename A>
+__device__ __forceinline__ LaneMask ident_accumulate_xy(float sx, float sy, float sz, float tx,
+                                                        float ty, f4v t, float thr2, A* acc)
+{
+    return gate_accumulate<kSp, kSkip>(sx, sy, sz, tx, ty, t, mask_gt(sz, 0.0f), thr2, acc);
 }
 
 // Wave sum of kN <= 32 per-lane accumulators by recursive halving: at lane

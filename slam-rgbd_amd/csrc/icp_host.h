@@ -82,6 +82,15 @@ struct youth_icp_ctx {
     unsigned* d_epoch = nullptr;     // [max_frames] persistent pose epochs
     unsigned* d_head = nullptr;      // queue words kQHead / kQError / kQSpins / kQWaited
     bool persistent = true;          // one k_icp launch per align (else per-iteration k_reduce)
+    // Iteration 0 of a persistent align without T_init takes the identity form
+    // (ident_accumulate): the intrinsics keep the identity lemma's bound
+    // (ident_first_ok) and YOUTH_ICP_NO_IDENT_FIRST=1 is not set.  It runs
+    // inside the prep pass (k_prep_ident) where that pass forms the pairs'
+    // targets, unless YOUTH_ICP_IDENT_FIRST=icp keeps it in k_icp.
+    bool ident_first = true;
+    bool ident_prep = true;
+    int prep_strip = 0;              // tiles per k_prep_ident workgroup (YOUTH_ICP_PREP_STRIP; 0: by batch size)
+    int last_first_form = 0;         // the last align's (youth_icp_get_first_iter)
     int reduce = YOUTH_REDUCE_EXACT; // spec a9 (youth_icp_set_reduce, YOUTH_ICP_REDUCE)
     youth_lanes lanes{};             // lane partition of the last align's iterations
     bool has_lanes = false;

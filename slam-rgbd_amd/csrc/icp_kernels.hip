@@ -263,11 +263,16 @@ __global__ void k_selftest_normalize(unsigned long long n, unsigned long long se
 // buffer stores) for an in-launch hand-off (k_icp_coop).  Contains a
 // workgroup barrier (every thread must call it); a caller reusing the LDS
 // planes for another tile adds one more before it.
-template <bool kFast, bool kWide, bool kSc1, int kThreads, int kTH, int kTW = kTileW>
-__device__ __forceinline__ void prep_tile(const int16_t* __restrict__ dep, float4* __restrict__ R,
-                                          int W, int H, size_t P, const Intr& K, const FastK& F,
-                                          float* __restrict__ X, int x0, int y0, float* sX,
-                                          float* sY, float* sZ)
+// prep_tile_with: per_record(k, px, py, pz, rec) runs for every pixel of the
+// frame right after its record is stored: k the step of the record loop
+// (pixel (x0 + tx, y0 + ty + (kThreads / kTW) k)), (px, py, pz) its point from
+// the planes, rec its record.  prep_tile passes nothing.
+template <bool kFast, bool kWide, bool kSc1, int kThreads, int kTH, int kTW = kTileW, typename Fn>
+__device__ __forceinline__ void prep_tile_with(const int16_t* __restrict__ dep,
+                                               float4* __restrict__ R, int W, int H, size_t P,
+                                               const Intr& K, const FastK& F,
+                                               float* __restrict__ X, int x0, int y0, float* sX,
+                                               float* sY, float* sZ, Fn&& per_record)
 {
     constexpr int kLH = kTH + 2;
     constexpr int kLW = kTW + 2;
@@ -450,7 +455,19 @@ __device__ __forceinline__ void prep_tile(const int16_t* __restrict__ dep, float
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, rec), rrec,
                                                    (int)(i * sizeof(float4)), 0, 2);
         }
+        per_record(k, px, py, pz, rec);
     }
+}
+
+template <bool kFast, bool kWide, bool kSc1, int kThreads, int kTH, int kTW = kTileW>
+__device__ __forceinline__ void prep_tile(const int16_t* __restrict__ dep, float4* __restrict__ R,
+                                          int W, int H, size_t P, const Intr& K, const FastK& F,
+                                          float* __restrict__ X, int x0, int y0, float* sX,
+                                          float* sY, float* sZ)
+{
+    prep_tile_with<kFast, kWide, kSc1, kThreads, kTH, kTW>(
+        dep, R, W, H, P, K, F, X, x0, y0, sX, sY, sZ,
+        [](int, float, float, float, const float4&) __attribute__((always_inline)) {});
 }
 
 // The persistent path's per-call state, set by k_prep's tile-(0,0) blocks
@@ -759,6 +776,76 @@ __device__ __forceinline__ void accumulate_chunk(const int16_t* __restrict__ sD,
     acc[28] += (threadIdx.x & 63) == 0 ? (double)cnt : 0.0;
 }
 
+// accumulate_chunk at the identity pose (k_icp's iteration 0 of an align
+// without T_init, exact reduction): the same lanes take the same pixels in
+// the same order, so the sums are accumulate_chunk's bit for bit, but each
+// pixel's record is the one at its own index (ident_accumulate): a lane's
+// four records are 64 contiguous bytes, requested before the back-projection
+// instead of gathered after the projection.  A pixel at or past `end` has
+// depth 0 (unaligned form), one past N reads the frame's zeroed pad.
+template <int kSp, bool kFast, bool kAligned>
+__device__ __forceinline__ void accumulate_chunk_ident(const int16_t* __restrict__ sD,
+                                                       const float4* __restrict__ rec,
+                                                       int rec_bytes, int start, int end, int W,
+                                                       int H, const Intr& K, const FastK& F,
+                                                       float thr2, double* acc)
+{
+    static_assert(!sp_lane32(kSp), "the lane32 sums keep the general path");
+    const __amdgpu_buffer_rsrc_t rrec = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float4*>(rec), (short)0, rec_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rdep = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<int16_t*>(sD), (short)0, W * H * (int)sizeof(int16_t), 0x00020000);
+    const int stepV = kRedStep / W;
+    const int stepU = kRedStep - stepV * W;
+    int i = start + threadIdx.x * 4;
+    int v0 = i / W;
+    int u0 = i - v0 * W;
+    int cnt = 0;
+    short4 dnext = kAligned && i < end ? __builtin_bit_cast(short4, __builtin_amdgcn_raw_buffer_load_b64(
+                                                                       rdep, i * 2, 0, 0))
+                                       : short4{};
+    for (; i < end; i += kRedStep) {
+        const short4 d4 = kAligned ? dnext : load_depth4<kAligned>(sD, i, end);
+        const int dd[4] = {d4.x, d4.y, d4.z, d4.w};
+        f4v t[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            t[q] = __builtin_bit_cast(
+                f4v, __builtin_amdgcn_raw_buffer_load_b128(rrec, (i + q) * 16, 0, 0));
+        asm volatile("" ::: "memory");
+        if (kAligned)
+            dnext = __builtin_bit_cast(
+                short4, __builtin_amdgcn_raw_buffer_load_b64(rdep, (i + kRedStep) * 2, 0, 0));
+        float sx[4], sy[4], sz[4];
+        backproject4<kFast, kAligned>(dd, i, end, u0, v0, W, K, F,
+                                      [&](int q, float x, float y, float z)
+                                          __attribute__((always_inline)) {
+                                              sx[q] = x;
+                                              sy[q] = y;
+                                              sz[q] = z;
+                                          });
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            int u = u0 + q, v = v0;  // backproject4's pixel q
+            if (!kAligned) {
+                const bool wrap = u >= W;
+                u = wrap ? u - W : u;
+                v = wrap ? v + 1 : v;
+            }
+            const LaneMask okm = ident_accumulate<kSp, kFast, true>(
+                sx[q], sy[q], sz[q], t[q], (float)u, (float)v, K, F, thr2, acc);
+            cnt += __builtin_popcountll(okm);
+        }
+        u0 += stepU;
+        v0 += stepV;
+        if (u0 >= W) {
+            u0 -= W;
+            ++v0;
+        }
+    }
+    acc[28] += (threadIdx.x & 63) == 0 ? (double)cnt : 0.0;
+}
+
 
 template <int kSp, bool kAssoc, bool kFast, bool kAligned, bool kFuse>
 __global__ __launch_bounds__(kRedThreads) void k_reduce(
@@ -912,13 +999,16 @@ struct IterState {
     float* T_out;         // [pair][16] fp32 4x4 written by the final solve, or null
     int iters, n_pairs, nblk, chunk;
     int nq;               // work queues (1..kMaxQueues): heads at head[kQHeads + 32 q]
+    int ident_first;      // every pose starts at identity: iteration 0 takes accumulate_chunk_ident
+    int first;            // first iteration to run (1: k_prep_ident ran iteration 0 and set epoch = 1)
 };
 
 // One dequeue: from the workgroup's current queue q, moving on to the next
 // queue when q is drained (each queue holds the pairs p = q (mod nq), items
 // (iteration, pair, chunk) in that order).  Returns the item in the global
 // numbering item = (k n_pairs + p) nblk + c, or `total` when every queue is
-// drained.  Dependencies stay inside a queue (an item waits only on earlier
+// drained.  The queues hold iterations is.first .. iters - 1 (first = 1 when
+// k_prep_ident ran iteration 0 and left epoch[p] = 1).  Dependencies stay inside a queue (an item waits only on earlier
 // items of its own pairs, dequeued before it by running workgroups), so
 // every queue is deadlock-free on its own, as the single queue was; nq > 1
 // spreads the contended returning atomics over nq words (one per 128-B line):
@@ -943,9 +1033,10 @@ __device__ __forceinline__ int icp_dequeue_from(const IterState& is, int& q, uns
         if (npq > 0) {
             const int per = npq * is.nblk;
             const int i = (int)t;
-            if (i < is.iters * per) {
-                const int k = i / per;
-                const int rem = i - k * per;
+            if (i < (is.iters - is.first) * per) {
+                const int k0 = i / per;
+                const int rem = i - k0 * per;
+                const int k = is.first + k0;
                 const int pl = rem / is.nblk;
                 const int c = rem - pl * is.nblk;
                 return (k * is.n_pairs + q + is.nq * pl) * is.nblk + c;
@@ -1081,10 +1172,21 @@ __global__ __launch_bounds__(kRedThreads, 4) void k_icp(const int16_t* __restric
         for (int q = 0; q < kNeq; ++q) acc[q] = 0.0;
         const int start = c * is.chunk;
         const int end = min(start + is.chunk, N);
-        accumulate_chunk<kSp, false, kFast, kAligned>(dsrc + (size_t)(pm.src0 + p) * N,
-                                                 recs + (size_t)(pm.tgt0 + p) * P,
-                                                 (int)(P * sizeof(float4)), T, start, end, W, H,
-                                                 K, F, thr2, acc, nullptr);
+        // iteration 0 from the identity pose: every pixel matches the record
+        // at its own index (wave-uniform choice per item; the same sums)
+        bool ident = false;
+        if constexpr (!sp_lane32(kSp)) ident = (k == 0) & (is.ident_first != 0);
+        if (ident) {
+            if constexpr (!sp_lane32(kSp))
+                accumulate_chunk_ident<kSp, kFast, kAligned>(
+                    dsrc + (size_t)(pm.src0 + p) * N, recs + (size_t)(pm.tgt0 + p) * P,
+                    (int)(P * sizeof(float4)), start, end, W, H, K, F, thr2, acc);
+        } else {
+            accumulate_chunk<kSp, false, kFast, kAligned>(dsrc + (size_t)(pm.src0 + p) * N,
+                                                     recs + (size_t)(pm.tgt0 + p) * P,
+                                                     (int)(P * sizeof(float4)), T, start, end, W,
+                                                     H, K, F, thr2, acc, nullptr);
+        }
         {
             double tot;
             wave_reduce_scatter<kNeq>(acc, lane, tot);
@@ -1162,6 +1264,168 @@ __global__ __launch_bounds__(kRedThreads, 4) void k_icp(const int16_t* __restric
         // ---- next item (this workgroup has published: waiting is safe)
         if (threadIdx.x == 0) sh_item = icp_claim(is, sh_next, total, per_iter, sh_T);
         __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------ k_prep_ident --
+// k_prep with the FIRST ICP iteration inside it, for aligns that start at the
+// identity pose (no T_init, exact reduction; run_iterations).  There every
+// source pixel matches the target record at its own index (icp_device.h
+// ident_accumulate), and k_prep holds that record in registers, and the
+// target's point in its LDS planes, when it stores it.  So the pass that is
+// bound by its 16 B/px store stream also loads the pair's source depth at
+// the pixel (2 B/px) and runs the gate, r, J and the 29 sums on its idle VALU,
+// and k_icp runs iterations 1 .. iters - 1 only.
+//   * A workgroup walks a STRIP of `strip` consecutive tiles of one frame
+//     (prep_tile_with, one more barrier per further tile) with its fp64 sums
+//     in registers, then reduces once: wave_reduce_scatter, the eight waves
+//     through LDS (the planes, after a barrier), one partial row published and
+//     one ticket on arrivals[p] (handoff_publish).
+//   * The pair's last arriver adds the rows in fixed order (handoff_sum),
+//     solves from the identity pose and writes everything k_init would have
+//     written and iteration 0 would have left: T64 / T32, status,
+//     stats[p][0], epoch[p] = 1, k_icp's tickets zeroed, and with iters == 1
+//     the fp32 4x4 output.  It re-arms arrivals[p] for the next launch.
+//   * No spin and no wait on another workgroup.  A frame that is no pair's
+//     target only gets its records.
+// The sums equal k_icp's iteration 0 up to fp64 summation order.
+struct IdentArgs {
+    const int16_t* dsrc;  // source depth frames
+    PairMap pm;           // pair p: source frame src0 + p, target record frame tgt0 + p
+    int n_pairs, iters;
+    float thr2;
+    double* partials;     // [pair][strips][kPartStride]
+    double* T64;          // [pair][16]
+    float* T32;           // [pair][12]
+    int32_t* status;      // [pair]
+    double* stats;        // [pair][iters][2] or null
+    unsigned* epoch;      // [pair]
+    unsigned* arr_it;     // [pair][iters] k_icp's arrival tickets
+    unsigned* arrivals;   // [pair] this kernel's tickets: zero at launch, re-armed by the last arriver
+    float* T_out;         // [pair][16] or null (written when iters == 1)
+    unsigned* head_err;   // queue words, zeroed by workgroup 0
+};
+
+template <int kSp, bool kFast, bool kWide>
+__global__ __launch_bounds__(kPrepThreads) void k_prep_ident(const int16_t* __restrict__ depth,
+                                                            int out0, int W, int H, size_t P,
+                                                            Intr K, FastK F,
+                                                            float4* __restrict__ recs, IdentArgs ia,
+                                                            int tiles_x, int tiles_y, int strip)
+{
+    static_assert(!sp_lane32(kSp), "exact sums only");
+    constexpr int kRows = kPrepThreads / kPrepTW;  // rows of a tile per record-loop step
+    constexpr int kSteps = kPrepTH / kRows;
+    constexpr int kWaves = kPrepThreads / 64;
+    __shared__ float sX[(kPrepTH + 2) * (kPrepTW + 2)];
+    __shared__ float sY[(kPrepTH + 2) * (kPrepTW + 2)];
+    __shared__ float sZ[(kPrepTH + 2) * (kPrepTW + 2)];
+    static_assert(sizeof(sX) >= kWaves * kNeq * sizeof(double), "the waves' sums fit a plane");
+    static_assert(sizeof(sY) >= (32 + 16) * sizeof(double) + 12 * sizeof(float), "solve scratch");
+    const int per = tiles_x * tiles_y;
+    const int strips = (per + strip - 1) / strip;
+    const int f = (int)blockIdx.x / strips;
+    const int sidx = (int)blockIdx.x - f * strips;
+    if (blockIdx.x == 0 && threadIdx.x < kMaxQueues && ia.head_err) {
+        if (threadIdx.x == 0) {
+            ia.head_err[kQHead] = 0u;
+            ia.head_err[kQError] = 0u;
+            ia.head_err[kQSpins] = 0u;
+            ia.head_err[kQWaited] = 0u;
+        }
+        ia.head_err[kQHeads + kQHeadStride * threadIdx.x] = 0u;
+    }
+    const int N = W * H;
+    const int p = out0 + f - ia.pm.tgt0;  // the pair whose target this frame is
+    const bool paired = (unsigned)p < (unsigned)ia.n_pairs;  // workgroup-uniform
+    // the pair's source depth through a buffer descriptor: a pixel outside
+    // the frame (ragged tile) takes the offset N 2, which reads as 0
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<int16_t*>(ia.dsrc + (size_t)(ia.pm.src0 + (paired ? p : 0)) * N), (short)0,
+        N * (int)sizeof(int16_t), 0x00020000);
+    const int tx = threadIdx.x % kPrepTW;
+    const int tyw = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kPrepTW);
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    double acc[kNeq];
+#pragma unroll
+    for (int q = 0; q < kNeq; ++q) acc[q] = 0.0;
+    int cnt = 0;  // this lane's matches (exact in the fp64 sum, whatever the order)
+
+    const int t0 = sidx * strip, t1 = min(t0 + strip, per);
+    for (int r = t0; r < t1; ++r) {
+        const int tyi = r / tiles_x;
+        const int x0 = (r - tyi * tiles_x) * kPrepTW, y0 = tyi * kPrepTH;
+        // this thread's source depths, requested ahead of the tile's own loads
+        int sd[kSteps];
+#pragma unroll
+        for (int k = 0; k < kSteps; ++k) {
+            const int gx = x0 + tx, gy = y0 + tyw + kRows * k;
+            const bool in = paired & (gx < W) & (gy < H);
+            sd[k] = (short)__builtin_amdgcn_raw_buffer_load_b16(rsrc, in ? (gy * W + gx) * 2 : N * 2,
+                                                                0, 0);
+        }
+        if (r > t0) __syncthreads();  // the planes are reused
+        prep_tile_with<kFast, kWide, false, kPrepThreads, kPrepTH, kPrepTW>(
+            depth + (size_t)f * N, recs + (size_t)(out0 + f) * P, W, H, P, K, F, nullptr, x0, y0, sX,
+            sY, sZ,
+            [&](int k, float px, float py, float pz, const float4& rec)
+                __attribute__((always_inline)) {
+                    if (!paired) return;
+                    float sx, sy, sz;
+                    backproject<kFast>(sd[k], x0 + tx, y0 + tyw + kRows * k, K, F, sx, sy, sz);
+                    const f4v t = {rec.x, rec.y, rec.z, rec.w};
+                    const LaneMask okm = ident_accumulate_xy<kSp, true>(sx, sy, sz, px, py, t,
+                                                                        ia.thr2, acc);
+                    cnt += lane_in(okm) ? 1 : 0;
+                });
+    }
+    if (!paired) return;
+    acc[28] = (double)cnt;
+    double tot;
+    wave_reduce_scatter<kNeq>(acc, lane, tot);
+    __syncthreads();  // every wave has left the planes
+    double(*red)[kNeq] = reinterpret_cast<double(*)[kNeq]>(sX);
+    if (!(lane & 1) && (lane >> 1) < kNeq) red[wave][lane >> 1] = tot;
+    __syncthreads();
+    if (threadIdx.x >= 64) return;  // wave 0 publishes (and, if last, solves)
+    double s = 0.0;
+    if (lane < kNeq) {
+        double w[kWaves];
+#pragma unroll
+        for (int q = 0; q < kWaves; ++q) w[q] = red[q][lane];
+        s = tree_sum<kWaves>(w);
+    }
+    PoseState ps{};
+    ps.arrivals = ia.arrivals;
+    if (!handoff_publish<kNeq>(ia.partials + ((size_t)p * strips + sidx) * kPartStride, ps, p, strips,
+                               lane, s))
+        return;
+    double neq[kNeq];
+    handoff_sum<kNeq, kPartStride>(ia.partials, p, strips, lane, neq);
+    double* sh_neq = reinterpret_cast<double*>(sY);  // [kNeq] (wave 0 alone is left)
+    double* sh_T64 = sh_neq + 32;                    // [16]
+    float* sh_T32 = reinterpret_cast<float*>(sh_T64 + 16);  // [12]
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < kNeq; ++q) sh_neq[q] = neq[q];
+    }
+    if (lane < 16) sh_T64[lane] = (lane % 5) == 0 ? 1.0 : 0.0;
+    if (lane < 12) sh_T32[lane] = (lane % 5) == 0 ? 1.0f : 0.0f;
+    const int st = solve_update_wave_call(sh_neq, sh_T64, sh_T32, lane);
+    if (lane < 16) ia.T64[(size_t)p * 16 + lane] = sh_T64[lane];
+    if (lane < 12) ia.T32[(size_t)p * 12 + lane] = sh_T32[lane];
+    if (ia.iters == 1 && ia.T_out && lane < 16)
+        ia.T_out[(size_t)p * 16 + lane] = lane < 12 ? sh_T32[lane] : (lane == 15 ? 1.0f : 0.0f);
+    for (int k = lane; k < ia.iters; k += 64) ia.arr_it[(size_t)p * ia.iters + k] = 0u;
+    if (lane == 0) {
+        ia.status[p] = st;
+        ia.epoch[p] = 1u;
+        ia.arrivals[p] = 0u;  // re-armed for the next launch (stream order)
+        if (ia.stats) {
+            ia.stats[(size_t)p * ia.iters * 2 + 0] = neq[28];
+            ia.stats[(size_t)p * ia.iters * 2 + 1] = neq[27];
+        }
     }
 }
 
@@ -1911,6 +2175,58 @@ static int launch_prep_with(youth_icp_ctx* c, hipStream_t s, const int16_t* dept
     return ev_end(c, s, &ep);
 }
 
+// k_prep_ident<spec, fast, wide> by index spec 4 + fast 2 + wide
+typedef void (*PrepIdentKernel)(const int16_t*, int, int, int, size_t, Intr, FastK, float4*,
+                                IdentArgs, int, int, int);
+static PrepIdentKernel prep_ident_kernel(int idx)
+{
+    static const PrepIdentKernel tab[8] = {
+        k_prep_ident<0, false, false>, k_prep_ident<0, false, true>, k_prep_ident<0, true, false>,
+        k_prep_ident<0, true, true>,   k_prep_ident<1, false, false>, k_prep_ident<1, false, true>,
+        k_prep_ident<1, true, false>,  k_prep_ident<1, true, true>};
+    return tab[idx & 7];
+}
+
+// The prep job with iteration 0 of every pair inside it (k_prep_ident); nb:
+// k_icp's chunks per pair, which share the partial rows.
+static int launch_prep_ident(youth_icp_ctx* c, hipStream_t s, const PrepJob* job,
+                             const int16_t* dsrc, PairMap pm, int n_pairs, int iters, float thr2,
+                             int nb, float* d_T_out)
+{
+    const int tiles_x = (c->W + kPrepTW - 1) / kPrepTW, tiles_y = (c->H + kPrepTH - 1) / kPrepTH;
+    const int per = tiles_x * tiles_y;
+    // Tiles per workgroup: a longer strip means fewer reductions and
+    // publishes (one tile per workgroup would be 51,200 of them at 512 frames
+    // of 640x480) but fewer workgroups to balance over the chip.  Measured at
+    // 512 pairs (profiles/ident/strip_sweep.txt): 2 tiles 88.3 K aligns/s, 4
+    // 90.3, 5 90.5, 10 91.2, 20 91.6, 25 91.7, 50 91.3, 100 91.1.  So 25,
+    // shortened for small batches until the grid holds about four rounds of
+    // the two resident workgroups per CU, but not below 5.
+    int strip = c->prep_strip;
+    if (strip <= 0) {
+        strip = (int)std::min<long long>(25, (long long)per * job->n / (8LL * c->n_cu));
+        strip = std::max(strip, 5);
+    }
+    strip = std::min(strip, per);
+    const int strips = (per + strip - 1) / strip;
+    const long long blocks = (long long)strips * job->n;
+    if (blocks > 0x7fffffffLL) return g_icp_err.set(YOUTH_EINVAL, "launch_prep: %lld strips", blocks);
+    int rc = ensure_partials(c, (size_t)std::max(nb, strips) * n_pairs * kPartStride);
+    if (rc) return rc;
+    EventPair ep{};
+    rc = ev_begin(c, s, &ep, 2);
+    if (rc) return rc;
+    const bool wide = (c->W % 4 == 0) && (reinterpret_cast<uintptr_t>(job->depth) % 8 == 0);
+    const IdentArgs ia{dsrc,      pm,        n_pairs,     iters,      thr2,
+                       c->d_partials, c->d_T64, c->d_T32,  c->d_status, c->d_stats,
+                       c->d_epoch, c->d_arr_it, c->d_arrivals, d_T_out,  c->d_head};
+    auto kern = prep_ident_kernel(c->spec * 4 + (c->fast ? 2 : 0) + (wide ? 1 : 0));
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kPrepThreads), 0, s, job->depth, job->out0,
+                       c->W, c->H, c->P, c->K, c->F, c->d_rec, ia, tiles_x, tiles_y, strip);
+    HIP_TRY(hipGetLastError());
+    return ev_end(c, s, &ep);
+}
+
 int launch_prep(youth_icp_ctx* c, hipStream_t s, const int16_t* depth, int n_frames, int out0,
                 bool want_xyz)
 {
@@ -2272,6 +2588,7 @@ int run_iterations(youth_icp_ctx* c, hipStream_t s, const int16_t* dsrc, int src
                coop_plan(c, n_pairs, &npx, &G);
     }
     c->last_coop = coop;
+    c->last_first_form = 0;
     int rc = ensure_stats(c, iters > 0 ? iters : 1);
     if (rc) return rc;
     const double* dTi = nullptr;
@@ -2296,7 +2613,25 @@ int run_iterations(youth_icp_ctx* c, hipStream_t s, const int16_t* dsrc, int src
         c->last_coop = false;
     }
     const bool persistent = c->persistent && iters > 0;
-    if (persistent && job) {
+    int chunk = 0;
+    const int nb = persistent ? reduce_geometry(c, n_pairs, &chunk) : 0;
+    const float thr2 = c->prm.dist_thresh * c->prm.dist_thresh;
+    // Every pose starts at identity (no T_init) and the sums are exact:
+    // iteration 0 matches every pixel with the record at its own index.  It
+    // runs inside the prep pass when that pass forms every pair's target
+    // records (k_prep_ident), else as k_icp's identity form.
+    const bool ident = persistent && !dTi && c->ident_first && c->reduce != YOUTH_REDUCE_LANE32;
+    // Not inside the prep pass when contexts share the device (set_concurrency):
+    // k_prep_ident holds its CUs about twice as long as k_prep, beside the
+    // other context's k_icp; 64- and 128-pair shards two in flight then ran
+    // anywhere from -3 % to +3 % of the parent (profiles/ident/shards.txt),
+    // where k_icp's own identity form is a steady +0.5 to +2 %.
+    const bool ident_prep = ident && c->ident_prep && c->share == 1 && job && job->wait &&
+                            job->out0 <= tgt0 && tgt0 + n_pairs <= job->out0 + job->n;
+    if (ident_prep) {
+        rc = launch_prep_ident(c, s, job, dsrc, pm, n_pairs, iters, thr2, nb, d_T_out);
+        if (rc) return rc;
+    } else if (persistent && job) {
         // k_prep also sets the per-call state (k_init folded in)
         const InitArgs ia{dTi,         n_pairs,    c->d_T64, c->d_T32, c->d_status,
                           c->d_epoch,  c->d_arr_it, iters,   c->d_head};
@@ -2311,14 +2646,13 @@ int run_iterations(youth_icp_ctx* c, hipStream_t s, const int16_t* dsrc, int src
         if (rc) return rc;
     }
     if (persistent) {
-        int chunk = 0;
-        const int nb = reduce_geometry(c, n_pairs, &chunk);
         rc = ensure_partials(c, (size_t)nb * n_pairs * kPartStride);
         if (rc) return rc;
         const bool aligned = (reinterpret_cast<uintptr_t>(dsrc) % 8 == 0) && (c->W % 4 == 0) &&
                            c->centred_exact;
         const int var = variant(c) * 4 + (c->fast ? 2 : 0) + (aligned ? 1 : 0);
-        const long long items = (long long)iters * n_pairs * nb;
+        const int first = ident_prep ? 1 : 0;
+        const long long items = (long long)(iters - first) * n_pairs * nb;
         long long grid = (long long)c->n_cu * c->icp_blocks_per_cu[var] / c->share;
         if (grid > items) grid = items;
         if (grid < 1) grid = 1;
@@ -2328,16 +2662,21 @@ int run_iterations(youth_icp_ctx* c, hipStream_t s, const int16_t* dsrc, int src
                            chunk,
                            // 8 per-XCD heads from 128 pairs (+0.7 % there), one below (64
                            // pairs: -0.8 % with 8; profiles/r03/ab_queues.txt)
-                           c->queues ? c->queues : (n_pairs >= 128 ? kMaxQueues : 1)};
+                           c->queues ? c->queues : (n_pairs >= 128 ? kMaxQueues : 1),
+                           // no T_init: iteration 0 at the identity pose (exact sums only:
+                           // the lane32 kernels have no such form)
+                           ident && !ident_prep, first};
+        c->last_first_form = ident_prep ? 2 : ident ? 1 : 0;
         if (exported) *exported = d_T_out != nullptr;  // k_icp's final solves write d_T_out
-        const float thr2 = c->prm.dist_thresh * c->prm.dist_thresh;
         EventPair ep{};
         rc = ev_begin(c, s, &ep, 0);
         if (rc) return rc;
-        auto kern = icp_kernel(var);
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kRedThreads), 0, s, dsrc, c->d_rec,
-                           c->P, pm, c->W, c->H, c->K, c->F, thr2, c->d_partials, is);
-        HIP_TRY(hipGetLastError());
+        if (items > 0) {  // (iters == 1 after k_prep_ident: nothing is left)
+            auto kern = icp_kernel(var);
+            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kRedThreads), 0, s, dsrc, c->d_rec,
+                               c->P, pm, c->W, c->H, c->K, c->F, thr2, c->d_partials, is);
+            HIP_TRY(hipGetLastError());
+        }
         c->lanes = youth_lanes{YOUTH_LANES_STRIDED, chunk, kRedThreads, 0};
         c->has_lanes = true;
         c->lanes_mixed = false;

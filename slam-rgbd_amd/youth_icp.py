@@ -160,6 +160,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "youth_icp_get_timing": (c_int, [c_void_p, c_int, PD, POINTER(c_int)]),
         "youth_icp_get_sched_stats": (c_int, [c_void_p, POINTER(c_uint32), POINTER(c_uint32)]),
         "youth_icp_get_plan": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
+        "youth_icp_get_first_iter": (c_int, [c_void_p]),
         "youth_icp_selftest_projdiv": (c_int, [c_int, ctypes.c_longlong, ctypes.c_ulonglong,
                                                POINTER(ctypes.c_longlong),
                                                POINTER(ctypes.c_longlong)]),
@@ -590,6 +591,13 @@ class IcpContext:
         if r == 2:
             return {"kernel": "k_prep + k_init + k_reduce x iters (per-iteration)"}
         return {"kernel": "k_prep + k_icp (persistent)"}
+
+    def get_first_iter(self) -> str:
+        """Form of the last align's first iteration: "prep" (at the identity
+        pose inside the target prep pass, k_prep_ident), "identity" (the same
+        form as k_icp's iteration 0) or "general"."""
+        return ("general", "identity", "prep")[
+            _check(self._lib.youth_icp_get_first_iter(self._ctx))]
 
     # host-array stage entry points (parity tests)
     def prepare(self, depth: np.ndarray, want_normals: bool = True, want_xyz: bool = True):
