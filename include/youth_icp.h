@@ -632,6 +632,12 @@ int youth_slam_get_status(int n, int32_t* status, long long* few_matches,
  * oldest down to 5 when it passes 10, SLAM.cpp:163-168): a producer that
  * must not lose frames waits while this is 10. */
 int youth_slam_queue_size(void);
+/* 1 while the module is running and tracks with colour (YOUTH_SLAM_RGBD=1 at
+ * initSlamModule: the streaming RGB-D tracker of youth_rgbd.h behind
+ * processSlamFrame, whose color_data is then required: RGB uint8
+ * [height][width][3]), else 0.  In RGB-D mode youth_slam_batched_frames counts
+ * the frames that travelled in submissions of more than one frame. */
+int youth_slam_rgbd_active(void);
 /* Block until the module stops (used by algorithmModule). */
 void youth_slam_wait_stopped(void);
 

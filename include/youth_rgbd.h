@@ -124,6 +124,55 @@ int youth_rgbd_reduce_host(youth_rgbd_ctx* ctx, const int16_t* src_depth, const 
 int youth_rgbd_track_host_sequence(youth_rgbd_ctx* ctx, const int16_t* depth, const uint8_t* rgb,
                                    int n_frames, double* T_rel, int32_t* status);
 
+/* --- Streaming tracker -----------------------------------
+ * Frames submitted as they arrive, each aligned to the frame before it,
+ * results collected in order: youth_icp_track_submit / _collect with colour.
+ * Frames are HOST pointers, depth int16 [H][W] and RGB uint8 [H][W][3].  A
+ * frame inside a buffer of youth_icp_host_alloc (page-locked; colour takes
+ * (3 W H + 1) / 2 of its values) is fetched by the GPU in place and must stay
+ * unchanged until it has been collected; any other frame is copied into
+ * page-locked staging before the call returns.  The tracker shares the
+ * context's workspace with the entry points above: do not call those while
+ * frames are pending; after one of them the next frame starts a new sequence.
+ * An RGB-D align contains no wait between workgroups, so its status never
+ * carries YOUTH_STATUS_TIMEOUT and there is no realign. */
+
+/* Frames per submission, 1 <= b <= YOUTH_TRACK_MAX_BATCH (default 1).  Fixes
+ * the launch geometry of every later submission, whatever its size, so a
+ * frame's pose does not depend on how the sequence was split.  Needs
+ * max_frames >= 2 b and no frame pending.  Returns the previous value. */
+int youth_rgbd_track_set_batch(youth_rgbd_ctx* ctx, int b);
+
+/* Filter every ingested depth frame once (youth_filter.h) before anything else
+ * reads it; NULL (the default) switches it off.  No frame pending. */
+int youth_rgbd_track_set_depth_filter(youth_rgbd_ctx* ctx, const youth_filter_params* P);
+
+/* 1 <= n_frames <= b frames, asynchronous; frame i is aligned to frame i - 1,
+ * the first to the last frame submitted before.  At most two submissions may be
+ * in flight (YOUTH_EINVAL beyond). */
+int youth_rgbd_track_submit(youth_rgbd_ctx* ctx, const int16_t* const* depth,
+                            const uint8_t* const* rgb, int n_frames);
+
+/* The oldest uncollected frame: returns its YOUTH_STATUS_* bits or a negative
+ * code; T_rel [16] fp64 with P_ref = T_rel P_new; *has_ref (nullable) 0 and
+ * the identity for the first frame after create or reset. */
+int youth_rgbd_track_collect(youth_rgbd_ctx* ctx, double* T_rel, int* has_ref);
+
+/* Frames submitted and not yet collected (0 for NULL). */
+int youth_rgbd_track_pending(const youth_rgbd_ctx* ctx);
+
+/* The next frame starts a new sequence.  No frame pending (YOUTH_EINVAL). */
+int youth_rgbd_track_reset(youth_rgbd_ctx* ctx);
+
+/* Stage entry: the ingest kernel alone (k_rgbd_pull).  m <=
+ * YOUTH_TRACK_MAX_BATCH host frames -> DEVICE d_depth [m][H][W] int16, d_gray
+ * [m][H][W] uint8 (the intensity above) and, unless NULL, d_rgb [m][H][W][3].
+ * Asynchronous on `stream`; frames outside youth_icp_host_alloc buffers are
+ * staged first. */
+int youth_rgbd_pull_host(youth_rgbd_ctx* ctx, const int16_t* const* depth,
+                         const uint8_t* const* rgb, int m, int16_t* d_depth, uint8_t* d_gray,
+                         uint8_t* d_rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -282,6 +282,9 @@ hipError_t launch_status_out(youth_icp_ctx* c, hipStream_t s, int n, int32_t* ou
 // k_pull_frames: m page-locked host frames of N values -> dst[0 .. m N).
 int launch_pull_frames(youth_icp_ctx* c, hipStream_t s, const int16_t* const* src, int m,
                        int16_t* dst, int N, int wg);
+// icp_track.cpp: whether [p, p + bytes) lies inside one buffer of
+// youth_icp_host_alloc (page-locked: a kernel may read it in place).
+bool host_alloc_covers_bytes(const void* p, size_t bytes);
 // The self-test kernels (0 projdiv, 1 projquot, 2 normalize) on the null
 // stream; returns hipGetLastError().
 hipError_t launch_selftest(int which, unsigned long long n, unsigned long long seed,

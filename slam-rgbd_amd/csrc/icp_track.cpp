@@ -672,3 +672,19 @@ void youth_icp_track_reset(youth_icp_ctx* c)
 }
 
 }  // extern "C"
+
+namespace youth_icp {
+
+// host_alloc_covers for the RGB-D tracker's frames (rgbd_align.hip): depth and
+// colour alike lie in buffers of youth_icp_host_alloc, sized in bytes here
+bool host_alloc_covers_bytes(const void* p, size_t bytes)
+{
+    const uintptr_t a = (uintptr_t)p;
+    std::lock_guard<std::mutex> lk(g_host_mu);
+    auto it = g_host_bufs.upper_bound(a);
+    if (it == g_host_bufs.begin()) return false;
+    --it;
+    return a >= it->first && a + bytes <= it->first + it->second;
+}
+
+}  // namespace youth_icp

@@ -35,12 +35,15 @@
 
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 
 #include "icp_device.h"
 #include "icp_host.h"
+#include "youth_filter.h"
 #include "youth_rgbd.h"
 
 using namespace youth_icp;
@@ -145,6 +148,126 @@ __global__ __launch_bounds__(kRgbdPrepThreads) void k_rgbd_prep(const uint8_t* _
                 if (gray) gray[o + k] = (uint8_t)yc[k];
                 if (photo) photo[o + k] = word[k];
             }
+    }
+}
+
+// The streaming tracker's ingest: m page-locked host frames,
+// depth int16 [N] and RGB uint8 [N][3] each, fetched over PCIe by the GPU
+// itself, as k_pull_frames does for depth alone and for its reason (a copy
+// engine transfer stalled the submitting thread for milliseconds about once
+// per run).  RGB crosses the bus once and leaves as intensity: 5 B/px in,
+// 3 B/px out (depth 2, Y 1); the RGB bytes are written only where the caller
+// wants them (rgb non-null: 8 B/px out).  grid (wg, m), 64 lanes; depth as
+// 16-byte non-temporal loads, four in flight per lane; colour in units of 16
+// pixels, three 16-byte loads and one 16-byte Y store, two units in flight.
+// Each vector body runs where its source and destinations are 16-byte
+// aligned, the rest of the frame (or all of it) element by element with the
+// same integer arithmetic: the bytes are the same either way.  No LDS, no
+// atomics, nothing waits on another workgroup.
+struct RgbdFramePtrs {
+    const int16_t* depth[YOUTH_TRACK_MAX_BATCH];
+    const uint8_t* rgb[YOUTH_TRACK_MAX_BATCH];
+};
+
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+
+// four pixels' Y from their twelve bytes in three words (load_y4's unpacking)
+__device__ __forceinline__ unsigned luma_word(unsigned a, unsigned b, unsigned c)
+{
+    return luma8(a & 255u, (a >> 8) & 255u, (a >> 16) & 255u) |
+           (luma8(a >> 24, b & 255u, (b >> 8) & 255u) << 8) |
+           (luma8((b >> 16) & 255u, b >> 24, c & 255u) << 16) |
+           (luma8((c >> 8) & 255u, (c >> 16) & 255u, c >> 24) << 24);
+}
+
+__device__ __forceinline__ v4u luma_unit(v4u a, v4u b, v4u c)
+{
+    return v4u{luma_word(a.x, a.y, a.z), luma_word(a.w, b.x, b.y), luma_word(b.z, b.w, c.x),
+               luma_word(c.y, c.z, c.w)};
+}
+
+__global__ __launch_bounds__(64) void k_rgbd_pull(RgbdFramePtrs fp, int16_t* __restrict__ depth,
+                                                  uint8_t* __restrict__ gray,
+                                                  uint8_t* __restrict__ rgb, int N, int m)
+{
+    const int f = blockIdx.y;
+    if (f >= m) return;
+    const int stride = gridDim.x * 64;
+    const int t0 = blockIdx.x * 64 + threadIdx.x;
+    {
+        const int16_t* __restrict__ s16 = fp.depth[f];
+        int16_t* __restrict__ d16 = depth + (size_t)f * N;
+        int done = 0;
+        if ((((uintptr_t)s16 | (uintptr_t)d16) & 15) == 0) {
+            const v4u* __restrict__ s = reinterpret_cast<const v4u*>(s16);
+            v4u* __restrict__ d = reinterpret_cast<v4u*>(d16);
+            const int nv = N / 8;
+            int i = t0;
+            for (; i + 3 * stride < nv; i += 4 * stride) {
+                const v4u a = __builtin_nontemporal_load(s + i);
+                const v4u b = __builtin_nontemporal_load(s + i + stride);
+                const v4u c = __builtin_nontemporal_load(s + i + 2 * stride);
+                const v4u e = __builtin_nontemporal_load(s + i + 3 * stride);
+                d[i] = a;
+                d[i + stride] = b;
+                d[i + 2 * stride] = c;
+                d[i + 3 * stride] = e;
+            }
+            for (; i < nv; i += stride) d[i] = __builtin_nontemporal_load(s + i);
+            done = nv * 8;
+        }
+        for (int i = done + t0; i < N; i += stride) d16[i] = s16[i];
+    }
+    const uint8_t* __restrict__ sc = fp.rgb[f];
+    uint8_t* __restrict__ g8 = gray + (size_t)f * N;
+    uint8_t* __restrict__ c8 = rgb ? rgb + (size_t)f * N * 3 : nullptr;
+    int done = 0;
+    if ((((uintptr_t)sc | (uintptr_t)g8 | (uintptr_t)c8) & 15) == 0) {
+        const v4u* __restrict__ s = reinterpret_cast<const v4u*>(sc);
+        v4u* __restrict__ g = reinterpret_cast<v4u*>(g8);
+        v4u* __restrict__ c = reinterpret_cast<v4u*>(c8);
+        const int nu = N / 16;  // units of 16 pixels: 48 bytes in, 16 bytes of Y out
+        int i = t0;
+        for (; i + stride < nu; i += 2 * stride) {
+            const int j = i + stride;
+            const v4u a0 = __builtin_nontemporal_load(s + 3 * (size_t)i);
+            const v4u a1 = __builtin_nontemporal_load(s + 3 * (size_t)i + 1);
+            const v4u a2 = __builtin_nontemporal_load(s + 3 * (size_t)i + 2);
+            const v4u b0 = __builtin_nontemporal_load(s + 3 * (size_t)j);
+            const v4u b1 = __builtin_nontemporal_load(s + 3 * (size_t)j + 1);
+            const v4u b2 = __builtin_nontemporal_load(s + 3 * (size_t)j + 2);
+            g[i] = luma_unit(a0, a1, a2);
+            g[j] = luma_unit(b0, b1, b2);
+            if (c) {
+                c[3 * (size_t)i] = a0;
+                c[3 * (size_t)i + 1] = a1;
+                c[3 * (size_t)i + 2] = a2;
+                c[3 * (size_t)j] = b0;
+                c[3 * (size_t)j + 1] = b1;
+                c[3 * (size_t)j + 2] = b2;
+            }
+        }
+        for (; i < nu; i += stride) {
+            const v4u a0 = __builtin_nontemporal_load(s + 3 * (size_t)i);
+            const v4u a1 = __builtin_nontemporal_load(s + 3 * (size_t)i + 1);
+            const v4u a2 = __builtin_nontemporal_load(s + 3 * (size_t)i + 2);
+            g[i] = luma_unit(a0, a1, a2);
+            if (c) {
+                c[3 * (size_t)i] = a0;
+                c[3 * (size_t)i + 1] = a1;
+                c[3 * (size_t)i + 2] = a2;
+            }
+        }
+        done = nu * 16;
+    }
+    for (int i = done + t0; i < N; i += stride) {
+        const unsigned r = sc[3 * (size_t)i], gg = sc[3 * (size_t)i + 1], b = sc[3 * (size_t)i + 2];
+        g8[i] = (uint8_t)luma8(r, gg, b);
+        if (c8) {
+            c8[3 * (size_t)i] = (uint8_t)r;
+            c8[3 * (size_t)i + 1] = (uint8_t)gg;
+            c8[3 * (size_t)i + 2] = (uint8_t)b;
+        }
     }
 }
 
@@ -344,6 +467,35 @@ struct youth_rgbd_ctx {
     double* d_neq = nullptr;       // [kRgbdNeq]
     int last_pairs = 0, last_iters = 0;
     hipStream_t last_stream = nullptr;
+
+    // streaming tracker (youth_rgbd_track_*).  Depth and
+    // intensity: two banks of trk_b frame slots, a submission's frames in the
+    // bank the one before it did not use.  Records and words: slot 0 the
+    // reference, slots 1 .. m the submission's frames (one bank: preps and
+    // iterations of all submissions are ordered on the context's stream).
+    int trk_b = 1;            // frames per submission at most; fixes the reduce geometry
+    int trk_ref = -1;         // record / word slot of the reference (-1: none yet)
+    int trk_bank = 0;         // bank of the next submission
+    bool flt_on = false;
+    youth_filter_params flt{8, 96};
+    int16_t* d_raw = nullptr;  // [trk_raw_cap][N] unfiltered frames of one submission
+    int trk_raw_cap = 0;
+    int pull_wg = 0;           // YOUTH_RGBD_PULL_WG: k_rgbd_pull workgroups per frame (0: auto)
+    hipEvent_t pull_ev = nullptr;  // youth_rgbd_pull_host: staging -> device done
+    int16_t* pull_stage_d = nullptr;  // its pinned staging of pageable frames
+    uint8_t* pull_stage_c = nullptr;
+    int pull_stage_cap = 0;
+    struct Sub {
+        int m = 0, next = 0;      // frames of the submission, the next to collect
+        int first_has_ref = 0;
+        double* res = nullptr;    // pinned: [trk_b][16] poses, then [trk_b] status words
+        int res_cap = 0;          // frames `res` holds
+        int16_t* stage_d = nullptr;  // pinned staging of pageable frames [stage_cap][N]
+        uint8_t* stage_c = nullptr;  //                                   [stage_cap][N][3]
+        int stage_cap = 0;
+        hipEvent_t h2d = nullptr, done = nullptr;
+    } sub[2];
+    int sub_head = 0, sub_n = 0;  // oldest submission in flight, submissions in flight
 };
 
 static int rgbd_size_ok(const char* who, int n, int W, int H)
@@ -388,13 +540,14 @@ static int rgbd_ensure_stats(youth_rgbd_ctx* r, int iters)
 
 // One k_rgbd_reduce launch over n_pairs pairs: iteration `it` with its fused
 // solve, or (neq_out) the sums alone.
+// geo_pairs: the pair count the chunks are planned for (0: n_pairs).
 static int rgbd_launch_reduce(youth_rgbd_ctx* r, hipStream_t s, const int16_t* dsrc,
                               const uint8_t* gsrc, PairMap pm, int n_pairs, int it,
-                              double* neq_out)
+                              double* neq_out, int geo_pairs = 0)
 {
     youth_icp_ctx* c = r->icp;
     int chunk = 0;
-    const int nb = rgbd_geometry(r, n_pairs, &chunk);
+    const int nb = rgbd_geometry(r, geo_pairs > 0 ? geo_pairs : n_pairs, &chunk);
     int rc = grow_device_buffer(g_icp_err, &r->d_part, &r->part_cap,
                                 (size_t)nb * n_pairs * kRgbdStride);
     if (rc) return rc;
@@ -420,6 +573,7 @@ static int rgbd_align(youth_rgbd_ctx* r, hipStream_t s, const int16_t* dsrc, con
                       const double* T_init_host, float* d_T_out)
 {
     youth_icp_ctx* c = r->icp;
+    r->trk_ref = -1;  // the workspace is shared: the streaming tracker starts anew
     const double* dTi = nullptr;
     int rc = upload_T_init(c, s, T_init_host, n_pairs, &dTi);
     if (rc) return rc;
@@ -464,10 +618,21 @@ void youth_rgbd_destroy(youth_rgbd_ctx* r)
         (void)hipSetDevice(r->icp->device);
         if (r->last_stream) (void)hipStreamSynchronize(r->last_stream);
         (void)hipStreamSynchronize(r->icp->stream);
+        if (r->icp->xfer) (void)hipStreamSynchronize(r->icp->xfer);
     }
-    void* bufs[] = {r->d_photo, r->d_gray, r->d_rgb, r->d_part, r->d_stats, r->d_neq};
+    void* bufs[] = {r->d_photo, r->d_gray, r->d_rgb, r->d_part, r->d_stats, r->d_neq, r->d_raw};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
+    for (auto& q : r->sub) {
+        void* pinned[] = {q.res, q.stage_d, q.stage_c};
+        for (void* b : pinned)
+            if (b) (void)hipHostFree(b);
+        if (q.h2d) (void)hipEventDestroy(q.h2d);
+        if (q.done) (void)hipEventDestroy(q.done);
+    }
+    if (r->pull_stage_d) (void)hipHostFree(r->pull_stage_d);
+    if (r->pull_stage_c) (void)hipHostFree(r->pull_stage_c);
+    if (r->pull_ev) (void)hipEventDestroy(r->pull_ev);
     youth_icp_destroy(r->icp);
     delete r;
 }
@@ -505,6 +670,8 @@ youth_rgbd_ctx* youth_rgbd_create(int device, int W, int H, int max_frames,
     r->pk.ky = (0.5f * r->pk.w) * c->K.fy;
     const char* ck = getenv("YOUTH_RGBD_CHUNKS");  // test knob
     if (ck && atoi(ck) > 0) r->chunks = atoi(ck);
+    const char* pw = getenv("YOUTH_RGBD_PULL_WG");  // tuning knob (tools/rgbd_track_bench.py)
+    if (pw && atoi(pw) > 0) r->pull_wg = std::min(atoi(pw), 1024);
     const size_t N = (size_t)c->N, F = (size_t)r->frames;
     hipError_t e;
     if ((e = hipMalloc(&r->d_photo, F * N * sizeof(unsigned))) != hipSuccess ||
@@ -652,6 +819,7 @@ int youth_rgbd_reduce_host(youth_rgbd_ctx* r, const int16_t* src_depth, const ui
     if (rc) return rc;
     hipStream_t s = c->stream;
     const size_t N = c->N;
+    r->trk_ref = -1;  // the workspace is shared: the streaming tracker starts anew
     // frame 0 the source, frame 1 the target
     HIP_TRY(hipMemcpyAsync(c->d_depth, src_depth, N * sizeof(int16_t), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(c->d_depth + N, dst_depth, N * sizeof(int16_t), hipMemcpyHostToDevice, s));
@@ -695,6 +863,359 @@ int youth_rgbd_track_host_sequence(youth_rgbd_ctx* r, const int16_t* depth, cons
     rc = youth_rgbd_get_poses(r, n_frames - 1, T_rel, nullptr, status);
     if (rc) return rc;
     return n_frames - 1;
+}
+
+}  // extern "C"
+
+// ==================================================== streaming tracker ==
+// youth_rgbd_track_* (DESIGN.md §14).  One submission of m <= trk_b frames:
+//
+//   transfer stream  wait for the last reader of the bank; k_rgbd_pull of the
+//                    m frames into the bank's depth (or the filter's raw
+//                    staging) and intensity slots; the depth filter; event
+//   context stream   wait for that event; the reference's record and word
+//                    copied into slot 0; k_prep and k_rgbd_prep<1> of the m
+//                    new frames into slots 1 .. m; k_init; prm.iters launches
+//                    of k_rgbd_reduce over the pairs (frame i against frame
+//                    i - 1, the first against slot 0) on the geometry of
+//                    trk_b pairs; poses and statuses to the submission's
+//                    pinned result slot; event
+//
+// Every frame is prepped once, as a new frame; what a pair computes depends on
+// its two frames and on trk_b alone, not on the submission it travelled in.
+// k_rgbd_reduce holds no wait (its last arriver sums, handoff_publish /
+// handoff_sum), so no status here carries YOUTH_STATUS_TIMEOUT.
+
+// Page-locked staging for m frames (grown while nothing reads it).
+static int rgbd_ensure_stage(youth_rgbd_ctx* r, int16_t** d, uint8_t** c, int* cap, int m)
+{
+    if (*cap >= m) return YOUTH_OK;
+    const size_t N = (size_t)r->icp->N;
+    if (*d) (void)hipHostFree(*d);
+    if (*c) (void)hipHostFree(*c);
+    *d = nullptr;
+    *c = nullptr;
+    *cap = 0;
+    HIP_TRY(hipHostMalloc((void**)d, (size_t)m * N * sizeof(int16_t), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void**)c, (size_t)m * N * 3, hipHostMallocDefault));
+    *cap = m;
+    return YOUTH_OK;
+}
+
+// Whether every frame lies in page-locked memory the GPU may read in place.
+static bool rgbd_frames_pinned(const youth_rgbd_ctx* r, const int16_t* const* depth,
+                               const uint8_t* const* rgb, int m)
+{
+    const size_t N = (size_t)r->icp->N;
+    for (int i = 0; i < m; ++i)
+        if (!host_alloc_covers_bytes(depth[i], N * sizeof(int16_t)) ||
+            !host_alloc_covers_bytes(rgb[i], N * 3))
+            return false;
+    return true;
+}
+
+// The frames k_rgbd_pull reads: the caller's where page-locked, else copies in
+// the staging (streaming stores: the GPU reads them next, host_copy.h).
+static void rgbd_stage_frames(const youth_rgbd_ctx* r, const int16_t* const* depth,
+                              const uint8_t* const* rgb, int m, int16_t* stage_d, uint8_t* stage_c,
+                              const int16_t** d_out, const uint8_t** c_out)
+{
+    const size_t N = (size_t)r->icp->N;
+    for (int i = 0; i < m; ++i) {
+        d_out[i] = depth[i];
+        c_out[i] = rgb[i];
+        if (!stage_d) continue;
+        if (!host_alloc_covers_bytes(depth[i], N * sizeof(int16_t))) {
+            youth::stream_copy(stage_d + (size_t)i * N, depth[i], N * sizeof(int16_t));
+            d_out[i] = stage_d + (size_t)i * N;
+        }
+        if (!host_alloc_covers_bytes(rgb[i], N * 3)) {
+            youth::stream_copy(stage_c + (size_t)i * N * 3, rgb[i], N * 3);
+            c_out[i] = stage_c + (size_t)i * N * 3;
+        }
+    }
+}
+
+static int rgbd_launch_pull(youth_rgbd_ctx* r, hipStream_t s, const int16_t* const* depth,
+                            const uint8_t* const* rgb, int m, int16_t* d_depth, uint8_t* d_gray,
+                            uint8_t* d_rgb)
+{
+    RgbdFramePtrs fp{};
+    for (int i = 0; i < m; ++i) {
+        fp.depth[i] = depth[i];
+        fp.rgb[i] = rgb[i];
+    }
+    // ~32 workgroups per launch, as k_pull_frames: the bus's latency is hidden
+    // by loads in flight, not by occupancy
+    const int wg = r->pull_wg > 0 ? r->pull_wg : std::max(4, 32 / m);
+    hipLaunchKernelGGL(k_rgbd_pull, dim3(wg, m), dim3(64), 0, s, fp, d_depth, d_gray, d_rgb,
+                       r->icp->N, m);
+    HIP_TRY(hipGetLastError());
+    return YOUTH_OK;
+}
+
+static int rgbd_check_frames(const char* who, const int16_t* const* depth,
+                             const uint8_t* const* rgb, int m, int max_m)
+{
+    if (!depth || !rgb) return g_icp_err.set(YOUTH_EINVAL, "%s: null frame array", who);
+    if (m < 1 || m > max_m)
+        return g_icp_err.set(YOUTH_EINVAL, "%s: %d frames (need 1 .. %d)", who, m, max_m);
+    for (int i = 0; i < m; ++i)
+        if (!depth[i] || !rgb[i])
+            return g_icp_err.set(YOUTH_EINVAL, "%s: frame %d has a null %s pointer", who, i,
+                                 depth[i] ? "colour" : "depth");
+    return YOUTH_OK;
+}
+
+static int rgbd_track_pending(const youth_rgbd_ctx* r)
+{
+    int n = 0;
+    for (int k = 0; k < r->sub_n; ++k) {
+        const auto& q = r->sub[(r->sub_head + k) % 2];
+        n += q.m - q.next;
+    }
+    return n;
+}
+
+// Lazily: the transfer stream, the two submissions' events and result slots.
+static int rgbd_ensure_track(youth_rgbd_ctx* r)
+{
+    youth_icp_ctx* c = r->icp;
+    if (!c->xfer) HIP_TRY(hipStreamCreateWithFlags(&c->xfer, hipStreamNonBlocking));
+    for (auto& q : r->sub) {
+        if (!q.h2d) HIP_TRY(hipEventCreateWithFlags(&q.h2d, hipEventDisableTiming));
+        if (!q.done) HIP_TRY(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
+        if (q.res_cap < r->trk_b) {
+            if (q.res) (void)hipHostFree(q.res);
+            q.res = nullptr;
+            q.res_cap = 0;
+            HIP_TRY(hipHostMalloc((void**)&q.res, (size_t)r->trk_b * 17 * sizeof(double),
+                                  hipHostMallocDefault));
+            q.res_cap = r->trk_b;
+        }
+    }
+    return YOUTH_OK;
+}
+
+// youth_icp_track_collect's wait: poll the event for up to 2 ms before the
+// runtime's blocking wait (a sleeping wait's wake-up costs a backlogged worker
+// more than the align it waits for)
+static hipError_t rgbd_track_wait(hipEvent_t ev)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+        const hipError_t e = hipEventQuery(ev);
+        if (e != hipErrorNotReady) return e;
+        if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
+    }
+    return hipEventSynchronize(ev);
+}
+
+static int rgbd_track_enqueue(youth_rgbd_ctx* r, youth_rgbd_ctx::Sub& q,
+                              const int16_t* const* depth, const uint8_t* const* rgb, int m)
+{
+    youth_icp_ctx* c = r->icp;
+    hipStream_t s = c->stream, xs = c->xfer;
+    const size_t N = (size_t)c->N;
+    const int d0 = r->trk_bank * r->trk_b;  // first depth / intensity slot of the bank
+    int16_t* const dbank = c->d_depth + (size_t)d0 * N;
+    uint8_t* const gbank = r->d_gray + (size_t)d0 * N;
+    // the bank's last reader is the submission that used this entry before
+    if (q.m > 0) HIP_TRY(hipStreamWaitEvent(xs, q.done, 0));
+    int rc = rgbd_launch_pull(r, xs, depth, rgb, m, r->flt_on ? r->d_raw : dbank, gbank, nullptr);
+    if (rc) return rc;
+    if (r->flt_on) {
+        rc = youth_depth_filter_device(c->device, r->d_raw, dbank, m, c->W, c->H, &r->flt, xs);
+        if (rc) return g_icp_err.set(rc, "depth filter: %s", youth_depth_filter_last_error());
+    }
+    HIP_TRY(hipEventRecord(q.h2d, xs));
+    HIP_TRY(hipStreamWaitEvent(s, q.h2d, 0));
+    const int ref = r->trk_ref;
+    if (ref > 0) {
+        HIP_TRY(hipMemcpyAsync(c->d_rec, c->d_rec + (size_t)ref * c->P, c->P * sizeof(float4),
+                               hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(r->d_photo, r->d_photo + (size_t)ref * N, N * sizeof(unsigned),
+                               hipMemcpyDeviceToDevice, s));
+    }
+    rc = launch_prep(c, s, dbank, m, 1, false);
+    if (rc) return rc;
+    rc = rgbd_launch_prep(s, gbank, 1, m, c->W, c->H, nullptr, r->d_photo + N);
+    if (rc) return rc;
+    // without a reference the first frame is prepped only
+    const int pairs = ref >= 0 ? m : m - 1;
+    if (pairs > 0) {
+        const int iters = r->prm.iters;
+        rc = rgbd_ensure_stats(r, iters > 0 ? iters : 1);
+        if (rc) return rc;
+        rc = launch_init(c, s, nullptr, pairs, iters, false);
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(c->d_arrivals, 0, (size_t)pairs * sizeof(unsigned), s));
+        const PairMap pm{ref >= 0 ? d0 : d0 + 1, ref >= 0 ? 0 : 1};
+        for (int it = 0; it < iters; ++it) {
+            rc = rgbd_launch_reduce(r, s, c->d_depth, r->d_gray, pm, pairs, it, nullptr, r->trk_b);
+            if (rc) return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(q.res, c->d_T64, (size_t)pairs * 16 * sizeof(double),
+                               hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(q.res + (size_t)q.res_cap * 16, c->d_status,
+                               (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        r->last_pairs = pairs;
+        r->last_iters = iters;
+    }
+    r->last_stream = s;
+    HIP_TRY(hipEventRecord(q.done, s));
+    return YOUTH_OK;
+}
+
+extern "C" {
+
+int youth_rgbd_track_set_batch(youth_rgbd_ctx* r, int b)
+{
+    static const char* who = "youth_rgbd_track_set_batch";
+    if (!r) return g_icp_err.set(YOUTH_EINVAL, "%s: null context", who);
+    if (b < 1 || b > YOUTH_TRACK_MAX_BATCH)
+        return g_icp_err.set(YOUTH_EINVAL, "%s: batch %d (need 1 .. %d)", who, b,
+                             YOUTH_TRACK_MAX_BATCH);
+    if (2 * b > r->frames - 1)
+        return g_icp_err.set(YOUTH_EINVAL, "%s: batch %d needs max_frames >= %d (the context has %d)",
+                             who, b, 2 * b, r->frames - 1);
+    if (r->sub_n > 0)
+        return g_icp_err.set(YOUTH_EINVAL, "%s: %d frames pending (collect them first)", who,
+                             rgbd_track_pending(r));
+    const int old = r->trk_b;
+    r->trk_b = b;
+    r->trk_bank = 0;
+    for (auto& q : r->sub) q.m = 0;  // collected: nothing reads the banks
+    return old;
+}
+
+int youth_rgbd_track_set_depth_filter(youth_rgbd_ctx* r, const youth_filter_params* P)
+{
+    static const char* who = "youth_rgbd_track_set_depth_filter";
+    if (!r) return g_icp_err.set(YOUTH_EINVAL, "%s: null context", who);
+    if (P && !filter_params_ok(P))
+        return g_icp_err.set(YOUTH_EINVAL, "%s: t0 %d, t2 %d (need 1 <= t0 <= 255, 0 <= t2 <= 1000)",
+                             who, P->t0, P->t2);
+    if (r->sub_n > 0)
+        return g_icp_err.set(YOUTH_EINVAL, "%s: %d frames pending (collect them first)", who,
+                             rgbd_track_pending(r));
+    if (P) r->flt = *P;
+    r->flt_on = P != nullptr;
+    return YOUTH_OK;
+}
+
+int youth_rgbd_track_submit(youth_rgbd_ctx* r, const int16_t* const* depth,
+                            const uint8_t* const* rgb, int n_frames)
+{
+    static const char* who = "youth_rgbd_track_submit";
+    if (!r) return g_icp_err.set(YOUTH_EINVAL, "%s: null context", who);
+    int rc = rgbd_check_frames(who, depth, rgb, n_frames, r->trk_b);
+    if (rc) return rc;
+    if (r->sub_n >= 2)
+        return g_icp_err.set(YOUTH_EINVAL, "%s: two submissions in flight (collect one first)", who);
+    youth_icp_ctx* c = r->icp;
+    rc = bind_device(c);
+    if (rc) return rc;
+    rc = rgbd_ensure_track(r);
+    if (rc) return rc;
+    if (r->flt_on) {
+        rc = grow_device_buffer(g_icp_err, &r->d_raw, &r->trk_raw_cap, r->trk_b, (size_t)c->N);
+        if (rc) return rc;
+    }
+    auto& q = r->sub[(r->sub_head + r->sub_n) % 2];
+    const int16_t* dp[YOUTH_TRACK_MAX_BATCH];
+    const uint8_t* cp[YOUTH_TRACK_MAX_BATCH];
+    const bool stage = !rgbd_frames_pinned(r, depth, rgb, n_frames);
+    if (stage) {  // the entry's staging is free: its last submission has been collected
+        rc = rgbd_ensure_stage(r, &q.stage_d, &q.stage_c, &q.stage_cap, r->trk_b);
+        if (rc) return rc;
+    }
+    rgbd_stage_frames(r, depth, rgb, n_frames, stage ? q.stage_d : nullptr, q.stage_c, dp, cp);
+    rc = rgbd_track_enqueue(r, q, dp, cp, n_frames);
+    if (rc) {
+        // nothing of these frames is kept: wait for what was enqueued, and the
+        // next frame starts a new sequence (the record slots may be half written)
+        (void)hipStreamSynchronize(c->xfer);
+        (void)hipStreamSynchronize(c->stream);
+        r->trk_ref = -1;
+        return rc;
+    }
+    q.m = n_frames;
+    q.next = 0;
+    q.first_has_ref = r->trk_ref >= 0 ? 1 : 0;
+    r->trk_ref = n_frames;  // the last new frame's record / word slot
+    r->trk_bank ^= 1;
+    ++r->sub_n;
+    return YOUTH_OK;
+}
+
+int youth_rgbd_track_collect(youth_rgbd_ctx* r, double* T_rel, int* has_ref)
+{
+    static const char* who = "youth_rgbd_track_collect";
+    if (!r || !T_rel) return g_icp_err.set(YOUTH_EINVAL, "%s: null %s", who, r ? "T_rel" : "context");
+    if (r->sub_n == 0) return g_icp_err.set(YOUTH_EINVAL, "%s: no frame pending", who);
+    int rc = bind_device(r->icp);
+    if (rc) return rc;
+    auto& q = r->sub[r->sub_head];
+    const hipError_t e = rgbd_track_wait(q.done);
+    const int i = q.next++;
+    if (q.next == q.m) {
+        r->sub_head ^= 1;
+        --r->sub_n;
+    }
+    HIP_TRY(e);
+    const int has = (i > 0 || q.first_has_ref) ? 1 : 0;
+    if (has_ref) *has_ref = has;
+    for (int k = 0; k < 16; ++k) T_rel[k] = (k % 5) == 0 ? 1.0 : 0.0;
+    if (!has) return 0;
+    const int p = q.first_has_ref ? i : i - 1;
+    for (int k = 0; k < 12; ++k) T_rel[k] = q.res[(size_t)p * 16 + k];
+    int32_t st;
+    memcpy(&st, reinterpret_cast<const char*>(q.res + (size_t)q.res_cap * 16) + (size_t)p * sizeof(st),
+           sizeof(st));
+    return st;
+}
+
+int youth_rgbd_track_pending(const youth_rgbd_ctx* r) { return r ? rgbd_track_pending(r) : 0; }
+
+int youth_rgbd_track_reset(youth_rgbd_ctx* r)
+{
+    static const char* who = "youth_rgbd_track_reset";
+    if (!r) return g_icp_err.set(YOUTH_EINVAL, "%s: null context", who);
+    if (r->sub_n > 0)
+        return g_icp_err.set(YOUTH_EINVAL, "%s: %d frames pending (collect them first)", who,
+                             rgbd_track_pending(r));
+    r->trk_ref = -1;
+    return YOUTH_OK;
+}
+
+int youth_rgbd_pull_host(youth_rgbd_ctx* r, const int16_t* const* depth, const uint8_t* const* rgb,
+                         int m, int16_t* d_depth, uint8_t* d_gray, uint8_t* d_rgb, void* stream)
+{
+    static const char* who = "youth_rgbd_pull_host";
+    if (!r) return g_icp_err.set(YOUTH_EINVAL, "%s: null context", who);
+    int rc = rgbd_check_frames(who, depth, rgb, m, YOUTH_TRACK_MAX_BATCH);
+    if (rc) return rc;
+    if (!d_depth || !d_gray) return g_icp_err.set(YOUTH_EINVAL, "%s: null destination", who);
+    rc = bind_device(r->icp);
+    if (rc) return rc;
+    hipStream_t s = pick_stream(r->icp, stream);
+    const int16_t* dp[YOUTH_TRACK_MAX_BATCH];
+    const uint8_t* cp[YOUTH_TRACK_MAX_BATCH];
+    const bool stage = !rgbd_frames_pinned(r, depth, rgb, m);
+    if (stage) {
+        // one staging for this entry point: the pull before it must have read it
+        if (!r->pull_ev) HIP_TRY(hipEventCreateWithFlags(&r->pull_ev, hipEventDisableTiming));
+        HIP_TRY(hipEventSynchronize(r->pull_ev));
+        rc = rgbd_ensure_stage(r, &r->pull_stage_d, &r->pull_stage_c, &r->pull_stage_cap,
+                               YOUTH_TRACK_MAX_BATCH);
+        if (rc) return rc;
+    }
+    rgbd_stage_frames(r, depth, rgb, m, stage ? r->pull_stage_d : nullptr, r->pull_stage_c, dp, cp);
+    rc = rgbd_launch_pull(r, s, dp, cp, m, d_depth, d_gray, d_rgb);
+    if (rc) return rc;
+    if (stage) HIP_TRY(hipEventRecord(r->pull_ev, s));
+    return YOUTH_OK;
 }
 
 }  // extern "C"

@@ -10,7 +10,9 @@
 // Differences from the reference that are deliberate:
 //  - processSlamFrame keeps depth as int16 millimetres (the GPU converts with
 //    the viewer's /1000.0f rule, viewerModule.c:343) instead of
-//    convertTo(CV_32F, 1/1000) (SLAM.cpp:154-155); colour is ignored (ICP).
+//    convertTo(CV_32F, 1/1000) (SLAM.cpp:154-155); colour is ignored unless
+//    YOUTH_SLAM_RGBD=1 (RGB-D tracking through slam_rgbd_hooks.h) or
+//    YOUTH_SLAM_MAP_COLOR=1 (colour for the voxel map) asks for it.
 //  - every frame path returns a value (SLAM.cpp:172-174 falls off the end).
 //  - the running flags are atomics (the reference shares plain bools).
 
@@ -34,6 +36,7 @@
 
 #include "host_copy.h"
 #include "slam_map_hooks.h"
+#include "slam_rgbd_hooks.h"
 #include "youth_map.h"
 #include "youth_icp.h"
 
@@ -114,6 +117,11 @@ struct youth_frame_queue {
         bool pinned = false;
         int w = 0, h = 0;
         uint32_t ts = 0;
+        // the frame's colour, RGB uint8 [h][w][3], in a buffer of its own
+        // (null: colour is not carried); pooled apart from the depth buffers
+        uint8_t* cbuf = nullptr;
+        size_t ccap = 0;      // bytes the buffer holds
+        bool cpinned = false;
     };
     static constexpr size_t kPinnedBytes = (size_t)256 << 20;
     static constexpr size_t kPoolMax = 48;  // pageable buffers kept
@@ -136,12 +144,31 @@ struct youth_frame_queue {
     std::mutex copier_mu;
     size_t pinned_bytes = 0;  // page-locked bytes allocated and not freed
     int pinned_count = 0;     // page-locked buffers allocated and not freed
+    // colour (the SLAM module with YOUTH_SLAM_RGBD / YOUTH_SLAM_MAP_COLOR): a
+    // pushed frame may bring a colour buffer; page-locked ones are pooled and
+    // prefilled like the depth buffers, with a budget of their own
+    bool color = false;
+    std::vector<Item> cpool;  // page-locked colour buffers (cbuf / ccap only)
+    size_t cpinned_bytes = 0;
+    int cpinned_count = 0;
 };
 
 namespace {
 
 void buf_free(youth_frame_queue* q, youth_frame_queue::Item& it)
 {
+    if (it.cbuf) {
+        if (it.cpinned) {
+            youth_icp_host_free(reinterpret_cast<int16_t*>(it.cbuf));
+            std::lock_guard<std::mutex> lk(q->mu);
+            q->cpinned_bytes -= it.ccap;
+            --q->cpinned_count;
+        } else {
+            free(it.cbuf);
+        }
+        it.cbuf = nullptr;
+        it.ccap = 0;
+    }
     if (!it.buf) return;
     if (it.pinned) {
         youth_icp_host_free(it.buf);
@@ -206,6 +233,15 @@ bool buf_new_pinned(youth_frame_queue* q, size_t n, youth_frame_queue::Item& it)
 void pool_put_locked(youth_frame_queue* q, youth_frame_queue::Item& it,
                      std::vector<youth_frame_queue::Item>& to_free)
 {
+    if (it.cbuf) {  // the colour buffer apart: page-locked to its pool, else freed
+        youth_frame_queue::Item c;
+        c.cbuf = it.cbuf;
+        c.ccap = it.ccap;
+        c.cpinned = it.cpinned;
+        (c.cpinned ? q->cpool : to_free).push_back(c);
+        it.cbuf = nullptr;
+        it.ccap = 0;
+    }
     if (!it.buf) return;
     if (it.pinned || (!q->pinned && q->pool.size() < q->kPoolMax))
         q->pool.push_back(it);
@@ -218,6 +254,106 @@ void free_all(youth_frame_queue* q, std::vector<youth_frame_queue::Item>& v)
 {
     for (auto& it : v) buf_free(q, it);
     v.clear();
+}
+
+// A new page-locked colour buffer of n bytes while its budget lasts (worker / init).
+bool color_new_pinned(youth_frame_queue* q, size_t n, youth_frame_queue::Item& it)
+{
+    {
+        std::lock_guard<std::mutex> lk(q->mu);
+        if (q->cpinned_bytes + n > 3 * q->kPinnedBytes) return false;
+        q->cpinned_bytes += n;
+        ++q->cpinned_count;
+    }
+    it.cbuf = reinterpret_cast<uint8_t*>(youth_icp_host_alloc((n + 1) / 2));
+    if (!it.cbuf) {
+        std::lock_guard<std::mutex> lk(q->mu);
+        q->cpinned_bytes -= n;
+        --q->cpinned_count;
+        return false;
+    }
+    it.cpinned = true;
+    it.ccap = n;
+    return true;
+}
+
+// A colour buffer of >= n bytes for the producer: pooled, else new pageable.
+bool color_get(youth_frame_queue* q, size_t n, youth_frame_queue::Item& it)
+{
+    {
+        std::lock_guard<std::mutex> lk(q->mu);
+        for (size_t k = q->cpool.size(); k-- > 0;) {
+            if (q->cpool[k].ccap < n) continue;
+            it.cbuf = q->cpool[k].cbuf;
+            it.ccap = q->cpool[k].ccap;
+            it.cpinned = true;
+            q->cpool.erase(q->cpool.begin() + (long)k);
+            return true;
+        }
+    }
+    it.cbuf = static_cast<uint8_t*>(malloc(n));
+    it.cpinned = false;
+    it.ccap = it.cbuf ? n : 0;
+    return it.cbuf != nullptr;
+}
+
+// queue_prefill's colour part: page-locked colour buffers of n bytes until
+// `count` exist; pooled ones smaller than n are freed first.
+int color_prefill(youth_frame_queue* q, size_t n, int count)
+{
+    std::vector<youth_frame_queue::Item> to_free;
+    {
+        std::lock_guard<std::mutex> lk(q->mu);
+        std::vector<youth_frame_queue::Item> keep;
+        for (auto& it : q->cpool) (it.ccap >= n ? keep : to_free).push_back(it);
+        q->cpool.swap(keep);
+    }
+    const int freed = (int)to_free.size();
+    for (auto& it : to_free) buf_free(q, it);
+    int added = 0;
+    for (;;) {
+        {
+            std::lock_guard<std::mutex> lk(q->mu);
+            if (q->cpinned_count >= count) break;
+        }
+        youth_frame_queue::Item it;
+        if (!color_new_pinned(q, n, it)) break;
+        std::lock_guard<std::mutex> lk(q->mu);
+        q->cpool.push_back(it);
+        ++added;
+    }
+    return added - freed;
+}
+
+// queue_release's colour part, by its rules: a page-locked buffer of at least
+// n bytes goes back to the pool; a pageable or too small one is freed and,
+// while fewer than `target` page-locked ones exist, replaced.
+int color_release(youth_frame_queue* q, youth_frame_queue::Item& it, size_t n, int target)
+{
+    if (!it.cbuf) return 0;
+    youth_frame_queue::Item c;
+    c.cbuf = it.cbuf;
+    c.ccap = it.ccap;
+    c.cpinned = it.cpinned;
+    it.cbuf = nullptr;
+    it.ccap = 0;
+    const bool keep = c.cpinned && !(n > 0 && c.ccap < n);
+    if (keep) {
+        std::lock_guard<std::mutex> lk(q->mu);
+        q->cpool.push_back(c);
+        return 0;
+    }
+    buf_free(q, c);
+    if (!q->pinned || !q->color || n == 0) return 0;
+    {
+        std::lock_guard<std::mutex> lk(q->mu);
+        if (q->cpinned_count >= target) return 0;
+    }
+    youth_frame_queue::Item fresh;
+    if (!color_new_pinned(q, n, fresh)) return 0;
+    std::lock_guard<std::mutex> lk(q->mu);
+    q->cpool.push_back(fresh);
+    return 1;
 }
 
 // The oldest frame, buffer and all (1), or 0 when empty.
@@ -236,6 +372,7 @@ int queue_take(youth_frame_queue* q, youth_frame_queue::Item& out)
 // number allocated minus the number freed.
 int queue_prefill(youth_frame_queue* q, size_t n, int count)
 {
+    if (q->color) color_prefill(q, 3 * n, count);
     std::vector<youth_frame_queue::Item> to_free;
     {
         std::lock_guard<std::mutex> lk(q->mu);
@@ -269,6 +406,7 @@ int queue_prefill(youth_frame_queue* q, size_t n, int count)
 // by a page-locked one of n values.  Returns 1 when it allocated one.
 int queue_release(youth_frame_queue* q, youth_frame_queue::Item& it, size_t n = 0, int target = 0)
 {
+    color_release(q, it, 3 * n, target);
     const bool replace = it.buf && (!it.pinned || (n > 0 && it.cap < n));
     std::vector<youth_frame_queue::Item> to_free;
     {
@@ -314,14 +452,20 @@ void youth_queue_destroy(youth_frame_queue* q)
     if (!q) return;
     std::vector<youth_frame_queue::Item> all(q->q.begin(), q->q.end());
     all.insert(all.end(), q->pool.begin(), q->pool.end());
+    all.insert(all.end(), q->cpool.begin(), q->cpool.end());
     q->q.clear();
     q->pool.clear();
+    q->cpool.clear();
     free_all(q, all);
     delete q;
 }
 
-int youth_queue_push(youth_frame_queue* q, const int16_t* depth, int width, int height,
-                     uint32_t timestamp)
+}  // extern "C"
+
+// youth_queue_push, with the frame's colour (RGB uint8 [height][width][3]) into
+// a buffer of its own where the queue carries colour and the caller has some.
+static int queue_push(youth_frame_queue* q, const int16_t* depth, const uint8_t* color, int width,
+                      int height, uint32_t timestamp)
 {
     if (!q || !depth || width <= 0 || height <= 0) return YOUTH_EINVAL;
     const size_t n = (size_t)width * (size_t)height;
@@ -329,6 +473,21 @@ int youth_queue_push(youth_frame_queue* q, const int16_t* depth, int width, int 
     int kind = 0;
     trace(YOUTH_SLAM_EV_PUSH_BEGIN, youth_queue_size(q));
     if (!buf_get(q, n, it, &kind)) return YOUTH_ENOMEM;
+    if (color && q->color) {
+        if (!color_get(q, 3 * n, it)) {
+            std::vector<youth_frame_queue::Item> back;
+            {
+                std::lock_guard<std::mutex> lk(q->mu);
+                pool_put_locked(q, it, back);
+            }
+            free_all(q, back);
+            return YOUTH_ENOMEM;
+        }
+        if (q->copy_mode == 1)
+            youth::stream_copy(it.cbuf, color, 3 * n);
+        else
+            memcpy(it.cbuf, color, 3 * n);
+    }
     bool copied = false;
     if (q->copier && n * sizeof(int16_t) >= ((size_t)256 << 10)) {
         std::unique_lock<std::mutex> lk(q->copier_mu, std::try_to_lock);
@@ -368,6 +527,14 @@ int youth_queue_push(youth_frame_queue* q, const int16_t* depth, int width, int 
     if (dropped) trace(YOUTH_SLAM_EV_DROP, dropped);
     trace(YOUTH_SLAM_EV_PUSH_END, kind);
     return dropped;
+}
+
+extern "C" {
+
+int youth_queue_push(youth_frame_queue* q, const int16_t* depth, int width, int height,
+                     uint32_t timestamp)
+{
+    return queue_push(q, depth, nullptr, width, height, timestamp);
 }
 
 int youth_queue_pop(youth_frame_queue* q, int16_t* depth_out, size_t cap, int* width,
@@ -491,6 +658,19 @@ std::atomic<const youth_slam_map_hooks*> g_map_hooks{nullptr};
 // worker records every pose under
 std::atomic<int> g_traj_len{0};
 int g_last_points = 0;
+// the RGB-D tracker's hook table (slam_rgbd_hooks.h): null unless
+// slam_rgbd.cpp is linked in.  g_rgbd: the module tracks with colour
+// (YOUTH_SLAM_RGBD=1 at initSlamModule, the table present); g_carry_color:
+// queue items carry a colour buffer (RGB-D mode or YOUTH_SLAM_MAP_COLOR=1)
+std::atomic<const youth_slam_rgbd_hooks*> g_rgbd_hooks{nullptr};
+std::atomic<bool> g_rgbd{false};
+std::atomic<bool> g_carry_color{false};
+
+bool env_on(const char* name)
+{
+    const char* e = getenv(name);
+    return e && *e && strcmp(e, "0") != 0;
+}
 
 void mat_mul4(const double* A, const double* B, double* C)
 {
@@ -646,7 +826,7 @@ void worker_main(int device)
         // frame's buffer (now ref_hold) is read before this returns
         if (const youth_slam_map_hooks* mh = g_map_hooks.load()) {
             const youth_intrinsics K = intrinsics_for(pr0.item.w, pr0.item.h);
-            mh->integrate(pr0.item.buf, pr0.item.w, pr0.item.h, &K, T_w_ref);
+            mh->integrate(pr0.item.buf, pr0.item.cbuf, pr0.item.w, pr0.item.h, &K, T_w_ref);
         }
     };
     while (g_process.load()) {
@@ -776,6 +956,179 @@ void worker_main(int device)
     fprintf(stderr, "youth_icp: SLAM processing thread stopped\n");
 }
 
+// The worker of RGB-D mode (YOUTH_SLAM_RGBD=1): worker_main's loop with the
+// streaming RGB-D tracker behind the hook table in place of the depth tracker.
+// Up to `batch` queued frames of one size go out as one submission, depth and
+// colour buffers in place, two submissions in flight, collected in order; the
+// tracker is planned for `batch`, so a frame's pose does not depend on the
+// queue's timing.  Simpler than worker_main in one respect: an RGB-D align
+// holds no wait between workgroups, so it never times out and
+// there is neither a realign nor a held reference frame.
+void worker_rgbd_main(int device)
+{
+    using Item = youth_frame_queue::Item;
+    fprintf(stderr, "youth_icp: SLAM processing thread started (RGB-D)\n");
+    const youth_slam_rgbd_hooks* rh = g_rgbd_hooks.load();
+    void* trk = nullptr;
+    int cw = 0, ch = 0;
+    const int batch = slam_batch();
+    bool held = false;  // a taken frame of another size (or sequence), next round
+    Item held_item;
+    double T_w_ref[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    struct Pending {
+        uint32_t ts;
+        int npts;   // valid pixels (counted for the last frame of a submission, else -1)
+        bool last;  // the last frame of its submission
+        Item item;  // its buffers, read in place until the frame is collected
+    };
+    std::deque<Pending> pend;  // submitted, not yet collected (oldest first)
+    int subs = 0;              // submissions in pend
+    auto release = [&](Item& it) {
+        if (queue_release(g_queue, it, (size_t)cw * ch, pool_target(batch))) trace(YOUTH_SLAM_EV_POOL, 1);
+    };
+    // collect the oldest submitted frame; record its pose unless a reset
+    // arrived since it was submitted
+    auto finish_one = [&](bool record) {
+        Pending pr0 = pend.front();
+        pend.pop_front();
+        subs -= pr0.last;
+        double T_rel[16];
+        int has_ref = 0;
+        trace(YOUTH_SLAM_EV_COLLECT_BEGIN, (int)pend.size() + 1);
+        const int st = rh->collect(trk, T_rel, &has_ref);
+        trace(YOUTH_SLAM_EV_COLLECT_END, pr0.last ? 1 : 0);
+        if (st < 0) fprintf(stderr, "youth_icp: tracking failed: %s\n", rh->last_error());
+        if (st >= 0 && record && !g_reset.load()) {
+            std::lock_guard<std::mutex> lk(g_slam_mu);
+            // resetSlam raises g_reset under this lock before it clears the
+            // trajectory: a frame of the old sequence that passed the check
+            // above sees the flag here and is not taken as the new origin
+            if (!g_reset.load()) {
+                if (!has_ref || g_traj.empty()) {
+                    // new sequence: this frame is the world origin
+                    double I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+                    memcpy(T_w_ref, I, sizeof(I));
+                    g_traj.clear();
+                    g_traj_len.store(0, std::memory_order_release);
+                    if (const youth_slam_map_hooks* mh = g_map_hooks.load()) mh->clear();
+                } else {
+                    // P_ref = T_rel P_new  =>  T_w_new = T_w_ref * T_rel
+                    mat_mul4(T_w_ref, T_rel, T_w_ref);
+                }
+                if (st & YOUTH_STATUS_FEW_MATCHES) g_weak[0].fetch_add(1);
+                if (st & YOUTH_STATUS_DEGENERATE) g_weak[1].fetch_add(1);
+                PoseRec pr;
+                pr.ts = pr0.ts;
+                pr.status = st;
+                memcpy(pr.T, T_w_ref, sizeof(pr.T));
+                g_traj.push_back(pr);
+                g_traj_len.store((int)g_traj.size(), std::memory_order_release);
+                if (pr0.npts >= 0) g_last_points = pr0.npts;
+                if (const youth_slam_map_hooks* mh = g_map_hooks.load()) {
+                    const youth_intrinsics K = intrinsics_for(pr0.item.w, pr0.item.h);
+                    mh->integrate(pr0.item.buf, pr0.item.cbuf, pr0.item.w, pr0.item.h, &K, T_w_ref);
+                }
+            }
+        }
+        release(pr0.item);
+    };
+    while (g_process.load()) {
+        Item items[YOUTH_TRACK_MAX_BATCH];
+        g_busy.store(true);
+        int got = 1;
+        if (held) {
+            items[0] = held_item;
+            held = false;
+        } else {
+            got = queue_take(g_queue, items[0]);
+        }
+        if (got != 1) {
+            if (!pend.empty()) {  // nothing new: finish what is in flight
+                finish_one(true);
+                continue;
+            }
+            g_busy.store(false);
+            trace(YOUTH_SLAM_EV_IDLE_BEGIN, 0);
+            {
+                // as worker_main: the predicate re-checks the queue under
+                // g_wake_mu, which processSlamFrame takes before notifying
+                std::unique_lock<std::mutex> lk(g_wake_mu);
+                g_wake_cv.wait_until(lk, std::chrono::system_clock::now() + std::chrono::milliseconds(20),
+                                     [] { return !g_process.load() || youth_queue_size(g_queue) > 0; });
+            }
+            trace(YOUTH_SLAM_EV_IDLE_END, youth_queue_size(g_queue));
+            continue;
+        }
+        const int w = items[0].w, h = items[0].h;
+        if (g_reset.exchange(false)) {
+            while (!pend.empty()) finish_one(false);  // frames of the old sequence
+            if (trk && rh->reset(trk) < 0)
+                fprintf(stderr, "youth_icp: tracker reset failed: %s\n", rh->last_error());
+        }
+        if (!trk || w != cw || h != ch) {
+            while (!pend.empty()) finish_one(true);  // the size-change rule: drain, then a new context
+            if (trk) rh->destroy(trk);
+            const youth_intrinsics K = intrinsics_for(w, h);
+            trk = rh->create(device, w, h, batch, &K);
+            cw = w;
+            ch = h;
+            if (!trk) {
+                fprintf(stderr, "youth_icp: context creation failed: %s\n", rh->last_error());
+                cw = ch = 0;
+                queue_release(g_queue, items[0]);
+                g_busy.store(false);
+                continue;
+            }
+            trace(YOUTH_SLAM_EV_POOL, queue_prefill(g_queue, (size_t)w * h, pool_target(batch)));
+        }
+        const size_t N = (size_t)w * h;
+        // two submissions in flight: with two out, finish the oldest first
+        if (subs >= 2)
+            while (!pend.empty()) {
+                const bool last = pend.front().last;
+                finish_one(true);
+                if (last) break;
+            }
+        int m = 1;
+        while (m < batch && !held) {
+            Item it;
+            if (queue_take(g_queue, it) != 1) break;
+            if (it.w == w && it.h == h && !g_reset.load()) {
+                items[m++] = it;
+            } else {
+                held_item = it;
+                held = true;
+            }
+        }
+        trace(YOUTH_SLAM_EV_TAKE, m);
+        const int16_t* fd[YOUTH_TRACK_MAX_BATCH];
+        const uint8_t* fc[YOUTH_TRACK_MAX_BATCH];
+        for (int i = 0; i < m; ++i) {
+            fd[i] = items[i].buf;
+            fc[i] = items[i].cbuf;  // never null: processSlamFrame refuses a frame without colour
+        }
+        trace(YOUTH_SLAM_EV_SUBMIT_BEGIN, m);
+        const int rc = rh->submit(trk, fd, fc, m);
+        trace(YOUTH_SLAM_EV_SUBMIT_END, rc);
+        if (rc < 0) {  // all or nothing: a refused submission leaves no frame pending
+            fprintf(stderr, "youth_icp: tracking failed: %s\n", rh->last_error());
+            for (int i = 0; i < m; ++i) release(items[i]);
+            continue;
+        }
+        if (m > 1) g_batched.fetch_add(m);
+        int npts = 0;
+        for (size_t i = 0; i < N; ++i) npts += items[m - 1].buf[i] > 0;
+        for (int i = 0; i < m; ++i)
+            pend.push_back(Pending{items[i].ts, i == m - 1 ? npts : -1, i == m - 1, items[i]});
+        ++subs;
+        if (batch == 1 && pend.size() == 2) finish_one(true);
+    }
+    while (trk && !pend.empty()) finish_one(true);
+    if (held) queue_release(g_queue, held_item);
+    if (trk) rh->destroy(trk);
+    fprintf(stderr, "youth_icp: SLAM processing thread stopped\n");
+}
+
 // Rotation matrix -> unit quaternion (x, y, z, w), Shepperd's method.
 void rot_to_quat(const double* T, double q[4])
 {
@@ -867,11 +1220,24 @@ void initSlamModule(const char* config_file, const char* vocabulary_file)
     int device = 0;
     if (const char* e = getenv("YOUTH_ICP_DEVICE")) device = atoi(e);
     if (device < 0 || device >= ndev) device = 0;
+    // colour: YOUTH_SLAM_RGBD=1 tracks with it (needs slam_rgbd.cpp's table),
+    // YOUTH_SLAM_MAP_COLOR=1 carries it to the voxel map; RGB-D implies both
+    bool rgbd = env_on("YOUTH_SLAM_RGBD");
+    const youth_slam_rgbd_hooks* rh = g_rgbd_hooks.load();
+    if (rgbd && !rh) {
+        fprintf(stderr, "youth_icp: YOUTH_SLAM_RGBD=1 refused: this build has no RGB-D tracker; "
+                        "tracking depth-only\n");
+        rgbd = false;
+    }
+    if (rgbd) rh->start();
+    g_rgbd.store(rgbd);
+    g_carry_color.store(rgbd || env_on("YOUTH_SLAM_MAP_COLOR"));
     if (!g_queue) {
         g_queue = youth_queue_create(10, 5);
         g_queue->pinned = true;  // buffers the tracker copies to the device in place
     }
     youth_queue_clear(g_queue);
+    g_queue->color = g_carry_color.load();
     // page-locked buffers for the configured frame size (the YAML's, else
     // 640x480) before the first frame: the producer never allocates them
     {
@@ -887,7 +1253,7 @@ void initSlamModule(const char* config_file, const char* vocabulary_file)
     for (auto& r : g_realigned) r.store(0);
     for (auto& r : g_weak) r.store(0);
     try {
-        g_worker = std::thread(worker_main, device);
+        g_worker = std::thread(rgbd ? worker_rgbd_main : worker_main, device);
     } catch (const std::exception& ex) {
         fprintf(stderr, "youth_icp: failed to start worker: %s\n", ex.what());
         g_process.store(false);
@@ -898,7 +1264,8 @@ void initSlamModule(const char* config_file, const char* vocabulary_file)
         g_running.store(true);
     }
     g_state_cv.notify_all();
-    fprintf(stderr, "youth_icp: HIP ICP module initialized (device %d)\n", device);
+    fprintf(stderr, "youth_icp: HIP ICP module initialized (device %d%s)\n", device,
+            rgbd ? ", RGB-D tracking" : "");
 }
 
 // SLAM.cpp:97-124
@@ -922,13 +1289,19 @@ void stopSlamModule(void)
 int processSlamFrame(const int16_t* depth_data, const uint8_t* color_data, int width,
                      int height, uint32_t timestamp)
 {
-    (void)color_data;
     if (!g_running.load() || !g_queue) return 0;
     if (!depth_data || width < 3 || height < 3 || width > 4096 || height > 4096) {
         fprintf(stderr, "youth_icp: processSlamFrame: bad frame %dx%d\n", width, height);
         return 0;
     }
-    const int rc = youth_queue_push(g_queue, depth_data, width, height, timestamp);
+    if (g_rgbd.load() && !color_data) {
+        fprintf(stderr, "youth_icp: processSlamFrame: RGB-D tracking needs color_data; frame %u not queued\n",
+                timestamp);
+        return 0;
+    }
+    // colour travels only when a mode asks for it (else: the depth push alone)
+    const int rc = queue_push(g_queue, depth_data, g_carry_color.load() ? color_data : nullptr, width,
+                              height, timestamp);
     if (rc >= 0) {
         std::lock_guard<std::mutex> lk(g_wake_mu);
         g_wake_cv.notify_one();
@@ -1054,6 +1427,10 @@ int youth_slam_wait_idle(int timeout_ms)
 }
 
 void youth_slam_set_map_hooks(const youth_slam_map_hooks* hooks) { g_map_hooks.store(hooks); }
+
+void youth_slam_set_rgbd_hooks(const youth_slam_rgbd_hooks* hooks) { g_rgbd_hooks.store(hooks); }
+
+int youth_slam_rgbd_active(void) { return g_running.load() && g_rgbd.load() ? 1 : 0; }
 
 // youth_map_render.h: the module's map seen from a pose, by default the last
 // recorded one; under the trajectory lock, so no reset and no new pose falls

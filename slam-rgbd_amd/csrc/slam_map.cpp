@@ -61,13 +61,14 @@ void map_stop(void)
     g_map_vpm = 0.0f;
 }
 
-void map_integrate(const int16_t* depth, int w, int h, const youth_intrinsics* K,
+void map_integrate(const int16_t* depth, const uint8_t* rgb, int w, int h, const youth_intrinsics* K,
                    const double* T_world)
 {
     std::lock_guard<std::mutex> lk(g_map_mu);
     if (!g_map) return;
-    // synchronous: the frame's buffer is free again when this returns
-    if (youth_map_integrate_host(g_map, depth, nullptr, w, h, K, T_world) < 0)
+    // synchronous: the frame's buffers are free again when this returns; rgb
+    // (YOUTH_SLAM_MAP_COLOR / YOUTH_SLAM_RGBD) gives the voxels their colour
+    if (youth_map_integrate_host(g_map, depth, rgb, w, h, K, T_world) < 0)
         fprintf(stderr, "youth_icp: map integration failed: %s\n", youth_map_last_error());
 }
 

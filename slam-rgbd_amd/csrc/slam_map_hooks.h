@@ -17,9 +17,10 @@ struct youth_slam_map_hooks {
     // stopSlamModule, after the worker has been joined
     void (*stop)(void);
     // a recorded frame and its camera -> world pose (fp64 4x4); returns when
-    // the frame's buffer has been read
-    void (*integrate)(const int16_t* depth, int w, int h, const youth_intrinsics* K,
-                      const double* T_world);
+    // the frame's buffers have been read; rgb: the frame's colour (uint8
+    // [h][w][3]), null when colour is not carried
+    void (*integrate)(const int16_t* depth, const uint8_t* rgb, int w, int h,
+                      const youth_intrinsics* K, const double* T_world);
     // resetSlam / a new sequence's origin
     void (*clear)(void);
     // saveSlamMap: <base>_map.ply; 1 written or map off, 0 failed

@@ -201,6 +201,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "youth_slam_wait_idle": (c_int, [c_int]),
         "youth_slam_batched_frames": (ctypes.c_longlong, []),
         "youth_slam_queue_size": (c_int, []),
+        "youth_slam_rgbd_active": (c_int, []),
         "youth_slam_wait_stopped": (None, []),
         "youth_slam_trace_enable": (c_int, [c_int]),
         "youth_slam_trace_read": (c_int, [c_int, PD, POINTER(c_int), POINTER(c_int)]),
@@ -301,6 +302,11 @@ def slam_batched_frames() -> int:
 def slam_queue_size() -> int:
     """Frames waiting in the SLAM module's ingest queue."""
     return load_library().youth_slam_queue_size()
+
+
+def slam_rgbd_active() -> int:
+    """1 while the SLAM module tracks with colour (YOUTH_SLAM_RGBD=1)."""
+    return load_library().youth_slam_rgbd_active()
 
 
 SLAM_EVENTS = {1: "push_begin", 2: "push_end", 3: "take", 4: "submit_begin", 5: "submit_end",

@@ -52,6 +52,14 @@ _SIGS = {
     "youth_rgbd_track_host_sequence": (c_int, [c_void_p, POINTER(c_int16),
                                                POINTER(c_uint8), c_int, _PD,
                                                POINTER(c_int32)]),
+    "youth_rgbd_track_set_batch": (c_int, [c_void_p, c_int]),
+    "youth_rgbd_track_set_depth_filter": (c_int, [c_void_p, POINTER(youth_icp.FilterParams)]),
+    "youth_rgbd_track_submit": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_int]),
+    "youth_rgbd_track_collect": (c_int, [c_void_p, _PD, POINTER(c_int)]),
+    "youth_rgbd_track_pending": (c_int, [c_void_p]),
+    "youth_rgbd_track_reset": (c_int, [c_void_p]),
+    "youth_rgbd_pull_host": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_int,
+                                     c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 
@@ -102,6 +110,43 @@ def luma_device(d_rgb, d_gray=None, stream: int = 0):
     _check(lib, lib.youth_rgbd_luma_device(d_rgb.device.index or 0, _ptr(d_rgb), _ptr(d_gray), n,
                                            W, H, stream or None))
     return d_gray
+
+
+class PinnedColor:
+    """One page-locked RGB frame [H][W][3] uint8 (a youth_icp_host_alloc buffer)
+    as a numpy view; ``youth_icp.PinnedFrame`` is its depth counterpart."""
+
+    def __init__(self, height: int, width: int):
+        self._lib = youth_icp.load_library()
+        n = height * width * 3
+        self.ptr = self._lib.youth_icp_host_alloc((n + 1) // 2)
+        if not self.ptr:
+            raise IcpError(youth_icp.YOUTH_ENOMEM, "youth_icp_host_alloc failed")
+        raw = np.ctypeslib.as_array(ctypes.cast(self.ptr, POINTER(c_uint8)), shape=(n,))
+        self.array = raw.reshape(height, width, 3)
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            self.array = None
+            self._lib.youth_icp_host_free(self.ptr)
+            self.ptr = None
+
+    __del__ = close
+
+
+def _frame_ptrs(frames, dtype, shape, what):
+    """(c_void_p array, the arrays it points into) of host frames used in place."""
+    keep = []
+    for f in frames:
+        if f is None:
+            keep.append(None)
+            continue
+        if not isinstance(f, np.ndarray) or f.dtype != dtype or f.shape != shape \
+                or not f.flags["C_CONTIGUOUS"]:
+            raise ValueError(f"{what}: C-contiguous {np.dtype(dtype).name} arrays of shape {shape}")
+        keep.append(f)
+    arr = (c_void_p * max(len(keep), 1))(*[None if f is None else f.ctypes.data for f in keep])
+    return arr, keep
 
 
 class RgbdContext:
@@ -208,3 +253,51 @@ class RgbdContext:
             self._ctx, d.ctypes.data_as(POINTER(c_int16)), c.ctypes.data_as(POINTER(c_uint8)), n,
             T.ctypes.data_as(POINTER(c_double)), st.ctypes.data_as(POINTER(c_int32))))
         return T, st
+
+    # ---- streaming tracker (host frames, used in place) ----
+    def track_set_batch(self, b: int) -> int:
+        return _check(self._lib, self._lib.youth_rgbd_track_set_batch(self._ctx, b))
+
+    def track_set_depth_filter(self, t0: int | None = 8, t2: int = 96):
+        """``t0=None`` switches the filter off."""
+        P = None if t0 is None else ctypes.byref(youth_icp.FilterParams(t0, t2))
+        _check(self._lib, self._lib.youth_rgbd_track_set_depth_filter(self._ctx, P))
+
+    def track_submit(self, depth, rgb):
+        """Lists of [H][W] int16 and [H][W][3] uint8 frames, read in place: they
+        stay unchanged (and are kept alive here) until collected."""
+        if len(depth) != len(rgb):
+            raise ValueError("as many colour frames as depth frames")
+        dp, kd = _frame_ptrs(depth, np.int16, (self.H, self.W), "depth")
+        cp, kc = _frame_ptrs(rgb, np.uint8, (self.H, self.W, 3), "rgb")
+        _check(self._lib, self._lib.youth_rgbd_track_submit(self._ctx, dp, cp, len(depth)))
+        self._held = getattr(self, "_held", [])
+        self._held.extend(zip(kd, kc))
+
+    def track_collect(self):
+        """-> (T_rel [4,4] fp64 with P_ref = T_rel P_new, has_ref, status)."""
+        T = np.zeros((4, 4), np.float64)
+        has = c_int(0)
+        st = _check(self._lib, self._lib.youth_rgbd_track_collect(
+            self._ctx, T.ctypes.data_as(POINTER(c_double)), ctypes.byref(has)))
+        if getattr(self, "_held", None):
+            self._held.pop(0)
+        return T, has.value, st
+
+    def track_pending(self) -> int:
+        return self._lib.youth_rgbd_track_pending(self._ctx)
+
+    def track_reset(self):
+        _check(self._lib, self._lib.youth_rgbd_track_reset(self._ctx))
+
+    def pull_host(self, depth, rgb, d_depth, d_gray, d_rgb=None, stream: int = 0):
+        """youth_rgbd_pull_host: host frame lists -> torch tensors on the GPU
+        (int16 [m][H][W], uint8 [m][H][W], optional uint8 [m][H][W][3]);
+        asynchronous on ``stream``: keep the frames alive until it has run."""
+        if len(depth) != len(rgb):
+            raise ValueError("as many colour frames as depth frames")
+        dp, _kd = _frame_ptrs(depth, np.int16, (self.H, self.W), "depth")
+        cp, _kc = _frame_ptrs(rgb, np.uint8, (self.H, self.W, 3), "rgb")
+        _check(self._lib, self._lib.youth_rgbd_pull_host(
+            self._ctx, dp, cp, len(depth), _ptr(d_depth), _ptr(d_gray), _ptr(d_rgb),
+            stream or None))
