@@ -4,8 +4,16 @@
 // Same entry points, argument meaning, 1/0 return convention and threading
 // model (caller threads enqueue; ONE private worker thread tracks), but the
 // ORB-SLAM3 TrackRGBD call (SLAM.cpp:54) is replaced by HIP frame-to-frame
-// point-to-plane ICP (youth_icp_track_submit / _collect, two frames in
+// point-to-plane ICP (youth_icp_track_submit / _collect, two submissions in
 // flight).  Host-only C++: no HIP types.
+//
+// In the file's order: the event trace; the ingest queue, whose depth and
+// colour buffers come from two pools of one type (BufPool; queue_configure
+// holds what sets them apart); the SLAM state; the worker, ONE loop
+// (worker_main, finish_one, record_pose) over a Tracker, which is the depth
+// tracker (DepthTracker, youth_icp_track_*) or the RGB-D one behind
+// slam_rgbd_hooks.h (RgbdTracker) as initSlamModule picks; the SLAM.h entry
+// points.
 //
 // Differences from the reference that are deliberate:
 //  - processSlamFrame keeps depth as int16 millimetres (the GPU converts with
@@ -98,8 +106,8 @@ void trace(int kind, int arg)
 // Frames live in reusable buffers: a push copies the caller's frame into a
 // free buffer of the queue's pool (the one host copy of a frame on the SLAM
 // path), the drop policy and pops hand buffers back to the pool.  The SLAM
-// module's queue uses page-locked buffers (youth_icp_host_alloc, up to
-// kPinnedBytes of them), which the worker takes out of the queue and submits
+// module's queue uses page-locked buffers (youth_icp_host_alloc, up to the
+// pool's budget of them), which the worker takes out of the queue and submits
 // to the tracker in place (youth_icp_track_submit_pinned), returning each to
 // the pool once its frame has been collected.
 // Page-locked buffers are allocated and freed only off the producer's path
@@ -110,18 +118,31 @@ void trace(int kind, int arg)
 // worker frees it after use and adds a page-locked one to the pool.  Pooled
 // page-locked buffers are never freed on a full pool: the page-locked budget
 // bounds how many exist.
+// A frame's depth and its colour travel in a buffer each, from a pool each:
+// one pool type (BufPool), whose rules differ only in what queue_configure
+// gives the two.
 struct youth_frame_queue {
-    struct Item {
-        int16_t* buf = nullptr;
-        size_t cap = 0;      // values the buffer holds
+    struct Buf {
+        void* p = nullptr;
+        size_t cap = 0;  // bytes the buffer holds
         bool pinned = false;
+    };
+    struct BufPool {
+        std::vector<Buf> free_list;  // searched last-in first, first fit by capacity
+        size_t pinned_bytes = 0;     // page-locked bytes allocated and not freed
+        int pinned_count = 0;        // page-locked buffers allocated and not freed
+        // the rules (queue_configure)
+        size_t budget = 0;         // page-locked bytes at most
+        size_t keep_pageable = 0;  // pageable buffers the free list may grow to with (0: they are freed)
+        bool replenish = false;    // the worker replaces a buffer it frees by a page-locked one
+    };
+    struct Item {
+        Buf depth;  // int16 millimetres [h][w]
+        Buf color;  // RGB uint8 [h][w][3]; empty: colour is not carried
         int w = 0, h = 0;
         uint32_t ts = 0;
-        // the frame's colour, RGB uint8 [h][w][3], in a buffer of its own
-        // (null: colour is not carried); pooled apart from the depth buffers
-        uint8_t* cbuf = nullptr;
-        size_t ccap = 0;      // bytes the buffer holds
-        bool cpinned = false;
+        int16_t* d() const { return static_cast<int16_t*>(depth.p); }
+        uint8_t* rgb() const { return static_cast<uint8_t*>(color.p); }
     };
     static constexpr size_t kPinnedBytes = (size_t)256 << 20;
     static constexpr size_t kPoolMax = 48;  // pageable buffers kept
@@ -131,9 +152,7 @@ struct youth_frame_queue {
     // it without the lock, so a producer polling the depth (the reference's
     // logger waits on it) never contends with the worker's takes
     std::atomic<int> depth{0};
-    std::vector<Item> pool;
     int high = 10, low = 5;
-    bool pinned = false;      // page-locked buffers (SLAM module queue), allocated off the producer path
     // the producer's copy (youth_queue_push): 1 streaming stores
     // (youth::stream_copy; YOUTH_SLAM_PUSH_COPY=nt), 0 memcpy (=memcpy)
     int copy_mode = 1;
@@ -142,222 +161,190 @@ struct youth_frame_queue {
     // a concurrent producer copies alone); 0 (default): the producer alone
     std::unique_ptr<youth::HostCopyPool> copier;
     std::mutex copier_mu;
-    size_t pinned_bytes = 0;  // page-locked bytes allocated and not freed
-    int pinned_count = 0;     // page-locked buffers allocated and not freed
+    BufPool depth_pool, color_pool;  // both under mu
     // colour (the SLAM module with YOUTH_SLAM_RGBD / YOUTH_SLAM_MAP_COLOR): a
-    // pushed frame may bring a colour buffer; page-locked ones are pooled and
-    // prefilled like the depth buffers, with a budget of their own
+    // pushed frame may bring a colour buffer
     bool color = false;
-    std::vector<Item> cpool;  // page-locked colour buffers (cbuf / ccap only)
-    size_t cpinned_bytes = 0;
-    int cpinned_count = 0;
 };
 
 namespace {
 
-void buf_free(youth_frame_queue* q, youth_frame_queue::Item& it)
+using Buf = youth_frame_queue::Buf;
+using BufPool = youth_frame_queue::BufPool;
+using Item = youth_frame_queue::Item;
+
+// What sets the two pools and the two kinds of queue apart, all of it:
+//  - a caller's queue (youth_queue_create) holds pageable depth buffers and
+//    keeps up to kPoolMax of them; the SLAM module's (`pinned`) holds
+//    page-locked ones, allocated off the producer's path, frees a pageable one
+//    after use and replaces it by a page-locked one;
+//  - the colour pool never keeps a pageable buffer, has three times the depth
+//    pool's page-locked budget (three bytes a pixel against two), and replaces
+//    buffers only while the module carries colour.
+void queue_configure(youth_frame_queue* q, bool pinned, bool color)
 {
-    if (it.cbuf) {
-        if (it.cpinned) {
-            youth_icp_host_free(reinterpret_cast<int16_t*>(it.cbuf));
-            std::lock_guard<std::mutex> lk(q->mu);
-            q->cpinned_bytes -= it.ccap;
-            --q->cpinned_count;
-        } else {
-            free(it.cbuf);
-        }
-        it.cbuf = nullptr;
-        it.ccap = 0;
-    }
-    if (!it.buf) return;
-    if (it.pinned) {
-        youth_icp_host_free(it.buf);
+    q->color = color;
+    q->depth_pool.budget = q->kPinnedBytes;
+    q->depth_pool.keep_pageable = pinned ? 0 : q->kPoolMax;
+    q->depth_pool.replenish = pinned;
+    q->color_pool.budget = 3 * q->kPinnedBytes;
+    q->color_pool.keep_pageable = 0;
+    q->color_pool.replenish = pinned && color;
+}
+
+// Page-locked memory comes in int16 values (youth_icp_host_alloc): a byte
+// count is rounded up to whole values, which only a colour buffer of an odd
+// number of pixels needs.
+void* host_alloc_bytes(size_t bytes) { return youth_icp_host_alloc((bytes + 1) / 2); }
+void host_free_bytes(void* p) { youth_icp_host_free(static_cast<int16_t*>(p)); }
+
+void buf_free(youth_frame_queue* q, BufPool& pool, Buf& b)
+{
+    if (!b.p) return;
+    if (b.pinned) {
+        host_free_bytes(b.p);
         std::lock_guard<std::mutex> lk(q->mu);
-        q->pinned_bytes -= it.cap * sizeof(int16_t);
-        --q->pinned_count;
+        pool.pinned_bytes -= b.cap;
+        --pool.pinned_count;
     } else {
-        free(it.buf);
+        free(b.p);
     }
-    it.buf = nullptr;
-    it.cap = 0;
+    b = Buf();
 }
 
-// A buffer of >= n values for the producer: a pooled one, else (no pooled
-// buffer fits) a new pageable one.  *kind: 0 pooled, 2 new pageable (this
-// path never allocates page-locked memory: the worker and init do).
-bool buf_get(youth_frame_queue* q, size_t n, youth_frame_queue::Item& it, int* kind)
+// A buffer of >= n bytes for the producer: a pooled one (returns 0), else (no
+// pooled buffer fits) a new pageable one (2); -1 out of memory.  This path
+// never allocates page-locked memory: the worker and init do.
+int pool_get(youth_frame_queue* q, BufPool& pool, size_t n, Buf& b)
 {
     {
         std::lock_guard<std::mutex> lk(q->mu);
-        for (size_t k = q->pool.size(); k-- > 0;) {
-            if (q->pool[k].cap < n) continue;
-            it.buf = q->pool[k].buf;
-            it.cap = q->pool[k].cap;
-            it.pinned = q->pool[k].pinned;
-            q->pool.erase(q->pool.begin() + (long)k);
-            *kind = 0;
-            return true;
+        for (size_t k = pool.free_list.size(); k-- > 0;) {
+            if (pool.free_list[k].cap < n) continue;
+            b = pool.free_list[k];
+            pool.free_list.erase(pool.free_list.begin() + (long)k);
+            return 0;
         }
     }
-    *kind = 2;
-    it.buf = static_cast<int16_t*>(malloc(n * sizeof(int16_t)));
-    it.pinned = false;
-    it.cap = it.buf ? n : 0;
-    return it.buf != nullptr;
+    b.p = malloc(n);
+    b.pinned = false;
+    b.cap = b.p ? n : 0;
+    return b.p ? 2 : -1;
 }
 
-// A new page-locked buffer of n values while the budget lasts (worker / init).
-bool buf_new_pinned(youth_frame_queue* q, size_t n, youth_frame_queue::Item& it)
+// A new page-locked buffer of n bytes while the budget lasts (worker / init).
+bool pool_new_pinned(youth_frame_queue* q, BufPool& pool, size_t n, Buf& b)
 {
     {
         std::lock_guard<std::mutex> lk(q->mu);
-        if (q->pinned_bytes + n * sizeof(int16_t) > q->kPinnedBytes) return false;
-        q->pinned_bytes += n * sizeof(int16_t);
-        ++q->pinned_count;
+        if (pool.pinned_bytes + n > pool.budget) return false;
+        pool.pinned_bytes += n;
+        ++pool.pinned_count;
     }
-    it.buf = youth_icp_host_alloc(n);
-    if (!it.buf) {
+    b.p = host_alloc_bytes(n);
+    if (!b.p) {
         std::lock_guard<std::mutex> lk(q->mu);
-        q->pinned_bytes -= n * sizeof(int16_t);
-        --q->pinned_count;
+        pool.pinned_bytes -= n;
+        --pool.pinned_count;
         return false;
     }
-    it.pinned = true;
-    it.cap = n;
+    b.pinned = true;
+    b.cap = n;
     return true;
 }
 
-// back to the pool (q->mu held): page-locked buffers always (the budget
-// bounds them), pageable ones up to kPoolMax (else freed by the caller, which
-// is plain free())
-void pool_put_locked(youth_frame_queue* q, youth_frame_queue::Item& it,
-                     std::vector<youth_frame_queue::Item>& to_free)
+// Back to the pool (q->mu held): page-locked buffers always (the budget
+// bounds them), pageable ones while the pool keeps any; true when pooled,
+// else the caller frees it (a pageable buffer: plain free()).
+bool pool_put_locked(BufPool& pool, Buf& b)
 {
-    if (it.cbuf) {  // the colour buffer apart: page-locked to its pool, else freed
-        youth_frame_queue::Item c;
-        c.cbuf = it.cbuf;
-        c.ccap = it.ccap;
-        c.cpinned = it.cpinned;
-        (c.cpinned ? q->cpool : to_free).push_back(c);
-        it.cbuf = nullptr;
-        it.ccap = 0;
-    }
-    if (!it.buf) return;
-    if (it.pinned || (!q->pinned && q->pool.size() < q->kPoolMax))
-        q->pool.push_back(it);
-    else
-        to_free.push_back(it);
-    it.buf = nullptr;
+    if (!b.pinned && pool.free_list.size() >= pool.keep_pageable) return false;
+    pool.free_list.push_back(b);
+    b = Buf();
+    return true;
 }
 
-void free_all(youth_frame_queue* q, std::vector<youth_frame_queue::Item>& v)
+// A frame's buffers back to their pools (q->mu held); those not pooled are
+// pageable and go to to_free, freed by the caller once the lock is dropped.
+void item_put_locked(youth_frame_queue* q, Item& it, std::vector<void*>& to_free)
 {
-    for (auto& it : v) buf_free(q, it);
+    auto put = [&](BufPool& pool, Buf& b) {
+        if (!b.p || pool_put_locked(pool, b)) return;
+        to_free.push_back(b.p);
+        b = Buf();
+    };
+    put(q->color_pool, it.color);
+    put(q->depth_pool, it.depth);
+}
+
+void free_all(std::vector<void*>& v)
+{
+    for (void* p : v) free(p);
     v.clear();
 }
 
-// A new page-locked colour buffer of n bytes while its budget lasts (worker / init).
-bool color_new_pinned(youth_frame_queue* q, size_t n, youth_frame_queue::Item& it)
+// Page-locked buffers of n bytes until `count` exist (worker / init; pooled
+// buffers smaller than n are freed first: a resolution change).  Returns the
+// number allocated minus the number freed.
+int pool_prefill(youth_frame_queue* q, BufPool& pool, size_t n, int count)
 {
+    std::vector<Buf> to_free;
     {
         std::lock_guard<std::mutex> lk(q->mu);
-        if (q->cpinned_bytes + n > 3 * q->kPinnedBytes) return false;
-        q->cpinned_bytes += n;
-        ++q->cpinned_count;
-    }
-    it.cbuf = reinterpret_cast<uint8_t*>(youth_icp_host_alloc((n + 1) / 2));
-    if (!it.cbuf) {
-        std::lock_guard<std::mutex> lk(q->mu);
-        q->cpinned_bytes -= n;
-        --q->cpinned_count;
-        return false;
-    }
-    it.cpinned = true;
-    it.ccap = n;
-    return true;
-}
-
-// A colour buffer of >= n bytes for the producer: pooled, else new pageable.
-bool color_get(youth_frame_queue* q, size_t n, youth_frame_queue::Item& it)
-{
-    {
-        std::lock_guard<std::mutex> lk(q->mu);
-        for (size_t k = q->cpool.size(); k-- > 0;) {
-            if (q->cpool[k].ccap < n) continue;
-            it.cbuf = q->cpool[k].cbuf;
-            it.ccap = q->cpool[k].ccap;
-            it.cpinned = true;
-            q->cpool.erase(q->cpool.begin() + (long)k);
-            return true;
-        }
-    }
-    it.cbuf = static_cast<uint8_t*>(malloc(n));
-    it.cpinned = false;
-    it.ccap = it.cbuf ? n : 0;
-    return it.cbuf != nullptr;
-}
-
-// queue_prefill's colour part: page-locked colour buffers of n bytes until
-// `count` exist; pooled ones smaller than n are freed first.
-int color_prefill(youth_frame_queue* q, size_t n, int count)
-{
-    std::vector<youth_frame_queue::Item> to_free;
-    {
-        std::lock_guard<std::mutex> lk(q->mu);
-        std::vector<youth_frame_queue::Item> keep;
-        for (auto& it : q->cpool) (it.ccap >= n ? keep : to_free).push_back(it);
-        q->cpool.swap(keep);
+        std::vector<Buf> keep;
+        for (auto& b : pool.free_list) (b.cap >= n ? keep : to_free).push_back(b);
+        pool.free_list.swap(keep);
     }
     const int freed = (int)to_free.size();
-    for (auto& it : to_free) buf_free(q, it);
+    for (auto& b : to_free) buf_free(q, pool, b);
     int added = 0;
     for (;;) {
         {
             std::lock_guard<std::mutex> lk(q->mu);
-            if (q->cpinned_count >= count) break;
+            if (pool.pinned_count >= count) break;
         }
-        youth_frame_queue::Item it;
-        if (!color_new_pinned(q, n, it)) break;
+        Buf b;
+        if (!pool_new_pinned(q, pool, n, b)) break;
         std::lock_guard<std::mutex> lk(q->mu);
-        q->cpool.push_back(it);
+        pool.free_list.push_back(b);
         ++added;
     }
     return added - freed;
 }
 
-// queue_release's colour part, by its rules: a page-locked buffer of at least
-// n bytes goes back to the pool; a pageable or too small one is freed and,
-// while fewer than `target` page-locked ones exist, replaced.
-int color_release(youth_frame_queue* q, youth_frame_queue::Item& it, size_t n, int target)
+// The worker's pass over a returned buffer: page-locked ones of at least n
+// bytes go back to the pool; a pageable one (the producer found the pool
+// empty), or a page-locked one smaller than the worker's frame size n (in
+// flight across a resolution change: pooled, it would count toward the
+// page-locked target forever and keep new-size buffers out; ADVICE r5), is
+// freed and, while fewer than `target` page-locked buffers exist, replaced
+// by a page-locked one of n bytes.  Returns 1 when it allocated one.  n = 0
+// (no worker frame size: a pop, the exit): pooled by the pool's rules, never
+// replaced.
+int pool_release(youth_frame_queue* q, BufPool& pool, Buf& b, size_t n, int target)
 {
-    if (!it.cbuf) return 0;
-    youth_frame_queue::Item c;
-    c.cbuf = it.cbuf;
-    c.ccap = it.ccap;
-    c.cpinned = it.cpinned;
-    it.cbuf = nullptr;
-    it.ccap = 0;
-    const bool keep = c.cpinned && !(n > 0 && c.ccap < n);
+    if (!b.p) return 0;
+    bool keep = b.pinned ? !(n > 0 && b.cap < n) : pool.keep_pageable > 0;
     if (keep) {
         std::lock_guard<std::mutex> lk(q->mu);
-        q->cpool.push_back(c);
-        return 0;
+        keep = pool_put_locked(pool, b);
     }
-    buf_free(q, c);
-    if (!q->pinned || !q->color || n == 0) return 0;
+    if (keep) return 0;
+    buf_free(q, pool, b);
+    if (!pool.replenish || n == 0) return 0;
     {
         std::lock_guard<std::mutex> lk(q->mu);
-        if (q->cpinned_count >= target) return 0;
+        if (pool.pinned_count >= target) return 0;
     }
-    youth_frame_queue::Item fresh;
-    if (!color_new_pinned(q, n, fresh)) return 0;
+    Buf fresh;
+    if (!pool_new_pinned(q, pool, n, fresh)) return 0;
     std::lock_guard<std::mutex> lk(q->mu);
-    q->cpool.push_back(fresh);
+    pool.free_list.push_back(fresh);
     return 1;
 }
 
-// The oldest frame, buffer and all (1), or 0 when empty.
-int queue_take(youth_frame_queue* q, youth_frame_queue::Item& out)
+// The oldest frame, buffers and all (1), or 0 when empty.
+int queue_take(youth_frame_queue* q, Item& out)
 {
     std::lock_guard<std::mutex> lk(q->mu);
     if (q->q.empty()) return 0;
@@ -367,68 +354,20 @@ int queue_take(youth_frame_queue* q, youth_frame_queue::Item& out)
     return 1;
 }
 
-// Page-locked buffers of n values until `count` exist (worker / init; pooled
-// buffers smaller than n are freed first: a resolution change).  Returns the
-// number allocated minus the number freed.
+// Both pools filled for frames of n pixels; the count returned is the depth
+// pool's (YOUTH_SLAM_EV_POOL).
 int queue_prefill(youth_frame_queue* q, size_t n, int count)
 {
-    if (q->color) color_prefill(q, 3 * n, count);
-    std::vector<youth_frame_queue::Item> to_free;
-    {
-        std::lock_guard<std::mutex> lk(q->mu);
-        std::vector<youth_frame_queue::Item> keep;
-        for (auto& it : q->pool) (it.cap >= n ? keep : to_free).push_back(it);
-        q->pool.swap(keep);
-    }
-    const int freed = (int)to_free.size();
-    free_all(q, to_free);
-    int added = 0;
-    for (;;) {
-        {
-            std::lock_guard<std::mutex> lk(q->mu);
-            if (q->pinned_count >= count) break;
-        }
-        youth_frame_queue::Item it;
-        if (!buf_new_pinned(q, n, it)) break;
-        std::lock_guard<std::mutex> lk(q->mu);
-        q->pool.push_back(it);
-        ++added;
-    }
-    return added - freed;
+    if (q->color) pool_prefill(q, q->color_pool, 3 * n, count);
+    return pool_prefill(q, q->depth_pool, n * sizeof(int16_t), count);
 }
 
-// The worker's pass over a returned buffer: page-locked ones of at least n
-// values go back to the pool; a pageable one (the producer found the pool
-// empty), or a page-locked one smaller than the worker's frame size n (in
-// flight across a resolution change: pooled, it would count toward the
-// page-locked target forever and keep new-size buffers out; ADVICE r5), is
-// freed and, while fewer than `target` page-locked buffers exist, replaced
-// by a page-locked one of n values.  Returns 1 when it allocated one.
-int queue_release(youth_frame_queue* q, youth_frame_queue::Item& it, size_t n = 0, int target = 0)
+// A frame's buffers back from the worker, whose frames have n pixels; 1 when
+// a page-locked depth buffer was allocated in place of the one returned.
+int queue_release(youth_frame_queue* q, Item& it, size_t n = 0, int target = 0)
 {
-    color_release(q, it, 3 * n, target);
-    const bool replace = it.buf && (!it.pinned || (n > 0 && it.cap < n));
-    std::vector<youth_frame_queue::Item> to_free;
-    {
-        std::lock_guard<std::mutex> lk(q->mu);
-        if (it.buf && it.pinned && n > 0 && it.cap < n) {
-            to_free.push_back(it);
-            it.buf = nullptr;
-        } else {
-            pool_put_locked(q, it, to_free);
-        }
-    }
-    free_all(q, to_free);
-    if (!replace || !q->pinned || n == 0) return 0;
-    {
-        std::lock_guard<std::mutex> lk(q->mu);
-        if (q->pinned_count >= target) return 0;
-    }
-    youth_frame_queue::Item fresh;
-    if (!buf_new_pinned(q, n, fresh)) return 0;
-    std::lock_guard<std::mutex> lk(q->mu);
-    q->pool.push_back(fresh);
-    return 1;
+    pool_release(q, q->color_pool, it.color, 3 * n, target);
+    return pool_release(q, q->depth_pool, it.depth, n * sizeof(int16_t), target);
 }
 
 }  // namespace
@@ -441,6 +380,7 @@ youth_frame_queue* youth_queue_create(int high_water, int low_water)
     auto* q = new youth_frame_queue();
     q->high = high_water;
     q->low = low_water;
+    queue_configure(q, false, false);
     if (const char* e = getenv("YOUTH_SLAM_PUSH_COPY")) q->copy_mode = strcmp(e, "memcpy") == 0 ? 0 : 1;
     if (const char* e = getenv("YOUTH_SLAM_PUSH_THREADS"))
         if (atoi(e) > 0) q->copier.reset(new youth::HostCopyPool(std::min(atoi(e), 7), q->copy_mode == 1));
@@ -450,13 +390,16 @@ youth_frame_queue* youth_queue_create(int high_water, int low_water)
 void youth_queue_destroy(youth_frame_queue* q)
 {
     if (!q) return;
-    std::vector<youth_frame_queue::Item> all(q->q.begin(), q->q.end());
-    all.insert(all.end(), q->pool.begin(), q->pool.end());
-    all.insert(all.end(), q->cpool.begin(), q->cpool.end());
+    for (auto& it : q->q) {
+        buf_free(q, q->depth_pool, it.depth);
+        buf_free(q, q->color_pool, it.color);
+    }
     q->q.clear();
-    q->pool.clear();
-    q->cpool.clear();
-    free_all(q, all);
+    for (BufPool* pool : {&q->depth_pool, &q->color_pool}) {
+        std::vector<Buf> all;
+        all.swap(pool->free_list);
+        for (auto& b : all) buf_free(q, *pool, b);
+    }
     delete q;
 }
 
@@ -469,30 +412,30 @@ static int queue_push(youth_frame_queue* q, const int16_t* depth, const uint8_t*
 {
     if (!q || !depth || width <= 0 || height <= 0) return YOUTH_EINVAL;
     const size_t n = (size_t)width * (size_t)height;
-    youth_frame_queue::Item it;
-    int kind = 0;
+    Item it;
     trace(YOUTH_SLAM_EV_PUSH_BEGIN, youth_queue_size(q));
-    if (!buf_get(q, n, it, &kind)) return YOUTH_ENOMEM;
+    const int kind = pool_get(q, q->depth_pool, n * sizeof(int16_t), it.depth);
+    if (kind < 0) return YOUTH_ENOMEM;
     if (color && q->color) {
-        if (!color_get(q, 3 * n, it)) {
-            std::vector<youth_frame_queue::Item> back;
+        if (pool_get(q, q->color_pool, 3 * n, it.color) < 0) {
+            std::vector<void*> back;
             {
                 std::lock_guard<std::mutex> lk(q->mu);
-                pool_put_locked(q, it, back);
+                item_put_locked(q, it, back);
             }
-            free_all(q, back);
+            free_all(back);
             return YOUTH_ENOMEM;
         }
         if (q->copy_mode == 1)
-            youth::stream_copy(it.cbuf, color, 3 * n);
+            youth::stream_copy(it.rgb(), color, 3 * n);
         else
-            memcpy(it.cbuf, color, 3 * n);
+            memcpy(it.rgb(), color, 3 * n);
     }
     bool copied = false;
     if (q->copier && n * sizeof(int16_t) >= ((size_t)256 << 10)) {
         std::unique_lock<std::mutex> lk(q->copier_mu, std::try_to_lock);
         if (lk.owns_lock()) {
-            const youth::HostCopyPool::Seg seg{it.buf, depth, n * sizeof(int16_t)};
+            const youth::HostCopyPool::Seg seg{it.d(), depth, n * sizeof(int16_t)};
             q->copier->run(&seg, 1, n * sizeof(int16_t) / (2 * (q->copier->helpers() + 1)));
             copied = true;
         }
@@ -500,13 +443,13 @@ static int queue_push(youth_frame_queue* q, const int16_t* depth, const uint8_t*
     if (copied)
         ;
     else if (q->copy_mode == 1)
-        youth::stream_copy(it.buf, depth, n * sizeof(int16_t));
+        youth::stream_copy(it.d(), depth, n * sizeof(int16_t));
     else
-        memcpy(it.buf, depth, n * sizeof(int16_t));
+        memcpy(it.d(), depth, n * sizeof(int16_t));
     it.w = width;
     it.h = height;
     it.ts = timestamp;
-    std::vector<youth_frame_queue::Item> to_free;
+    std::vector<void*> to_free;
     int dropped = 0;
     {
         std::lock_guard<std::mutex> lk(q->mu);
@@ -516,14 +459,14 @@ static int queue_push(youth_frame_queue* q, const int16_t* depth, const uint8_t*
             fprintf(stderr, "youth_icp: frame queue is getting large (%zu), dropping to %d\n",
                     q->q.size(), q->low);
             while ((int)q->q.size() > q->low) {
-                pool_put_locked(q, q->q.front(), to_free);
+                item_put_locked(q, q->q.front(), to_free);
                 q->q.pop_front();
                 ++dropped;
             }
         }
         q->depth.store((int)q->q.size(), std::memory_order_release);
     }
-    free_all(q, to_free);
+    free_all(to_free);
     if (dropped) trace(YOUTH_SLAM_EV_DROP, dropped);
     trace(YOUTH_SLAM_EV_PUSH_END, kind);
     return dropped;
@@ -541,7 +484,7 @@ int youth_queue_pop(youth_frame_queue* q, int16_t* depth_out, size_t cap, int* w
                     int* height, uint32_t* timestamp)
 {
     if (!q) return YOUTH_EINVAL;
-    youth_frame_queue::Item it;
+    Item it;
     {
         std::lock_guard<std::mutex> lk(q->mu);
         if (q->q.empty()) return 0;
@@ -551,7 +494,7 @@ int youth_queue_pop(youth_frame_queue* q, int16_t* depth_out, size_t cap, int* w
         q->q.pop_front();
         q->depth.store((int)q->q.size(), std::memory_order_release);
     }
-    memcpy(depth_out, it.buf, (size_t)it.w * it.h * sizeof(int16_t));
+    memcpy(depth_out, it.d(), (size_t)it.w * it.h * sizeof(int16_t));
     if (width) *width = it.w;
     if (height) *height = it.h;
     if (timestamp) *timestamp = it.ts;
@@ -568,14 +511,14 @@ int youth_queue_size(youth_frame_queue* q)
 void youth_queue_clear(youth_frame_queue* q)
 {
     if (!q) return;
-    std::vector<youth_frame_queue::Item> to_free;
+    std::vector<void*> to_free;
     {
         std::lock_guard<std::mutex> lk(q->mu);
-        for (auto& it : q->q) pool_put_locked(q, it, to_free);
+        for (auto& it : q->q) item_put_locked(q, it, to_free);
         q->q.clear();
         q->depth.store(0, std::memory_order_release);
     }
-    free_all(q, to_free);
+    free_all(to_free);
 }
 
 // ---------------------------------------------------------- YAML config ---
@@ -702,132 +645,271 @@ int slam_batch()
 }
 int pool_target(int batch) { return 12 + 3 * batch; }
 
-// SLAM.cpp:32-63 processFramesThread, with TrackRGBD replaced by HIP ICP.
+// What the worker needs of a tracker, and all that differs between tracking
+// with depth alone and with colour.  One tracker at a time exists behind it
+// (create .. destroy); submit / collect run in order, two submissions in flight.
+struct Tracker {
+    virtual ~Tracker() {}
+    // `batch` frames per submission at most; false: last_error says why
+    virtual bool create(int device, int w, int h, int batch, const youth_intrinsics& K) = 0;
+    virtual void destroy() = 0;  // nothing in flight
+    virtual void reset() = 0;    // nothing in flight: the next frame starts a sequence
+    // m frames of the tracker's size, with `in_flight` submitted before them
+    // and not collected.  Returns the tracker's code; *sent: how many leading
+    // frames it took (m unless the code is negative).
+    virtual int submit(const Item* items, int m, int in_flight, int* sent) = 0;
+    virtual int collect(double* T_rel, int* has_ref) = 0;
+    virtual const char* last_error() = 0;
+    // a timed-out align (YOUTH_STATUS_TIMEOUT) again, from the two frames'
+    // host buffers; *how: 0 the cooperative plan, 1 the persistent kernel, 2 lost
+    virtual int realign(const int16_t*, const int16_t*, double*, int* how) { return *how = 2, YOUTH_EINVAL; }
+    virtual bool alive() const = 0;
+    // an align can time out and be realigned against the frame before it, so
+    // the worker keeps the last collected frame's buffer until the next collect
+    bool holds_reference = false;
+    // a refused frame's buffer replaced by a new page-locked one is traced
+    // (YOUTH_SLAM_EV_POOL), as every other replacement is
+    bool traces_refused_pool = false;
+    const char* banner = "";  // after "SLAM processing thread started"
+};
+
+// Depth alone: HIP point-to-plane ICP, frame to frame (youth_icp_track_*).
+struct DepthTracker final : Tracker {
+    youth_icp_ctx* ctx = nullptr;
+    size_t N = 0;
+    std::vector<int16_t> packed;  // pageable frames of a micro-batch, packed (rare)
+    DepthTracker() { holds_reference = true; }
+    bool alive() const override { return ctx != nullptr; }
+    bool create(int device, int w, int h, int batch, const youth_intrinsics& K) override
+    {
+        ctx = youth_icp_create(device, w, h, 2 * batch, &K, nullptr);
+        N = (size_t)w * h;
+        // planned for `batch`: every frame runs on that plan whether it
+        // arrived alone or in a backlog
+        if (ctx && batch > 1) youth_icp_track_set_batch(ctx, batch);
+        return ctx != nullptr;
+    }
+    void destroy() override
+    {
+        youth_icp_destroy(ctx);
+        ctx = nullptr;
+    }
+    void reset() override { youth_icp_track_reset(ctx); }
+    int submit(const Item* items, int m, int in_flight, int* sent) override
+    {
+        const long long chained0 = youth_icp_track_chained_frames(ctx);
+        bool pinned = true;
+        for (int i = 0; i < m; ++i) pinned &= items[i].depth.pinned;
+        int rc;
+        if (pinned) {  // the queue's page-locked buffers, copied to the device in place
+            const int16_t* fr[YOUTH_TRACK_MAX_BATCH];
+            for (int i = 0; i < m; ++i) fr[i] = items[i].d();
+            rc = youth_icp_track_submit_pinned(ctx, fr, m);
+        } else if (m == 1) {
+            rc = youth_icp_track_submit(ctx, items[0].d(), nullptr);
+        } else {
+            packed.resize((size_t)m * N);
+            for (int i = 0; i < m; ++i)
+                memcpy(packed.data() + (size_t)i * N, items[i].d(), N * sizeof(int16_t));
+            rc = youth_icp_track_submit_batch(ctx, packed.data(), m);
+        }
+        // frames of this submission that ran in chained (micro-batch) launches
+        g_batched.fetch_add(youth_icp_track_chained_frames(ctx) - chained0);
+        // a failed micro-batch may have submitted its first frames
+        *sent = rc < 0 ? youth_icp_track_pending(ctx) - in_flight : m;
+        return rc;
+    }
+    int collect(double* T_rel, int* has_ref) override { return youth_icp_track_collect(ctx, T_rel, has_ref); }
+    const char* last_error() override { return youth_icp_last_error(); }
+    // never composed: aligned again (the cooperative plan, bit-identical when
+    // it completes; else the persistent kernel); still timed out = lost
+    int realign(const int16_t* ref, const int16_t* depth, double* T_rel, int* how) override
+    {
+        long long p0 = 0, p1 = 0;
+        const long long c0 = youth_icp_track_realigned(ctx, &p0, nullptr);
+        const int st = youth_icp_track_realign(ctx, ref, depth, nullptr, T_rel);
+        const long long c1 = youth_icp_track_realigned(ctx, &p1, nullptr);
+        *how = c1 > c0 ? 0 : p1 > p0 ? 1 : 2;
+        return st;
+    }
+};
+
+// Depth and colour (YOUTH_SLAM_RGBD=1): the streaming RGB-D tracker behind the
+// hook table.  An RGB-D align holds no wait between workgroups, so it never
+// times out: neither a realign nor a held reference frame.  A
+// submission is all or nothing.
+struct RgbdTracker final : Tracker {
+    const youth_slam_rgbd_hooks* const rh;
+    void* trk = nullptr;
+    explicit RgbdTracker(const youth_slam_rgbd_hooks* hooks) : rh(hooks)
+    {
+        traces_refused_pool = true;
+        banner = " (RGB-D)";
+    }
+    bool alive() const override { return trk != nullptr; }
+    bool create(int device, int w, int h, int batch, const youth_intrinsics& K) override
+    {
+        trk = rh->create(device, w, h, batch, &K);
+        return trk != nullptr;
+    }
+    void destroy() override
+    {
+        rh->destroy(trk);
+        trk = nullptr;
+    }
+    void reset() override
+    {
+        if (rh->reset(trk) < 0) fprintf(stderr, "youth_icp: tracker reset failed: %s\n", rh->last_error());
+    }
+    int submit(const Item* items, int m, int, int* sent) override
+    {
+        const int16_t* fd[YOUTH_TRACK_MAX_BATCH] = {};
+        const uint8_t* fc[YOUTH_TRACK_MAX_BATCH] = {};
+        for (int i = 0; i < m; ++i) {
+            fd[i] = items[i].d();
+            fc[i] = items[i].rgb();  // never null: processSlamFrame refuses a frame without colour
+        }
+        const int rc = rh->submit(trk, fd, fc, m);
+        if (rc >= 0 && m > 1) g_batched.fetch_add(m);
+        *sent = rc < 0 ? 0 : m;
+        return rc;
+    }
+    int collect(double* T_rel, int* has_ref) override { return rh->collect(trk, T_rel, has_ref); }
+    const char* last_error() override { return rh->last_error(); }
+};
+
+struct Pending {
+    uint32_t ts;
+    int npts;   // valid pixels (counted for the last frame of a submission, else -1)
+    bool last;  // the last frame of its submission
+    Item item;  // its buffers, read in place until the frame is collected
+};
+
+// A collected frame's pose into the trajectory, T_w_ref (the world pose of
+// the tracker's reference) moved on to it, and the frame to the map, which
+// reads the frame's buffers before this returns.
+void record_pose(const Pending& f, int st, int has_ref, const double* T_rel, double* T_w_ref)
+{
+    std::lock_guard<std::mutex> lk(g_slam_mu);
+    // resetSlam raises g_reset under this lock before it clears the
+    // trajectory: a frame of the old sequence that passed the caller's check
+    // of the flag sees it here and is not taken as the new origin
+    if (g_reset.load()) return;
+    if (!has_ref || g_traj.empty()) {
+        // new sequence: this frame is the world origin
+        double I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        memcpy(T_w_ref, I, sizeof(I));
+        g_traj.clear();
+        g_traj_len.store(0, std::memory_order_release);
+        if (const youth_slam_map_hooks* mh = g_map_hooks.load()) mh->clear();
+    } else {
+        // P_ref = T_rel P_new  =>  T_w_new = T_w_ref * T_rel
+        mat_mul4(T_w_ref, T_rel, T_w_ref);
+    }
+    // FEW_MATCHES / DEGENERATE: some iteration skipped its update; the pose
+    // the others reached is composed (identity motion if none applied)
+    // and the bits are kept with it (youth_slam_get_status)
+    if (st & YOUTH_STATUS_FEW_MATCHES) g_weak[0].fetch_add(1);
+    if (st & YOUTH_STATUS_DEGENERATE) g_weak[1].fetch_add(1);
+    PoseRec pr;
+    pr.ts = f.ts;
+    pr.status = st;
+    memcpy(pr.T, T_w_ref, sizeof(pr.T));
+    g_traj.push_back(pr);
+    g_traj_len.store((int)g_traj.size(), std::memory_order_release);
+    if (f.npts >= 0) g_last_points = f.npts;
+    // the map takes every recorded frame with the pose just recorded
+    if (const youth_slam_map_hooks* mh = g_map_hooks.load()) {
+        const youth_intrinsics K = intrinsics_for(f.item.w, f.item.h);
+        mh->integrate(f.item.d(), f.item.rgb(), f.item.w, f.item.h, &K, T_w_ref);
+    }
+}
+
+// SLAM.cpp:32-63 processFramesThread, with TrackRGBD replaced by a Tracker.
 // The worker takes every frame of the current size already queued behind
 // the one it pops, up to `batch` (YOUTH_TRACK_MAX_BATCH by default;
 // YOUTH_SLAM_TRACK_BATCH=m overrides, 1 = one frame per launch), and
-// submits them as ONE micro-batch (youth_icp_track_submit_pinned: the queue's
-// page-locked buffers are copied to the device in place), two submissions in
-// flight.  The context is planned for `batch` (youth_icp_track_set_batch), so
+// submits them as ONE micro-batch, the queue's page-locked buffers read in
+// place, two submissions in flight.  The tracker is planned for `batch`, so
 // every frame runs on that plan whether it arrived alone (a live camera) or
 // in a backlog (a .bin replay, a burst): a frame's pose does not depend on
 // the queue's timing.  A frame's pose reaches the trajectory when the
 // submission after its own is made or the queue runs empty (the worker stays
 // busy until then: youth_slam_wait_idle).
-void worker_main(int device)
+void worker_main(int device, std::unique_ptr<Tracker> trk)
 {
-    using Item = youth_frame_queue::Item;
-    fprintf(stderr, "youth_icp: SLAM processing thread started\n");
-    youth_icp_ctx* ctx = nullptr;
+    fprintf(stderr, "youth_icp: SLAM processing thread started%s\n", trk->banner);
     int cw = 0, ch = 0;
     const int batch = slam_batch();
-    std::vector<int16_t> packed;  // pageable frames of a micro-batch, packed (rare)
-    bool held = false;            // a taken frame of another size (or sequence), next round
+    bool held = false;  // a taken frame of another size (or sequence), next round
     Item held_item;
     double T_w_ref[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    struct Pending {
-        uint32_t ts;
-        int npts;   // valid pixels (counted for the last frame of a submission, else -1)
-        bool last;  // the last frame of its submission
-        Item item;  // its buffer, in use by the H2D until the frame is collected
-    };
     std::deque<Pending> pend;  // submitted, not yet collected (oldest first)
     int subs = 0;              // submissions in pend
-    // The last collected frame's buffer stays out of the pool until the next
-    // frame has been collected: it is the target a timed-out align of that
-    // frame is realigned against (youth_icp_track_realign).
+    // A tracker that holds a reference: the last collected frame's buffer
+    // stays out of the pool until the next frame has been collected, the
+    // target a timed-out align of that frame is realigned against.
     Item ref_hold;
     bool ref_valid = false;  // ref_hold is the tracker's reference of the next collected frame
+    auto release = [&](Item& it) {
+        if (queue_release(g_queue, it, (size_t)cw * ch, pool_target(batch))) trace(YOUTH_SLAM_EV_POOL, 1);
+    };
     auto drop_ref = [&]() {
-        if (ref_hold.buf && queue_release(g_queue, ref_hold, (size_t)cw * ch, pool_target(batch)))
-            trace(YOUTH_SLAM_EV_POOL, 1);
+        if (ref_hold.depth.p) release(ref_hold);
         ref_hold = Item();
         ref_valid = false;
     };
     // collect the oldest submitted frame; record its pose unless a reset
-    // arrived since it was submitted; it becomes the held reference and the
-    // previous one's buffer goes back to the pool
+    // arrived since it was submitted.  With a held reference, in this order:
+    // collect, realign against the reference, drop it, the frame becomes the
+    // reference, record (the map reads the buffer, now ref_hold); without,
+    // the frame's buffers go back once it is recorded.
     auto finish_one = [&](bool record) {
-        Pending pr0 = pend.front();
+        Pending f = pend.front();
         pend.pop_front();
-        subs -= pr0.last;
+        subs -= f.last;
         double T_rel[16];
         int has_ref = 0;
         trace(YOUTH_SLAM_EV_COLLECT_BEGIN, (int)pend.size() + 1);
-        int st = youth_icp_track_collect(ctx, T_rel, &has_ref);
-        trace(YOUTH_SLAM_EV_COLLECT_END, pr0.last ? 1 : 0);
+        int st = trk->collect(T_rel, &has_ref);
+        trace(YOUTH_SLAM_EV_COLLECT_END, f.last ? 1 : 0);
         // (a frame of a sequence that a reset ended is not recorded: no retry)
         const bool keep = record && !g_reset.load();
-        if (st >= 0 && has_ref && (st & YOUTH_STATUS_TIMEOUT) && keep) {
-            // never composed: aligned again from the two frames' host buffers
-            // (the cooperative plan, bit-identical when it completes; else the
-            // persistent kernel); still timed out = lost
+        const bool holds = trk->holds_reference;
+        if (holds && st >= 0 && has_ref && (st & YOUTH_STATUS_TIMEOUT) && keep) {
             int how = 2;
             if (ref_valid) {
-                long long p0 = 0, p1 = 0;
-                const long long c0 = youth_icp_track_realigned(ctx, &p0, nullptr);
-                const int st2 = youth_icp_track_realign(ctx, ref_hold.buf, pr0.item.buf, nullptr, T_rel);
-                const long long c1 = youth_icp_track_realigned(ctx, &p1, nullptr);
+                const int st2 = trk->realign(ref_hold.d(), f.item.d(), T_rel, &how);
                 if (st2 < 0)
-                    fprintf(stderr, "youth_icp: realign failed: %s\n", youth_icp_last_error());
+                    fprintf(stderr, "youth_icp: realign failed: %s\n", trk->last_error());
                 else
                     st = st2;
-                how = c1 > c0 ? 0 : p1 > p0 ? 1 : 2;
             }
             g_realigned[how].fetch_add(1);
             trace(YOUTH_SLAM_EV_REALIGN, how);
         }
         drop_ref();
         if (st < 0) {
-            if (queue_release(g_queue, pr0.item, (size_t)cw * ch, pool_target(batch)))
-                trace(YOUTH_SLAM_EV_POOL, 1);
-            fprintf(stderr, "youth_icp: tracking failed: %s\n", youth_icp_last_error());
+            // not the reference, not recorded.  The line stays on the side of
+            // the release it had for each tracker: a release may allocate a
+            // page-locked buffer, whose failure would replace last_error's text
+            if (!holds) fprintf(stderr, "youth_icp: tracking failed: %s\n", trk->last_error());
+            release(f.item);
+            if (holds) fprintf(stderr, "youth_icp: tracking failed: %s\n", trk->last_error());
             return;
         }
-        ref_hold = pr0.item;
-        ref_valid = true;
-        if (!keep) return;
-        if (st & YOUTH_STATUS_TIMEOUT) {
+        if (holds) {
+            ref_hold = f.item;
+            ref_valid = true;
+        }
+        if (keep && holds && (st & YOUTH_STATUS_TIMEOUT))
             // no pose for this frame: it is left out of the trajectory and the
             // next frame composes onto the last recorded pose (no motion
             // across the lost frame)
-            fprintf(stderr, "youth_icp: frame %u lost (align timed out twice)\n", pr0.ts);
-            return;
-        }
-        std::lock_guard<std::mutex> lk(g_slam_mu);
-        // resetSlam raises g_reset under this lock before it clears the
-        // trajectory: a frame of the old sequence that passed the check
-        // above sees the flag here and is not taken as the new origin
-        if (g_reset.load()) return;
-        if (!has_ref || g_traj.empty()) {
-            // new sequence: this frame is the world origin
-            double I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-            memcpy(T_w_ref, I, sizeof(I));
-            g_traj.clear();
-            g_traj_len.store(0, std::memory_order_release);
-            if (const youth_slam_map_hooks* mh = g_map_hooks.load()) mh->clear();
-        } else {
-            // P_ref = T_rel P_new  =>  T_w_new = T_w_ref * T_rel
-            mat_mul4(T_w_ref, T_rel, T_w_ref);
-        }
-        // FEW_MATCHES / DEGENERATE: some iteration skipped its update; the pose
-        // the others reached is composed (identity motion if none applied)
-        // and the bits are kept with it (youth_slam_get_status)
-        if (st & YOUTH_STATUS_FEW_MATCHES) g_weak[0].fetch_add(1);
-        if (st & YOUTH_STATUS_DEGENERATE) g_weak[1].fetch_add(1);
-        PoseRec pr;
-        pr.ts = pr0.ts;
-        pr.status = st;
-        memcpy(pr.T, T_w_ref, sizeof(pr.T));
-        g_traj.push_back(pr);
-        g_traj_len.store((int)g_traj.size(), std::memory_order_release);
-        if (pr0.npts >= 0) g_last_points = pr0.npts;
-        // the map takes every recorded frame with the pose just recorded; the
-        // frame's buffer (now ref_hold) is read before this returns
-        if (const youth_slam_map_hooks* mh = g_map_hooks.load()) {
-            const youth_intrinsics K = intrinsics_for(pr0.item.w, pr0.item.h);
-            mh->integrate(pr0.item.buf, pr0.item.cbuf, pr0.item.w, pr0.item.h, &K, T_w_ref);
-        }
+            fprintf(stderr, "youth_icp: frame %u lost (align timed out twice)\n", f.ts);
+        else if (keep)
+            record_pose(f, st, has_ref, T_rel, T_w_ref);
+        if (!holds) release(f.item);
     };
     while (g_process.load()) {
         Item items[YOUTH_TRACK_MAX_BATCH];
@@ -862,25 +944,21 @@ void worker_main(int device)
         if (g_reset.exchange(false)) {
             while (!pend.empty()) finish_one(false);  // frames of the old sequence
             drop_ref();
-            if (ctx) youth_icp_track_reset(ctx);
+            if (trk->alive()) trk->reset();
         }
-        if (!ctx || w != cw || h != ch) {
-            while (!pend.empty()) finish_one(true);
+        if (!trk->alive() || w != cw || h != ch) {
+            while (!pend.empty()) finish_one(true);  // the size-change rule: drain, then a new tracker
             drop_ref();
-            if (ctx) youth_icp_destroy(ctx);
-            const youth_intrinsics K = intrinsics_for(w, h);
-            ctx = youth_icp_create(device, w, h, 2 * batch, &K, nullptr);
+            if (trk->alive()) trk->destroy();
             cw = w;
             ch = h;
-            if (!ctx) {
-                fprintf(stderr, "youth_icp: context creation failed: %s\n",
-                        youth_icp_last_error());
+            if (!trk->create(device, w, h, batch, intrinsics_for(w, h))) {
+                fprintf(stderr, "youth_icp: context creation failed: %s\n", trk->last_error());
                 cw = ch = 0;
                 queue_release(g_queue, items[0]);
                 g_busy.store(false);
                 continue;
             }
-            if (batch > 1) youth_icp_track_set_batch(ctx, batch);
             // page-locked buffers for this size up front (initSlamModule made
             // them for the configured size already)
             trace(YOUTH_SLAM_EV_POOL, queue_prefill(g_queue, (size_t)w * h, pool_target(batch)));
@@ -889,7 +967,9 @@ void worker_main(int device)
         // two submissions in flight: with two queued, finish the oldest
         // before gathering the batch (the queue fills meanwhile, so a backlog
         // goes out in full micro-batches rather than as many small launches
-        // each costing a full one)
+        // each costing a full one).  pend then holds one submission at most,
+        // of at most `batch` frames: with the m <= batch gathered below, never
+        // more than the 2 batch frames a tracker holds in flight.
         if (subs >= 2)
             while (!pend.empty()) {
                 const bool last = pend.front().last;
@@ -911,221 +991,28 @@ void worker_main(int device)
             }
         }
         trace(YOUTH_SLAM_EV_TAKE, m);
-        // the tracker holds 2 batch frames in flight
-        while (!pend.empty() && (int)pend.size() + m > 2 * batch) finish_one(true);
-        const long long chained0 = youth_icp_track_chained_frames(ctx);
-        bool pinned = true;
-        for (int i = 0; i < m; ++i) pinned &= items[i].pinned;
-        int rc;
+        int sent = 0;
         trace(YOUTH_SLAM_EV_SUBMIT_BEGIN, m);
-        if (pinned) {
-            const int16_t* fr[YOUTH_TRACK_MAX_BATCH];
-            for (int i = 0; i < m; ++i) fr[i] = items[i].buf;
-            rc = youth_icp_track_submit_pinned(ctx, fr, m);
-        } else if (m == 1) {
-            rc = youth_icp_track_submit(ctx, items[0].buf, nullptr);
-        } else {
-            packed.resize((size_t)m * N);
-            for (int i = 0; i < m; ++i)
-                memcpy(packed.data() + (size_t)i * N, items[i].buf, N * sizeof(int16_t));
-            rc = youth_icp_track_submit_batch(ctx, packed.data(), m);
-        }
+        const int rc = trk->submit(items, m, (int)pend.size(), &sent);
         trace(YOUTH_SLAM_EV_SUBMIT_END, rc);
-        // frames of this submission that ran in chained (micro-batch) launches
-        g_batched.fetch_add(youth_icp_track_chained_frames(ctx) - chained0);
+        if (rc < 0) fprintf(stderr, "youth_icp: tracking failed: %s\n", trk->last_error());
         // getSlamMapPoints reports the newest recorded frame: only the last
         // frame of a submission is counted
         int npts = 0;
-        for (size_t i = 0; i < N; ++i) npts += items[m - 1].buf[i] > 0;
-        // a failed micro-batch may have submitted its first frames
-        const int sent = rc < 0 ? youth_icp_track_pending(ctx) - (int)pend.size() : m;
-        if (rc < 0) fprintf(stderr, "youth_icp: tracking failed: %s\n", youth_icp_last_error());
+        for (size_t i = 0; sent == m && i < N; ++i) npts += items[m - 1].d()[i] > 0;
         for (int i = 0; i < m; ++i) {
             if (i < sent)
                 pend.push_back(Pending{items[i].ts, i == m - 1 ? npts : -1, i == sent - 1, items[i]});
-            else
-                queue_release(g_queue, items[i], N, pool_target(batch));
+            else if (queue_release(g_queue, items[i], N, pool_target(batch)) && trk->traces_refused_pool)
+                trace(YOUTH_SLAM_EV_POOL, 1);
         }
         subs += sent > 0;
         if (batch == 1 && pend.size() == 2) finish_one(true);
     }
-    while (ctx && !pend.empty()) finish_one(true);
+    while (trk->alive() && !pend.empty()) finish_one(true);
     drop_ref();
     if (held) queue_release(g_queue, held_item);
-    if (ctx) youth_icp_destroy(ctx);
-    fprintf(stderr, "youth_icp: SLAM processing thread stopped\n");
-}
-
-// The worker of RGB-D mode (YOUTH_SLAM_RGBD=1): worker_main's loop with the
-// streaming RGB-D tracker behind the hook table in place of the depth tracker.
-// Up to `batch` queued frames of one size go out as one submission, depth and
-// colour buffers in place, two submissions in flight, collected in order; the
-// tracker is planned for `batch`, so a frame's pose does not depend on the
-// queue's timing.  Simpler than worker_main in one respect: an RGB-D align
-// holds no wait between workgroups, so it never times out and
-// there is neither a realign nor a held reference frame.
-void worker_rgbd_main(int device)
-{
-    using Item = youth_frame_queue::Item;
-    fprintf(stderr, "youth_icp: SLAM processing thread started (RGB-D)\n");
-    const youth_slam_rgbd_hooks* rh = g_rgbd_hooks.load();
-    void* trk = nullptr;
-    int cw = 0, ch = 0;
-    const int batch = slam_batch();
-    bool held = false;  // a taken frame of another size (or sequence), next round
-    Item held_item;
-    double T_w_ref[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    struct Pending {
-        uint32_t ts;
-        int npts;   // valid pixels (counted for the last frame of a submission, else -1)
-        bool last;  // the last frame of its submission
-        Item item;  // its buffers, read in place until the frame is collected
-    };
-    std::deque<Pending> pend;  // submitted, not yet collected (oldest first)
-    int subs = 0;              // submissions in pend
-    auto release = [&](Item& it) {
-        if (queue_release(g_queue, it, (size_t)cw * ch, pool_target(batch))) trace(YOUTH_SLAM_EV_POOL, 1);
-    };
-    // collect the oldest submitted frame; record its pose unless a reset
-    // arrived since it was submitted
-    auto finish_one = [&](bool record) {
-        Pending pr0 = pend.front();
-        pend.pop_front();
-        subs -= pr0.last;
-        double T_rel[16];
-        int has_ref = 0;
-        trace(YOUTH_SLAM_EV_COLLECT_BEGIN, (int)pend.size() + 1);
-        const int st = rh->collect(trk, T_rel, &has_ref);
-        trace(YOUTH_SLAM_EV_COLLECT_END, pr0.last ? 1 : 0);
-        if (st < 0) fprintf(stderr, "youth_icp: tracking failed: %s\n", rh->last_error());
-        if (st >= 0 && record && !g_reset.load()) {
-            std::lock_guard<std::mutex> lk(g_slam_mu);
-            // resetSlam raises g_reset under this lock before it clears the
-            // trajectory: a frame of the old sequence that passed the check
-            // above sees the flag here and is not taken as the new origin
-            if (!g_reset.load()) {
-                if (!has_ref || g_traj.empty()) {
-                    // new sequence: this frame is the world origin
-                    double I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-                    memcpy(T_w_ref, I, sizeof(I));
-                    g_traj.clear();
-                    g_traj_len.store(0, std::memory_order_release);
-                    if (const youth_slam_map_hooks* mh = g_map_hooks.load()) mh->clear();
-                } else {
-                    // P_ref = T_rel P_new  =>  T_w_new = T_w_ref * T_rel
-                    mat_mul4(T_w_ref, T_rel, T_w_ref);
-                }
-                if (st & YOUTH_STATUS_FEW_MATCHES) g_weak[0].fetch_add(1);
-                if (st & YOUTH_STATUS_DEGENERATE) g_weak[1].fetch_add(1);
-                PoseRec pr;
-                pr.ts = pr0.ts;
-                pr.status = st;
-                memcpy(pr.T, T_w_ref, sizeof(pr.T));
-                g_traj.push_back(pr);
-                g_traj_len.store((int)g_traj.size(), std::memory_order_release);
-                if (pr0.npts >= 0) g_last_points = pr0.npts;
-                if (const youth_slam_map_hooks* mh = g_map_hooks.load()) {
-                    const youth_intrinsics K = intrinsics_for(pr0.item.w, pr0.item.h);
-                    mh->integrate(pr0.item.buf, pr0.item.cbuf, pr0.item.w, pr0.item.h, &K, T_w_ref);
-                }
-            }
-        }
-        release(pr0.item);
-    };
-    while (g_process.load()) {
-        Item items[YOUTH_TRACK_MAX_BATCH];
-        g_busy.store(true);
-        int got = 1;
-        if (held) {
-            items[0] = held_item;
-            held = false;
-        } else {
-            got = queue_take(g_queue, items[0]);
-        }
-        if (got != 1) {
-            if (!pend.empty()) {  // nothing new: finish what is in flight
-                finish_one(true);
-                continue;
-            }
-            g_busy.store(false);
-            trace(YOUTH_SLAM_EV_IDLE_BEGIN, 0);
-            {
-                // as worker_main: the predicate re-checks the queue under
-                // g_wake_mu, which processSlamFrame takes before notifying
-                std::unique_lock<std::mutex> lk(g_wake_mu);
-                g_wake_cv.wait_until(lk, std::chrono::system_clock::now() + std::chrono::milliseconds(20),
-                                     [] { return !g_process.load() || youth_queue_size(g_queue) > 0; });
-            }
-            trace(YOUTH_SLAM_EV_IDLE_END, youth_queue_size(g_queue));
-            continue;
-        }
-        const int w = items[0].w, h = items[0].h;
-        if (g_reset.exchange(false)) {
-            while (!pend.empty()) finish_one(false);  // frames of the old sequence
-            if (trk && rh->reset(trk) < 0)
-                fprintf(stderr, "youth_icp: tracker reset failed: %s\n", rh->last_error());
-        }
-        if (!trk || w != cw || h != ch) {
-            while (!pend.empty()) finish_one(true);  // the size-change rule: drain, then a new context
-            if (trk) rh->destroy(trk);
-            const youth_intrinsics K = intrinsics_for(w, h);
-            trk = rh->create(device, w, h, batch, &K);
-            cw = w;
-            ch = h;
-            if (!trk) {
-                fprintf(stderr, "youth_icp: context creation failed: %s\n", rh->last_error());
-                cw = ch = 0;
-                queue_release(g_queue, items[0]);
-                g_busy.store(false);
-                continue;
-            }
-            trace(YOUTH_SLAM_EV_POOL, queue_prefill(g_queue, (size_t)w * h, pool_target(batch)));
-        }
-        const size_t N = (size_t)w * h;
-        // two submissions in flight: with two out, finish the oldest first
-        if (subs >= 2)
-            while (!pend.empty()) {
-                const bool last = pend.front().last;
-                finish_one(true);
-                if (last) break;
-            }
-        int m = 1;
-        while (m < batch && !held) {
-            Item it;
-            if (queue_take(g_queue, it) != 1) break;
-            if (it.w == w && it.h == h && !g_reset.load()) {
-                items[m++] = it;
-            } else {
-                held_item = it;
-                held = true;
-            }
-        }
-        trace(YOUTH_SLAM_EV_TAKE, m);
-        const int16_t* fd[YOUTH_TRACK_MAX_BATCH];
-        const uint8_t* fc[YOUTH_TRACK_MAX_BATCH];
-        for (int i = 0; i < m; ++i) {
-            fd[i] = items[i].buf;
-            fc[i] = items[i].cbuf;  // never null: processSlamFrame refuses a frame without colour
-        }
-        trace(YOUTH_SLAM_EV_SUBMIT_BEGIN, m);
-        const int rc = rh->submit(trk, fd, fc, m);
-        trace(YOUTH_SLAM_EV_SUBMIT_END, rc);
-        if (rc < 0) {  // all or nothing: a refused submission leaves no frame pending
-            fprintf(stderr, "youth_icp: tracking failed: %s\n", rh->last_error());
-            for (int i = 0; i < m; ++i) release(items[i]);
-            continue;
-        }
-        if (m > 1) g_batched.fetch_add(m);
-        int npts = 0;
-        for (size_t i = 0; i < N; ++i) npts += items[m - 1].buf[i] > 0;
-        for (int i = 0; i < m; ++i)
-            pend.push_back(Pending{items[i].ts, i == m - 1 ? npts : -1, i == m - 1, items[i]});
-        ++subs;
-        if (batch == 1 && pend.size() == 2) finish_one(true);
-    }
-    while (trk && !pend.empty()) finish_one(true);
-    if (held) queue_release(g_queue, held_item);
-    if (trk) rh->destroy(trk);
+    if (trk->alive()) trk->destroy();
     fprintf(stderr, "youth_icp: SLAM processing thread stopped\n");
 }
 
@@ -1232,12 +1119,10 @@ void initSlamModule(const char* config_file, const char* vocabulary_file)
     if (rgbd) rh->start();
     g_rgbd.store(rgbd);
     g_carry_color.store(rgbd || env_on("YOUTH_SLAM_MAP_COLOR"));
-    if (!g_queue) {
-        g_queue = youth_queue_create(10, 5);
-        g_queue->pinned = true;  // buffers the tracker copies to the device in place
-    }
+    if (!g_queue) g_queue = youth_queue_create(10, 5);
+    // page-locked buffers, which the tracker copies to the device in place
+    queue_configure(g_queue, true, g_carry_color.load());
     youth_queue_clear(g_queue);
-    g_queue->color = g_carry_color.load();
     // page-locked buffers for the configured frame size (the YAML's, else
     // 640x480) before the first frame: the producer never allocates them
     {
@@ -1253,7 +1138,12 @@ void initSlamModule(const char* config_file, const char* vocabulary_file)
     for (auto& r : g_realigned) r.store(0);
     for (auto& r : g_weak) r.store(0);
     try {
-        g_worker = std::thread(rgbd ? worker_rgbd_main : worker_main, device);
+        std::unique_ptr<Tracker> trk;
+        if (rgbd)
+            trk.reset(new RgbdTracker(rh));
+        else
+            trk.reset(new DepthTracker());
+        g_worker = std::thread(worker_main, device, std::move(trk));
     } catch (const std::exception& ex) {
         fprintf(stderr, "youth_icp: failed to start worker: %s\n", ex.what());
         g_process.store(false);

@@ -15,7 +15,10 @@
 //   7. timed-out aligns (the stub's YOUTH_STUB_TIMEOUT_EVERY) realigned by
 //      the worker, with the event trace enabled, read and disabled from
 //      another thread while the worker records (a freed trace
-//      buffer must never be written).
+//      buffer must never be written);
+//   8. a micro-batch the tracker refuses part way (the stub's
+//      YOUTH_STUB_REFUSE_AT): its accepted frames are recorded, the refused
+//      ones are not, the stream goes on and no buffer is lost.
 // Exit 0 when every check holds; the sanitizers abort (exit 66 / non-zero)
 // on a report.
 #include <stdio.h>
@@ -315,6 +318,48 @@ static void scenario_realign_and_trace()
     initSlamModule(nullptr, nullptr);  // scenario_stop_under_load stops it
 }
 
+// icp_stub.c only: frames of partly accepted submissions that the stub refused
+extern "C" long long youth_stub_refused_frames(void);
+
+// A micro-batch that fails part way (the stub's YOUTH_STUB_REFUSE_AT): the
+// frames the tracker took are collected and recorded, the refused ones go
+// back to the pool unrecorded, and the stream goes on.
+static void scenario_partial_submission()
+{
+    stopSlamModule();
+    setenv("YOUTH_STUB_REFUSE_AT", "2", 1);
+    initSlamModule(nullptr, nullptr);
+    const long long refused0 = youth_stub_refused_frames();
+    const int F = 48, burst = 6;
+    std::vector<std::vector<int16_t>> fr;
+    for (int k = 0; k < F; ++k) fr.push_back(frame(100 + 3 * k));
+    // bursts into an empty queue (no frame dropped by the >10 -> 5 policy):
+    // what arrives while the worker collects travels as one micro-batch
+    for (int k = 0; k < F; ++k) {
+        if (k % burst == 0)
+            while (youth_slam_queue_size() > 0) std::this_thread::yield();
+        check(processSlamFrame(fr[k].data(), nullptr, W, H, (uint32_t)(k + 1)) == 1, "processSlamFrame accepted");
+    }
+    check(youth_slam_wait_idle(20000) == 1, "worker idle after a partly refused submission");
+    const long long refused = youth_stub_refused_frames() - refused0;
+    check(refused > 0, "a submission was refused");
+    check(youth_slam_trajectory_length() == F - (int)refused, "every frame but the refused ones recorded");
+    // a frame pushed after the failure is recorded too
+    auto tail = frame(777);
+    check(processSlamFrame(tail.data(), nullptr, W, H, (uint32_t)(F + 1)) == 1, "processSlamFrame accepted");
+    check(youth_slam_wait_idle(20000) == 1, "worker idle");
+    check(youth_stub_refused_frames() - refused0 == refused, "one submission refused, no more");
+    const int len = youth_slam_trajectory_length();
+    check(len == F + 1 - (int)refused, "the frame after the failure recorded");
+    std::vector<uint32_t> ts(len);
+    check(youth_slam_get_trajectory(len, ts.data(), nullptr) == len, "trajectory");
+    for (int i = 1; i < len; ++i) check(ts[i] > ts[i - 1], "timestamps strictly increase");
+    check(ts[len - 1] == (uint32_t)(F + 1), "the last frame pushed is the last recorded");
+    stopSlamModule();
+    unsetenv("YOUTH_STUB_REFUSE_AT");
+    initSlamModule(nullptr, nullptr);  // scenario_stop_under_load stops it
+}
+
 int main()
 {
     scenario_init_and_producers();
@@ -322,6 +367,7 @@ int main()
     scenario_frame_loop();
     scenario_mq_loop();
     scenario_realign_and_trace();
+    scenario_partial_submission();
     scenario_stop_under_load();
     printf("sanitizer driver: all scenarios passed\n");
     return 0;

@@ -16,8 +16,14 @@
  * makes every k-th frame with a reference come back YOUTH_STATUS_TIMEOUT with
  * a wrong pose, as a timed-out cooperative align does, so the worker's
  * realign path runs too; youth_icp_track_realign recomputes the pose from the
- * two frames it is given.
+ * two frames it is given.  YOUTH_STUB_REFUSE_AT=k (read at create) makes the
+ * context's k-th multi-frame submit_pinned / submit_batch accept the first half
+ * of its frames and return YOUTH_EINVAL, as a micro-batch that fails part way
+ * does; youth_stub_refused_frames counts the frames refused so.
+ * youth_stub_host_min_values reports the smallest page-locked buffer alive (a
+ * driver checks that none of an earlier frame size is left behind).
  */
+#include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
@@ -39,7 +45,21 @@ struct youth_icp_ctx {
     int status[YOUTH_TRACK_MAX_IN_FLIGHT];
     int timeout_every, tracked;
     long long realigned;
+    int refuse_at, multi; /* YOUTH_STUB_REFUSE_AT; multi-frame submissions so far */
 };
+
+/* frames of partly accepted submissions that the stub refused (all contexts) */
+static long long g_refused;
+long long youth_stub_refused_frames(void) { return __atomic_load_n(&g_refused, __ATOMIC_SEQ_CST); }
+
+/* How many of n_frames this multi-frame submission accepts: all, or on the
+ * k-th one the first half. */
+static int stub_accept(youth_icp_ctx* c, int n_frames)
+{
+    if (n_frames < 2 || c->refuse_at <= 0 || ++c->multi != c->refuse_at) return n_frames;
+    __atomic_fetch_add(&g_refused, (long long)(n_frames - n_frames / 2), __ATOMIC_SEQ_CST);
+    return n_frames / 2;
+}
 
 static long long depth_sum(const youth_icp_ctx* c, const int16_t* d)
 {
@@ -48,12 +68,51 @@ static long long depth_sum(const youth_icp_ctx* c, const int16_t* d)
     return s;
 }
 
+/* the page-locked buffers alive, with their sizes */
+#define STUB_LIVE_MAX 1024
+static struct { int16_t* p; size_t values; } g_live[STUB_LIVE_MAX];
+static pthread_mutex_t g_live_mu = PTHREAD_MUTEX_INITIALIZER;
+
 int16_t* youth_icp_host_alloc(size_t values)
 {
-    return values ? (int16_t*)malloc(values * sizeof(int16_t)) : NULL;
+    int16_t* p = values ? (int16_t*)malloc(values * sizeof(int16_t)) : NULL;
+    if (!p) return NULL;
+    pthread_mutex_lock(&g_live_mu);
+    int k = 0;
+    while (k < STUB_LIVE_MAX && g_live[k].p) ++k;
+    if (k == STUB_LIVE_MAX) abort();
+    g_live[k].p = p;
+    g_live[k].values = values;
+    pthread_mutex_unlock(&g_live_mu);
+    return p;
 }
 
-void youth_icp_host_free(int16_t* p) { free(p); }
+void youth_icp_host_free(int16_t* p)
+{
+    if (!p) return;
+    pthread_mutex_lock(&g_live_mu);
+    int k = 0;
+    while (k < STUB_LIVE_MAX && g_live[k].p != p) ++k;
+    if (k == STUB_LIVE_MAX) abort(); /* not a page-locked buffer, or freed twice */
+    g_live[k].p = NULL;
+    pthread_mutex_unlock(&g_live_mu);
+    free(p);
+}
+
+/* values of the smallest page-locked buffer alive (0: none), their number in *count */
+size_t youth_stub_host_min_values(int* count)
+{
+    size_t m = 0;
+    int n = 0;
+    pthread_mutex_lock(&g_live_mu);
+    for (int k = 0; k < STUB_LIVE_MAX; ++k)
+        if (g_live[k].p) {
+            if (n++ == 0 || g_live[k].values < m) m = g_live[k].values;
+        }
+    pthread_mutex_unlock(&g_live_mu);
+    if (count) *count = n;
+    return m;
+}
 
 int youth_icp_device_count(void) { return 1; }
 const char* youth_icp_last_error(void) { return "stub"; }
@@ -72,6 +131,8 @@ youth_icp_ctx* youth_icp_create(int device, int W, int H, int max_frames,
     if (c) c->W = W, c->H = H;
     const char* e = getenv("YOUTH_STUB_TIMEOUT_EVERY");
     if (c && e) c->timeout_every = atoi(e);
+    e = getenv("YOUTH_STUB_REFUSE_AT");
+    if (c && e) c->refuse_at = atoi(e);
     return c;
 }
 
@@ -146,13 +207,15 @@ int youth_icp_track_submit_batch(youth_icp_ctx* c, const int16_t* depth, int n_f
     if (n_frames < 1 || n_frames > YOUTH_TRACK_MAX_BATCH ||
         c->n + n_frames > YOUTH_TRACK_MAX_IN_FLIGHT)
         return YOUTH_EINVAL;
+    const int asked = n_frames;
+    n_frames = stub_accept(c, asked);
     const int first_alone = !c->has_ref;
     const int chain = n_frames - first_alone > 1;
     for (int i = 0; i < n_frames; ++i)
         youth_icp_track_submit(c, depth + (size_t)i * c->W * c->H, NULL);
     c->chained += chain;
     c->chained_frames += chain ? n_frames - first_alone : 0;
-    return 0;
+    return n_frames < asked ? YOUTH_EINVAL : 0;
 }
 
 int youth_icp_track_submit_pinned(youth_icp_ctx* c, const int16_t* const* frames, int n_frames)
@@ -160,6 +223,8 @@ int youth_icp_track_submit_pinned(youth_icp_ctx* c, const int16_t* const* frames
     if (n_frames < 1 || n_frames > YOUTH_TRACK_MAX_BATCH ||
         c->n + n_frames > YOUTH_TRACK_MAX_IN_FLIGHT)
         return YOUTH_EINVAL;
+    const int asked = n_frames;
+    n_frames = stub_accept(c, asked);
     const int first_alone = !c->has_ref;
     const int chain = n_frames - first_alone > 1;
     for (int i = 0; i < n_frames; ++i) {
@@ -170,7 +235,7 @@ int youth_icp_track_submit_pinned(youth_icp_ctx* c, const int16_t* const* frames
     }
     c->chained += chain;
     c->chained_frames += chain ? n_frames - first_alone : 0;
-    return 0;
+    return n_frames < asked ? YOUTH_EINVAL : 0;
 }
 
 int youth_icp_track_frame(youth_icp_ctx* c, const int16_t* depth, const double* T_init,

@@ -8,6 +8,9 @@
 // (sum of the last frame - sum of the first) * 1e-6 and the driver can check
 // that every frame, colour included, reached the trajectory in order.  Frames
 // are read in place: a buffer changed between submit and collect aborts.
+// YOUTH_STUB_RGBD_REFUSE_AT=k (read at create) makes the tracker refuse its
+// k-th submission whole, as the real one does (all or nothing);
+// youth_rgbd_stub_refused_frames counts the frames refused so.
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
@@ -31,7 +34,11 @@ struct Stub {
     Frame f[2 * YOUTH_TRACK_MAX_BATCH];  // submitted, not collected (oldest first)
     int sub_m[2];                        // frames left of the submissions in flight
     int n, subs;
+    int refuse_at, submits;  // YOUTH_STUB_RGBD_REFUSE_AT; submissions asked for so far
 };
+
+// frames of the submissions the stub refused (all trackers)
+long long g_refused = 0;
 
 long long frame_sum(const Stub* s, const int16_t* d, const uint8_t* c)
 {
@@ -49,6 +56,8 @@ void* stub_create(int device, int w, int h, int batch, const youth_intrinsics* K
     (void)device, (void)K;
     Stub* s = static_cast<Stub*>(calloc(1, sizeof(Stub)));
     if (s) s->W = w, s->H = h, s->batch = batch;
+    const char* e = getenv("YOUTH_STUB_RGBD_REFUSE_AT");
+    if (s && e) s->refuse_at = atoi(e);
     return s;
 }
 
@@ -64,6 +73,10 @@ int stub_submit(void* t, const int16_t* const* depth, const uint8_t* const* rgb,
     if (!s || !depth || !rgb || n < 1 || n > s->batch || s->subs >= 2) return YOUTH_EINVAL;
     for (int i = 0; i < n; ++i)
         if (!depth[i] || !rgb[i]) return YOUTH_EINVAL;
+    if (s->refuse_at > 0 && ++s->submits == s->refuse_at) {  // all or nothing: no frame taken
+        __atomic_fetch_add(&g_refused, (long long)n, __ATOMIC_SEQ_CST);
+        return YOUTH_EINVAL;
+    }
     for (int i = 0; i < n; ++i) {
         Frame& f = s->f[s->n++];
         f.d = depth[i];
@@ -117,3 +130,9 @@ struct Registrar {
 } g_registrar;
 
 }  // namespace
+
+// stub only (declared in rgbd_driver.cpp): frames of refused submissions
+extern "C" long long youth_rgbd_stub_refused_frames(void)
+{
+    return __atomic_load_n(&g_refused, __ATOMIC_SEQ_CST);
+}
