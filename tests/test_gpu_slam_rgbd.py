@@ -26,9 +26,10 @@ import numpy as np
 import youth_icp, youth_map, youth_synth
 out, plan = sys.argv[1], json.loads(sys.argv[2])
 W, H, n = plan["W"], plan["H"], plan["n"]
-fr, _, rgb = youth_synth.sequence_rgb(0, n, W, H)
+K = youth_icp.Intrinsics(*plan["K"]) if plan.get("K") else None
+fr, _, rgb = youth_synth.sequence_rgb(0, n, W, H, K=K)
 res = {}
-youth_icp.initSlamModule(None)
+youth_icp.initSlamModule(plan.get("config"))
 assert youth_icp.isSlamModuleRunning() == 1
 try:
     res["active"] = youth_icp.slam_rgbd_active()
@@ -128,6 +129,41 @@ def test_rgbd_mode_tracks_with_colour(tmp_path, seq8):
     _, live, res1 = _run_child(tmp_path, "live", {"YOUTH_SLAM_RGBD": "1"}, backlog=False)
     assert live["active"] == 1 and live["batched"] == 0
     assert np.array_equal(res1["T"], res["T"]) and np.array_equal(res1["ts"], res["ts"])
+
+
+def test_rgbd_mode_tracks_with_the_camera_of_the_config_file(tmp_path):
+    """initSlamModule with a camera file whose fx != fy: the worker hands that
+    camera to its RGB-D tracker (slam_api.cpp intrinsics_for ->
+    youth_rgbd_create), so the trajectory is the composed track of a context
+    made with it, bit for bit, and not the one the viewer's camera gives."""
+    W, H, n = 160, 120, 4
+    k = tuple(float(np.float32(v)) for v in (131.7, 197.3, 77.4, 62.6, 1000.0))
+    cfg = tmp_path / "camera.yaml"
+    cfg.write_text("%YAML:1.0\nCamera.type: \"PinHole\"\n"
+                   + "".join(f"Camera.{name}: {v!r}\n" for name, v in zip(("fx", "fy", "cx", "cy"), k))
+                   + f"Camera.width: {W}\nCamera.height: {H}\nDepthMapFactor: {k[4]!r}\n")
+    K, Wc, Hc = youth_icp.parse_camera_yaml(str(cfg))
+    assert (Wc, Hc) == (W, H) and K.as_tuple() == k and K.fx != K.fy
+    _, info, res = _run_child(tmp_path, "yaml", {"YOUTH_SLAM_RGBD": "1"}, W=W, H=H, n=n,
+                              backlog=False, config=str(cfg), K=list(k))
+    assert info["active"] == 1 and res["ts"].tolist() == list(range(n))
+    T = res["T"].reshape(-1, 4, 4)
+    fr, _, rgb = youth_synth.sequence_rgb(0, n, W, H, K=youth_icp.Intrinsics(*k))
+    trajs = []
+    for Kc in (youth_icp.Intrinsics(*k), None):
+        with youth_rgbd.RgbdContext(W, H, 16, K=Kc) as ctx:
+            ctx.track_set_batch(8)
+            ctx.track_submit(list(fr), list(rgb))
+            traj = [np.eye(4)]
+            for f in range(n):
+                T_rel, has, st = ctx.track_collect()
+                assert st == 0 and has == int(f > 0)
+                if has:
+                    traj.append(_mat_mul4(traj[-1], T_rel))
+        trajs.append(np.array(traj))
+    assert np.array_equal(T, trajs[0])
+    print("max |T - T under the viewer's camera|:", np.abs(T - trajs[1]).max())
+    assert np.abs(T - trajs[1]).max() > 1e-4
 
 
 # ------------------------------------------------------------- default mode --

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle
+import rgbd_draws
 import rgbd_truth
 import youth_synth
 from conftest import GOLDEN
@@ -134,6 +135,77 @@ def test_truth_at_lambda_zero_equals_oracle_bitwise(name):
             want = oracle.reduce(src, dst, T12, K, thr)
         assert np.array_equal(got[:29].view(np.uint64), want.view(np.uint64))
         assert got[28] > 0 and got[29] == 0.0 and got[30] == got[28]
+
+
+@pytest.mark.parametrize("W,H", [(97, 53), (160, 120)])
+def test_truth_at_lambda_zero_equals_oracle_bitwise_random_intrinsics(W, H):
+    """The geometric half under the cameras of tests/rgbd_draws.py (fx != fy,
+    fractional principal points, three depth scales), scenes rendered with the
+    same camera."""
+    rng = np.random.default_rng(7 + W)
+    th = np.deg2rad(3.0)
+    R = np.array([[np.cos(th), 0, np.sin(th)], [0, 1, 0], [-np.sin(th), 0, np.cos(th)]])
+    draws = rgbd_draws.camera_draws(W, H)
+    assert len(draws) >= 6
+    for d, k in enumerate(draws):
+        src, dst, _ = youth_synth.pairs(400 + d, 1, W, H, K=rgbd_draws.intrinsics(k))
+        src, dst = src[0], dst[0]
+        sg = rng.integers(0, 256, src.shape, dtype=np.uint8)
+        dg = rng.integers(0, 256, src.shape, dtype=np.uint8)
+        for T in (np.eye(4)[:3], np.hstack([np.eye(3), [[0.004], [-0.002], [0.003]]]),
+                  np.hstack([R, [[0.04], [0.01], [-0.02]]])):
+            T12 = T.astype(f32)
+            got = rgbd_truth.reduce(src, sg, dst, dg, T12, k, 0.10, lam=0.0)
+            with oracle.spec("survey"):
+                want = oracle.reduce(src, dst, T12, oracle.K_of(k), 0.10)
+            assert np.array_equal(got[:29].view(np.uint64), want.view(np.uint64)), (d, k)
+            assert got[28] > 0 and got[29] == 0.0 and got[30] == got[28], (d, k)
+
+
+def test_photometric_jacobian_is_the_derivative_of_the_residual():
+    """Jp against central differences of rp, under a camera with fx != fy: the
+    check that §13's constants kx = 0.5 w fx and ky = 0.5 w fy are the right
+    ones, which restating the definition cannot give.  The target intensity is
+    the integer ramp Y = 2u - v + 80 (gx = 4 and gy = -2 exactly), so It = 2 uf -
+    vf + 80 is linear in the projection whichever pixel it rounds to, and rp is
+    smooth in the pose.  Measured: differences of at most 2.1e-5 against |Jp| up
+    to 0.47; exchanging kx and ky moves the y-dependent part by 1 - 61.7 / 92.3
+    = 33 %.  1e-3 leaves 50x for the fp32 noise of rp over 2 eps."""
+    W, H, lam, eps = 64, 48, 0.7, 2e-3
+    k = (61.7, 92.3, 29.4, 26.2, 1000.0)
+    src, dst, _, srgb, _ = youth_synth.pairs_rgb(300, 1, W, H, K=rgbd_draws.intrinsics(k))
+    src, dst, sg = src[0], dst[0], rgbd_truth.luma(srgb[0])
+    u, v = np.meshgrid(np.arange(W), np.arange(H))
+    ramp = 2 * u - v + 80
+    assert ramp.min() >= 0 and ramp.max() <= 255
+    dg = ramp.astype(np.uint8)
+    gx, gy, valid = rgbd_truth.photo_record(dg)
+    assert (gx[valid] == 4).all() and (gy[valid] == -2).all()
+    T = np.eye(4)
+    T[:3, 3] = (0.004, -0.002, 0.003)
+
+    def at(Tp):
+        _, _, Jp, rp, pv, m, _ = rgbd_truth.terms(src, sg, dst, dg, Tp[:3].astype(f32), k, 0.10, lam)
+        return m[pv], rp[pv].astype(f64), [a[pv].astype(f64) for a in Jp]
+
+    m0, _, Jp0 = at(T)
+    assert m0.size >= 1000
+    worst, big = 0.0, 0.0
+    for c in range(6):
+        xi = np.zeros(6)
+        xi[c] = eps
+        mp, rp_p, _ = at(oracle.se3_exp(xi) @ T)
+        mm, rp_m, _ = at(oracle.se3_exp(-xi) @ T)
+        both = np.intersect1d(np.intersect1d(m0, mp), mm)      # matched in all three
+        assert both.size >= m0.size / 2, (c, both.size, m0.size)
+        diff = (rp_p[np.searchsorted(mp, both)] - rp_m[np.searchsorted(mm, both)]) / (2 * eps)
+        Jc = Jp0[c][np.searchsorted(m0, both)]
+        err = float(np.abs(diff - Jc).max())
+        print(f"twist {c}: {both.size} of {m0.size} pixels, max |Jp| {np.abs(Jc).max():.3f}, "
+              f"max |difference - Jp| {err:.2e}")
+        assert err <= 1e-3, (c, err)
+        worst, big = max(worst, err), max(big, float(np.abs(Jc).max()))
+    assert big >= 0.1          # the bound is far below the Jacobian it checks
 
 
 # ------------------------------------------------------------------- synth --
