@@ -43,6 +43,7 @@
 #include <vector>
 
 #include "host_copy.h"
+#include "slam_loop_hooks.h"
 #include "slam_map_hooks.h"
 #include "slam_rgbd_hooks.h"
 #include "youth_map.h"
@@ -596,6 +597,9 @@ std::vector<PoseRec> g_traj;
 // linked in; its integrate / clear run under g_slam_mu, next to the
 // trajectory change they belong to
 std::atomic<const youth_slam_map_hooks*> g_map_hooks{nullptr};
+// the loop closer's hook table (slam_loop_hooks.h): null unless slam_loop.cpp
+// is linked in; called beside the map's hooks, off unless YOUTH_SLAM_LOOP=1
+std::atomic<const youth_slam_loop_hooks*> g_loop_hooks{nullptr};
 // g_traj.size(), stored under g_slam_mu after every change: a host polling
 // for its pose (youth_slam_trajectory_length) does not take the lock the
 // worker records every pose under
@@ -802,6 +806,7 @@ void record_pose(const Pending& f, int st, int has_ref, const double* T_rel, dou
         g_traj.clear();
         g_traj_len.store(0, std::memory_order_release);
         if (const youth_slam_map_hooks* mh = g_map_hooks.load()) mh->clear();
+        if (const youth_slam_loop_hooks* lh = g_loop_hooks.load()) lh->clear();
     } else {
         // P_ref = T_rel P_new  =>  T_w_new = T_w_ref * T_rel
         mat_mul4(T_w_ref, T_rel, T_w_ref);
@@ -822,6 +827,11 @@ void record_pose(const Pending& f, int st, int has_ref, const double* T_rel, dou
     if (const youth_slam_map_hooks* mh = g_map_hooks.load()) {
         const youth_intrinsics K = intrinsics_for(f.item.w, f.item.h);
         mh->integrate(f.item.d(), f.item.rgb(), f.item.w, f.item.h, &K, T_w_ref);
+    }
+    // so does the loop closer, which picks its keyframes among them
+    if (const youth_slam_loop_hooks* lh = g_loop_hooks.load()) {
+        const youth_intrinsics K = intrinsics_for(f.item.w, f.item.h);
+        lh->frame(f.item.d(), f.item.rgb(), f.item.w, f.item.h, &K, T_w_ref, f.ts);
     }
 }
 
@@ -1073,6 +1083,18 @@ int write_tum(const std::string& path, const std::vector<PoseRec>& traj)
     return ok;
 }
 
+// timestamps and 16 fp64 values per pose as trajectory records
+std::vector<PoseRec> pose_recs(const std::vector<uint32_t>& ts, const std::vector<double>& T)
+{
+    std::vector<PoseRec> out(ts.size());
+    for (size_t k = 0; k < ts.size(); ++k) {
+        out[k].ts = ts[k];
+        out[k].status = 0;
+        memcpy(out[k].T, T.data() + k * 16, sizeof(out[k].T));
+    }
+    return out;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1133,6 +1155,7 @@ void initSlamModule(const char* config_file, const char* vocabulary_file)
     g_traj_len.store(0, std::memory_order_release);
     g_last_points = 0;
     if (const youth_slam_map_hooks* mh = g_map_hooks.load()) mh->start(device);
+    if (const youth_slam_loop_hooks* lh = g_loop_hooks.load()) lh->start(device);
     g_process.store(true);
     g_batched.store(0);
     for (auto& r : g_realigned) r.store(0);
@@ -1167,6 +1190,7 @@ void stopSlamModule(void)
     if (g_worker.joinable()) g_worker.join();
     if (g_queue) youth_queue_clear(g_queue);
     if (const youth_slam_map_hooks* mh = g_map_hooks.load()) mh->stop();
+    if (const youth_slam_loop_hooks* lh = g_loop_hooks.load()) lh->stop();
     {
         std::lock_guard<std::mutex> sl(g_state_mu);
         g_running.store(false);
@@ -1216,10 +1240,21 @@ int saveSlamMap(const char* map_file)
         traj = g_traj;
     }
     const std::string base(map_file);
-    // every frame is tracked frame-to-frame, so the keyframe file equals the
-    // trajectory (SLAM.cpp:188 writes both)
-    int ok = write_tum(base + "_trajectory.txt", traj) &&
-             write_tum(base + "_keyframes.txt", traj);
+    // every frame is tracked frame-to-frame, so without loop closing the
+    // keyframe file equals the trajectory (SLAM.cpp:188 writes both); with it
+    // (YOUTH_SLAM_LOOP=1, youth_loop.h) the file holds the optimised keyframes
+    // and the corrected trajectory goes beside the recorded one
+    std::vector<uint32_t> kf_ts, cl_ts;
+    std::vector<double> kf_T, cl_T;
+    const youth_slam_loop_hooks* lh = g_loop_hooks.load();
+    const bool closed = lh && lh->corrected(kf_ts, kf_T, cl_ts, cl_T);
+    int ok = write_tum(base + "_trajectory.txt", traj);
+    if (closed) {
+        ok = write_tum(base + "_keyframes.txt", pose_recs(kf_ts, kf_T)) && ok;
+        ok = write_tum(base + "_trajectory_closed.txt", pose_recs(cl_ts, cl_T)) && ok;
+    } else {
+        ok = ok && write_tum(base + "_keyframes.txt", traj);
+    }
     // <map_file>_map.ply when the voxel map is on (youth_map.h)
     if (const youth_slam_map_hooks* mh = g_map_hooks.load()) ok = mh->save(map_file) && ok;
     if (ok)
@@ -1251,6 +1286,7 @@ void resetSlam(void)
         g_traj_len.store(0, std::memory_order_release);
         g_last_points = 0;
         if (const youth_slam_map_hooks* mh = g_map_hooks.load()) mh->clear();
+        if (const youth_slam_loop_hooks* lh = g_loop_hooks.load()) lh->clear();
     }
     fprintf(stderr, "youth_icp: SLAM system reset\n");
 }
@@ -1317,6 +1353,8 @@ int youth_slam_wait_idle(int timeout_ms)
 }
 
 void youth_slam_set_map_hooks(const youth_slam_map_hooks* hooks) { g_map_hooks.store(hooks); }
+
+void youth_slam_set_loop_hooks(const youth_slam_loop_hooks* hooks) { g_loop_hooks.store(hooks); }
 
 void youth_slam_set_rgbd_hooks(const youth_slam_rgbd_hooks* hooks) { g_rgbd_hooks.store(hooks); }
 
