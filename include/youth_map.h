@@ -62,7 +62,8 @@ struct youth_map_stats {
     uint64_t integrated;    /* points added to a voxel */
     uint64_t out_of_range;  /* contributing pixels whose voxel index left [-2^20, 2^20) */
     uint64_t dropped;       /* points that found no slot within the probe bound */
-    uint64_t occupied;      /* slots holding a voxel (= youth_map_voxels) */
+    uint64_t occupied;      /* slots holding a voxel (= youth_map_voxels); an upper bound on
+                               the voxels once something was removed (youth_map_remove.h) */
     uint64_t direct;        /* points sent straight to the global table: their workgroup's
                                LDS table was full (every point with YOUTH_MAP_LDS=0) */
     uint64_t capacity;      /* slots of the table */
@@ -107,12 +108,13 @@ int youth_map_integrate_device(youth_map* map, const int16_t* d_depth, const uin
 int youth_map_integrate_host(youth_map* map, const int16_t* depth, const uint8_t* rgb, int W,
                              int H, const youth_intrinsics* K, const double* T_world);
 
-/* Voxels in the map; waits for the map's stream. */
+/* Slots holding a key: the voxels in the map, or an upper bound on them once
+ * something was removed (youth_map_remove.h); waits for the map's stream. */
 long long youth_map_voxels(youth_map* map);
 
-/* The map's records sorted by (iz, iy, ix) into out[cap]; returns their
- * number, or YOUTH_EINVAL when cap is too small.  Waits for the map's stream;
- * integration may continue afterwards. */
+/* The map's records sorted by (iz, iy, ix) into out[cap]; returns their exact
+ * number, or YOUTH_EINVAL when cap is below youth_map_voxels.  Waits for the
+ * map's stream; integration may continue afterwards. */
 int youth_map_extract(youth_map* map, youth_voxel* out, int cap);
 
 /* The counters; waits for the map's stream. */
@@ -145,6 +147,7 @@ long long youth_slam_map_voxels(void);                    /* 0 when disabled */
 int youth_slam_map_extract(youth_voxel* out, int cap);    /* as youth_map_extract; 0 when disabled */
 float youth_slam_map_vpm(void);                           /* 0 when disabled */
 
+
 #ifdef __cplusplus
 }
 #endif
@@ -152,5 +155,10 @@ float youth_slam_map_vpm(void);                           /* 0 when disabled */
 /* Rendering the map into depth and colour frames from any pose (DESIGN.md
  * §12): part of this interface, kept in a file of its own. */
 #include "youth_map_render.h"
+
+/* Taking frames out of the map again, moving them to other poses and
+ * re-integrating the SLAM module's map after a loop closure (DESIGN.md §10,
+ * §15): part of this interface, kept in a file of its own. */
+#include "youth_map_remove.h"
 
 #endif /* YOUTH_MAP_H */

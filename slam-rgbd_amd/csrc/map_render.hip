@@ -74,7 +74,9 @@ __device__ __forceinline__ bool project(const MapTable& t, uint32_t slot, const 
     const uint4 a = rec[0];   // count, sum_q
     const uint4 b = rec[1];   // sum_c, pad
     const uint32_t count = a.x;
-    if (count < P.min_count) return false;   // min_count >= 1: no division by 0
+    // min_count >= 1: no division by 0, and a slot vacated by a removal (its key
+    // kept, count 0: youth_map_remove.h) is no voxel here either
+    if (count < P.min_count) return false;
     int32_t ix, iy, iz;
     key_cell(key, ix, iy, iz);
     const float fc = (float)count;

@@ -1256,7 +1256,16 @@ int saveSlamMap(const char* map_file)
         ok = ok && write_tum(base + "_keyframes.txt", traj);
     }
     // <map_file>_map.ply when the voxel map is on (youth_map.h)
-    if (const youth_slam_map_hooks* mh = g_map_hooks.load()) ok = mh->save(map_file) && ok;
+    if (const youth_slam_map_hooks* mh = g_map_hooks.load()) {
+        ok = mh->save(map_file) && ok;
+        // <map_file>_map_closed.ply when the map keeps its frames
+        // (YOUTH_SLAM_MAP_KEEP): the map re-integrated with the corrected
+        // trajectory; no frame is recorded meanwhile
+        if (closed && !cl_T.empty() && mh->save_closed) {
+            std::lock_guard<std::mutex> lk(g_slam_mu);
+            ok = mh->save_closed(map_file, (int)(cl_T.size() / 16), cl_T.data()) && ok;
+        }
+    }
     if (ok)
         fprintf(stderr, "youth_icp: map saved to %s\n", map_file);
     else
@@ -1372,6 +1381,17 @@ int youth_slam_map_render(const struct youth_map_view* view, const youth_intrins
     if (!T_world && g_traj.empty()) return 0;
     const youth_intrinsics Kd = K ? *K : intrinsics_for(view->W, view->H);
     return mh->render(view, &Kd, T_world ? T_world : g_traj.back().T, depth, rgb);
+}
+
+// youth_map.h: the kept frames moved to a corrected trajectory; under the
+// trajectory lock, so no frame is recorded (and integrated) in between
+int youth_slam_map_reintegrate(int n, const double* T_wc)
+{
+    const youth_slam_map_hooks* mh = g_map_hooks.load();
+    if (!mh || !mh->reintegrate) return 0;
+    if (n < 0 || (n > 0 && !T_wc)) return YOUTH_EINVAL;
+    std::lock_guard<std::mutex> lk(g_slam_mu);
+    return mh->reintegrate(n, T_wc);
 }
 
 // recorded from inside the tracker (icp_track.cpp: a submission's steps)

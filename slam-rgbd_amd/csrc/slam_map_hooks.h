@@ -29,6 +29,16 @@ struct youth_slam_map_hooks {
     // resolved: 1 rendered, 0 map off or failed (outputs untouched)
     int (*render)(const struct youth_map_view* view, const youth_intrinsics* K,
                   const double* T_world, int16_t* depth, uint8_t* rgb);
+    // The two below stand last and may be null (a table aggregate-initialised
+    // without them, as the sanitizer drivers' is): null means off.
+    // youth_slam_map_reintegrate, called under the trajectory lock: the kept
+    // frames i < n moved to T_wc[i] (fp64 4x4 each); the number of frames whose
+    // pose changed, 0 when the map or its frame store is off, or a negative code
+    int (*reintegrate)(int n, const double* T_wc);
+    // saveSlamMap with loop closing on, after save and under the trajectory
+    // lock: re-integrate with the corrected trajectory, compact, write
+    // <base>_map_closed.ply; 1 written or nothing to do (store off), 0 failed
+    int (*save_closed)(const char* base, int n, const double* T_wc);
 };
 
 extern "C" void youth_slam_set_map_hooks(const youth_slam_map_hooks* hooks);

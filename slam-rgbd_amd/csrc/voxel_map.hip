@@ -20,8 +20,18 @@
 //                    A run that finds no room in the LDS table within its
 //                    probe bound goes straight to the global table; with
 //                    YOUTH_MAP_LDS=0 every run does (no LDS is allocated).
-//   k_map_extract    compacts the occupied slots into youth_voxel records
-//                    (slot order; the host sorts).
+//   k_map_update     the same tile code (voxel_map_tile.inc) taking frames out
+//                    again (youth_map_remove.h): the LDS table sums a tile's runs
+//                    as before, and each of its slots is then looked up in the
+//                    global table without claiming anything and subtracted, the
+//                    count with a returning atomic (an old value below the
+//                    subtrahend is an underflow), the sums without.  A voxel
+//                    emptied this way keeps its slot and key (count 0) for the
+//                    next integration of the voxel.  Also both legs of a move.
+//   k_map_extract    compacts the live slots (count > 0) into youth_voxel
+//                    records (slot order; the host sorts).
+//   k_map_scan       counts live, vacant and stale slots, on request.
+//   k_map_rehash     compaction: every live slot into a fresh table.
 //
 // The table's layout is shared with map_render.hip (map_table.h), which renders
 // the map from a pose and reaches a youth_map through youth_map_render_acquire.
@@ -53,7 +63,10 @@ constexpr int kMapPx = 8;                       // pixels per thread
 constexpr int kLdsSlots = kMapThreads * kMapPx / 2;   // per-workgroup table: half the tile
 constexpr int kLdsProbe = 8;                    // LDS probe bound
 constexpr int kProbe = 128;                     // global probe bound
-enum { kStIntegrated, kStOutOfRange, kStDropped, kStOccupied, kStDirect, kStExtracted, kStN };
+enum { kStIntegrated, kStOutOfRange, kStDropped, kStOccupied, kStDirect, kStExtracted,
+       // removal (k_map_update), the scan and the rehash: beside the above, so that
+       // struct youth_map_stats keeps its size
+       kStRemoved, kStMissing, kStUnderflow, kStLive, kStVacant, kStStale, kStRehashFail, kStN };
 
 struct Acc {
     unsigned long long key;
@@ -111,14 +124,63 @@ __device__ __forceinline__ bool global_slot(const MapTable& t, unsigned long lon
     return false;
 }
 
+// The slot of `key`, never claiming one: false when an empty slot or the probe
+// bound is reached first (the key is absent).  Removal runs after the
+// integrations it undoes, in stream order, so every key it looks for is visible.
+__device__ __forceinline__ bool global_find(const MapTable& t, unsigned long long key, uint32_t& slot)
+{
+    const uint32_t h = (uint32_t)mix64(key);
+    for (int p = 0; p < kProbe; ++p) {
+        const uint32_t s = (h + (uint32_t)p) & t.mask;
+        const unsigned long long k =
+            __hip_atomic_load(&t.keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == key) {
+            slot = s;
+            return true;
+        }
+        if (k == kEmpty) return false;
+    }
+    return false;
+}
+
+// A removing launch counts removed / missing / underflow where an adding one
+// counts integrated / dropped / occupied; out_of_range and direct it leaves alone.
 struct Tally {
     uint32_t integrated = 0, out_of_range = 0, dropped = 0, occupied = 0, direct = 0;
 };
 
-// A run (or an LDS slot's sum) into the global table.
+// A run (or an LDS slot's sum) out of the global table.  The slot keeps its key
+// (open addressing cannot hand it back): a vacated slot has count 0.  The count
+// is subtracted with a returning atomic, which is what detects an underflow; the
+// sums need no answer.
 template <bool kRgb>
+__device__ __forceinline__ void global_sub(const MapTable& t, const Acc& a, Tally& n)
+{
+    uint32_t slot;
+    if (!global_find(t, a.key, slot)) {
+        n.dropped += a.cnt;   // missing
+        return;
+    }
+    uint32_t* v = t.vals + (size_t)slot * kValWords;
+    const uint32_t old = atomicSub(v + 0, a.cnt);
+    if (old < a.cnt) ++n.occupied;   // one underflow event
+#pragma unroll
+    for (int j = 0; j < 3; ++j) atomicSub(v + 1 + j, a.q[j]);
+    if (kRgb) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) atomicSub(v + 4 + j, a.c[j]);
+    }
+    n.integrated += a.cnt;   // removed
+}
+
+// A run (or an LDS slot's sum) into the global table, or with kRemove out of it.
+template <bool kRgb, bool kRemove = false>
 __device__ __forceinline__ void global_add(const MapTable& t, const Acc& a, Tally& n)
 {
+    if (kRemove) {
+        global_sub<kRgb>(t, a, n);
+        return;
+    }
     uint32_t slot;
     if (!global_slot(t, a.key, slot, n.occupied)) {
         n.dropped += a.cnt;
@@ -140,7 +202,7 @@ struct LdsTable {
     uint32_t vals[7][kLdsSlots];   // [word][slot]: a flush reads consecutive banks
 };
 
-template <bool kLds, bool kRgb>
+template <bool kLds, bool kRgb, bool kRemove = false>
 __device__ __forceinline__ void emit_run(const MapTable& t, LdsTable* lt, const Acc& a, Tally& n)
 {
     if (kLds) {
@@ -160,8 +222,8 @@ __device__ __forceinline__ void emit_run(const MapTable& t, LdsTable* lt, const 
             }
         }
     }
-    n.direct += a.cnt;   // the LDS table has no room for this key (or there is none)
-    global_add<kRgb>(t, a, n);
+    if (!kRemove) n.direct += a.cnt;   // the LDS table has no room for this key (or there is none)
+    global_add<kRgb, kRemove>(t, a, n);
 }
 
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x)
@@ -176,109 +238,35 @@ __global__ __launch_bounds__(kMapThreads) void k_map_integrate(
     const int16_t* __restrict__ depth, const uint8_t* __restrict__ rgb, int W, int N, CloudK K,
     const float* __restrict__ T_world, float vpm, int max_depth, MapTable t)
 {
-    __shared__ __align__(8) unsigned char lds_raw[kLds ? sizeof(LdsTable) : 8];
-    LdsTable* lt = reinterpret_cast<LdsTable*>(lds_raw);   // unused without kLds
-    if (kLds) {
-        for (int s = threadIdx.x; s < kLdsSlots; s += kMapThreads) {
-            lt->keys[s] = kEmpty;
-#pragma unroll
-            for (int j = 0; j < 7; ++j) lt->vals[j][s] = 0;
-        }
-        __syncthreads();
-    }
-    const int f = blockIdx.y, tile = blockIdx.x;
-    const int i = (tile * kMapThreads + threadIdx.x) * kMapPx;
-    int dd[kMapPx];
-    youth_cloud::load_depth<kVec, kMapPx>(depth + (size_t)f * N, i, N, dd);
-    unsigned char cc[kMapPx * 3];
-    if (kRgb) {
-        youth_cloud::load_rgb<kVec, kMapPx>(rgb + ((size_t)f * N + i) * 3, i, N, cc);
-    } else {
-#pragma unroll
-        for (int k = 0; k < kMapPx * 3; ++k) cc[k] = 0;
-    }
-    // frame f's camera -> world pose, or the identity: one path, the same fma chains
-    float Tw[12] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f};
-    if (T_world) {
-#pragma unroll
-        for (int q = 0; q < 12; ++q) Tw[q] = T_world[(size_t)f * 12 + q];
-    }
-    Tally n;
-    Acc cur;
-    bool have = false;
-    // (u, v) of pixel i; a thread's pixels may wrap rows (any W >= 1)
-    int v = i / W;
-    int u = i - v * W;
-#pragma unroll
-    for (int k = 0; k < kMapPx; ++k) {
-        const int d = dd[k];
-        if (d > 0 && (max_depth == 0 || d <= max_depth)) {
-            float x, y, z;
-            youth_cloud::camera_point(d, u, v, K, x, y, z);
-            const float X = youth_cloud::world_axis(Tw, x, y, z);
-            const float Y = youth_cloud::world_axis(Tw + 4, x, y, z);
-            const float Z = youth_cloud::world_axis(Tw + 8, x, y, z);
-            uint32_t cx, cy, cz, qx, qy, qz;
-            const bool in = axis_key(X, vpm, cx, qx) && axis_key(Y, vpm, cy, qy) &&
-                            axis_key(Z, vpm, cz, qz);
-            if (in) {
-                const unsigned long long key =
-                    ((unsigned long long)cz << 42) | ((unsigned long long)cy << 21) | cx;
-                if (have && key != cur.key) {
-                    emit_run<kLds, kRgb>(t, lt, cur, n);
-                    have = false;
-                }
-                if (!have) {
-                    cur.key = key;
-                    cur.cnt = 0;
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) cur.q[j] = cur.c[j] = 0;
-                    have = true;
-                }
-                ++cur.cnt;
-                cur.q[0] += qx;
-                cur.q[1] += qy;
-                cur.q[2] += qz;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) cur.c[j] += cc[3 * k + j];
-            } else {
-                ++n.out_of_range;
-            }
-        }
-        ++u;
-        while (u >= W) {
-            u -= W;
-            ++v;
-        }
-    }
-    if (have) emit_run<kLds, kRgb>(t, lt, cur, n);
-    if (kLds) {
-        __syncthreads();
-        for (int s = threadIdx.x; s < kLdsSlots; s += kMapThreads) {
-            Acc a;
-            a.key = lt->keys[s];
-            if (a.key == kEmpty) continue;
-            a.cnt = lt->vals[0][s];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                a.q[j] = lt->vals[1 + j][s];
-                a.c[j] = lt->vals[4 + j][s];
-            }
-            global_add<kRgb>(t, a, n);
-        }
-    }
-    // the counters: one add per wave and counter that has something to add
-    const uint32_t sums[5] = {wave_sum_u32(n.integrated), wave_sum_u32(n.out_of_range),
-                              wave_sum_u32(n.dropped), wave_sum_u32(n.occupied),
-                              wave_sum_u32(n.direct)};
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < 5; ++j)
-            if (sums[j]) atomicAdd(&t.stats[j], (unsigned long long)sums[j]);
-    }
+    constexpr bool kRemove = false;
+#include "voxel_map_tile.inc"
 }
 
-// Occupied slots -> records, in slot order of arrival (the host sorts).
+// k_map_integrate's removing form (kRemove) and the two legs of a move: the
+// same tile code.  T_other, when given, is the move's other pose array: a frame
+// whose twelve floats are bitwise equal in both stays where it is and is
+// skipped by both legs.  The test is uniform over the workgroup, so the early
+// return is taken before any barrier by all of its threads or by none.
+template <bool kVec, bool kLds, bool kRgb, bool kRemove>
+__global__ __launch_bounds__(kMapThreads) void k_map_update(
+    const int16_t* __restrict__ depth, const uint8_t* __restrict__ rgb, int W, int N, CloudK K,
+    const float* __restrict__ T_world, const float* __restrict__ T_other, float vpm, int max_depth,
+    MapTable t)
+{
+    if (T_other) {
+        const size_t at = (size_t)blockIdx.y * 12;
+        bool same = true;
+#pragma unroll
+        for (int q = 0; q < 12; ++q)
+            same = same && __float_as_uint(T_world[at + q]) == __float_as_uint(T_other[at + q]);
+        if (same) return;
+    }
+#include "voxel_map_tile.inc"
+}
+
+// Live slots -> records, in slot order of arrival (the host sorts).  A slot
+// vacated by a removal (count 0) holds no record; a map that was only ever
+// added to has none, because a claimed slot receives its add in the same launch.
 __global__ __launch_bounds__(kMapThreads) void k_map_extract(MapTable t, youth_voxel* __restrict__ out,
                                                              uint32_t cap)
 {
@@ -286,9 +274,10 @@ __global__ __launch_bounds__(kMapThreads) void k_map_extract(MapTable t, youth_v
     if (s > t.mask) return;
     const unsigned long long key = t.keys[s];
     if (key == kEmpty) return;
+    const uint32_t* v = t.vals + (size_t)s * kValWords;
+    if (v[0] == 0) return;
     const uint32_t at = (uint32_t)atomicAdd(&t.stats[kStExtracted], 1ull);
     if (at >= cap) return;
-    const uint32_t* v = t.vals + (size_t)s * kValWords;
     youth_voxel r;
     key_cell(key, r.ix, r.iy, r.iz);
     r.count = v[0];
@@ -297,6 +286,56 @@ __global__ __launch_bounds__(kMapThreads) void k_map_extract(MapTable t, youth_v
         r.sum_c[j] = v[4 + j];
     }
     out[at] = r;
+}
+
+// One pass over the table: live (key, count > 0), vacant (key, count 0) and
+// stale (vacant with a sum left over) slots, exact whatever was interleaved
+// before it.  The host zeroes the three counters first.
+__global__ __launch_bounds__(kMapThreads) void k_map_scan(MapTable t)
+{
+    const uint32_t s = blockIdx.x * kMapThreads + threadIdx.x;
+    uint32_t live = 0, vacant = 0, stale = 0;
+    if (s <= t.mask && t.keys[s] != kEmpty) {
+        const uint4* v = reinterpret_cast<const uint4*>(t.vals + (size_t)s * kValWords);
+        const uint4 a = v[0], b = v[1];   // count q q q | c c c pad
+        live = a.x != 0;
+        vacant = a.x == 0;
+        stale = vacant && (a.y | a.z | a.w | b.x | b.y | b.z) != 0;
+    }
+    const uint32_t sums[3] = {wave_sum_u32(live), wave_sum_u32(vacant), wave_sum_u32(stale)};
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            if (sums[j]) atomicAdd(&t.stats[kStLive + j], (unsigned long long)sums[j]);
+    }
+}
+
+// Every live slot of `t` into the fresh table (keys, vals) of the same
+// capacity.  Keys are unique, so a claim is one CAS on an empty slot and the
+// eight value words are plain stores.  A key that finds no slot within the
+// probe bound is counted (kStRehashFail, in the old table's stats) and the host
+// keeps the old table; the moved slots are counted as live.
+__global__ __launch_bounds__(kMapThreads) void k_map_rehash(MapTable t, unsigned long long* keys,
+                                                            uint32_t* vals)
+{
+    const uint32_t s = blockIdx.x * kMapThreads + threadIdx.x;
+    if (s > t.mask) return;
+    const unsigned long long key = t.keys[s];
+    if (key == kEmpty) return;
+    const uint4* v = reinterpret_cast<const uint4*>(t.vals + (size_t)s * kValWords);
+    if (t.vals[(size_t)s * kValWords] == 0) return;   // vacated: nothing to move
+    const uint32_t h = (uint32_t)mix64(key);
+    for (int p = 0; p < kProbe; ++p) {
+        const uint32_t d = (h + (uint32_t)p) & t.mask;
+        if (__hip_atomic_load(&keys[d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != kEmpty) continue;
+        if (atomicCAS(&keys[d], kEmpty, key) != kEmpty) continue;
+        uint4* o = reinterpret_cast<uint4*>(vals + (size_t)d * kValWords);
+        o[0] = v[0];   // count q q q
+        o[1] = v[1];   // c c c pad
+        atomicAdd(&t.stats[kStLive], 1ull);
+        return;
+    }
+    atomicAdd(&t.stats[kStRehashFail], 1ull);
 }
 
 }  // namespace
@@ -458,16 +497,22 @@ int youth_map_set_max_depth(youth_map* m, int max_depth)
     return YOUTH_OK;
 }
 
-int youth_map_integrate_device(youth_map* m, const int16_t* d_depth, const uint8_t* d_rgb,
-                               int n_frames, int W, int H, const youth_intrinsics* K,
-                               const float* d_T_world, void* stream)
+// Shared by the integrate, remove and move entry points (`who` names the one
+// reporting): the checks, the launch shape and the launch of one kernel over
+// n_frames frames.  kAdd runs k_map_integrate; kRemoveLeg / kAddLeg run
+// k_map_update, which also takes the other pose array of a move (or NULL).
+enum MapLeg { kAdd, kRemoveLeg, kAddLeg };
+
+static int map_launch(youth_map* m, const char* who, MapLeg leg, const int16_t* d_depth,
+                      const uint8_t* d_rgb, int n_frames, int W, int H, const youth_intrinsics* K,
+                      const float* d_T_world, const float* d_T_other, void* stream)
 {
-    if (!m || !d_depth) return g_map_err.set(YOUTH_EINVAL, "youth_map_integrate_device: null argument");
+    if (!m || !d_depth) return g_map_err.set(YOUTH_EINVAL, "%s: null argument", who);
     if (n_frames < 0 || n_frames > youth::kMaxFrames || !youth::frame_size_ok(W, H, 1))
         return g_map_err.set(YOUTH_EINVAL,
-                             "youth_map_integrate_device: %d frames of %dx%d (need 0 <= frames <= 65535, "
+                             "%s: %d frames of %dx%d (need 0 <= frames <= 65535, "
                              "1 <= W,H <= 16384, W*H <= 2^26)",
-                             n_frames, W, H);
+                             who, n_frames, W, H);
     if (n_frames == 0) return YOUTH_OK;
     HIP_TRY(hipSetDevice(m->device));
     const int N = W * H;
@@ -481,31 +526,48 @@ int youth_map_integrate_device(youth_map* m, const int16_t* d_depth, const uint8
     // depth word and the 8-byte colour words (as k_cloud_emit)
     const bool vec = (N % kMapPx) == 0 && ((uintptr_t)d_depth % 16) == 0 &&
                      (!d_rgb || ((uintptr_t)d_rgb % 8) == 0);
-    using Fn = void (*)(const int16_t*, const uint8_t*, int, int, CloudK, const float*, float, int,
-                        MapTable);
-    static const Fn fn[2][2][2] = {
-        {{k_map_integrate<false, false, false>, k_map_integrate<false, false, true>},
-         {k_map_integrate<false, true, false>, k_map_integrate<false, true, true>}},
-        {{k_map_integrate<true, false, false>, k_map_integrate<true, false, true>},
-         {k_map_integrate<true, true, false>, k_map_integrate<true, true, true>}}};
-    hipLaunchKernelGGL(fn[vec][m->lds][d_rgb != nullptr], dim3(tiles, n_frames), dim3(kMapThreads),
-                       0, s, d_depth, d_rgb, W, N, k, d_T_world, m->vpm, m->max_depth, m->t);
+    const dim3 grid(tiles, n_frames), block(kMapThreads);
+    if (leg == kAdd) {
+        using Fn = void (*)(const int16_t*, const uint8_t*, int, int, CloudK, const float*, float, int,
+                            MapTable);
+        static const Fn fn[2][2][2] = {
+            {{k_map_integrate<false, false, false>, k_map_integrate<false, false, true>},
+             {k_map_integrate<false, true, false>, k_map_integrate<false, true, true>}},
+            {{k_map_integrate<true, false, false>, k_map_integrate<true, false, true>},
+             {k_map_integrate<true, true, false>, k_map_integrate<true, true, true>}}};
+        hipLaunchKernelGGL(fn[vec][m->lds][d_rgb != nullptr], grid, block, 0, s, d_depth, d_rgb, W, N,
+                           k, d_T_world, m->vpm, m->max_depth, m->t);
+    } else {
+        using Fn = void (*)(const int16_t*, const uint8_t*, int, int, CloudK, const float*,
+                            const float*, float, int, MapTable);
+#define YOUTH_MAP_UPDATE_FNS(R)                                                                  \
+    {{{k_map_update<false, false, false, R>, k_map_update<false, false, true, R>},               \
+      {k_map_update<false, true, false, R>, k_map_update<false, true, true, R>}},                \
+     {{k_map_update<true, false, false, R>, k_map_update<true, false, true, R>},                 \
+      {k_map_update<true, true, false, R>, k_map_update<true, true, true, R>}}}
+        static const Fn fn[2][2][2][2] = {YOUTH_MAP_UPDATE_FNS(false), YOUTH_MAP_UPDATE_FNS(true)};
+#undef YOUTH_MAP_UPDATE_FNS
+        hipLaunchKernelGGL(fn[leg == kRemoveLeg][vec][m->lds][d_rgb != nullptr], grid, block, 0, s,
+                           d_depth, d_rgb, W, N, k, d_T_world, d_T_other, m->vpm, m->max_depth, m->t);
+    }
     HIP_TRY(hipGetLastError());
     return YOUTH_OK;
 }
 
-int youth_map_integrate_host(youth_map* m, const int16_t* depth, const uint8_t* rgb, int W, int H,
-                             const youth_intrinsics* K, const double* T_world)
+// One host frame in (kAdd) or out (kRemoveLeg) through the staging buffers.
+static int map_host_frame(youth_map* m, const char* who, MapLeg leg, const int16_t* depth,
+                          const uint8_t* rgb, int W, int H, const youth_intrinsics* K,
+                          const double* T_world)
 {
-    if (!m || !depth) return g_map_err.set(YOUTH_EINVAL, "youth_map_integrate_host: null argument");
+    if (!m || !depth) return g_map_err.set(YOUTH_EINVAL, "%s: null argument", who);
     if (!youth::frame_size_ok(W, H, 1))
-        return g_map_err.set(YOUTH_EINVAL, "youth_map_integrate_host: %dx%d frame", W, H);
+        return g_map_err.set(YOUTH_EINVAL, "%s: %dx%d frame", who, W, H);
     float T32[12];
     if (T_world) {
         for (int q = 0; q < 12; ++q) {
             T32[q] = (float)T_world[q];
             if (!std::isfinite(T_world[q]) || !std::isfinite(T32[q]))
-                return g_map_err.set(YOUTH_EINVAL, "youth_map_integrate_host: pose entry %d is not finite", q);
+                return g_map_err.set(YOUTH_EINVAL, "%s: pose entry %d is not finite", who, q);
         }
     }
     HIP_TRY(hipSetDevice(m->device));
@@ -516,11 +578,119 @@ int youth_map_integrate_host(youth_map* m, const int16_t* depth, const uint8_t* 
     if (rgb) HIP_TRY(hipMemcpyAsync(m->d_rgb, rgb, N * 3, hipMemcpyHostToDevice, m->stream));
     if (T_world)
         HIP_TRY(hipMemcpyAsync(m->d_T, T32, sizeof(T32), hipMemcpyHostToDevice, m->stream));
-    const int rc = youth_map_integrate_device(m, m->d_depth, rgb ? m->d_rgb : nullptr, 1, W, H, K,
-                                              T_world ? m->d_T : nullptr, m->stream);
+    const int rc = map_launch(m, who, leg, m->d_depth, rgb ? m->d_rgb : nullptr, 1, W, H, K,
+                              T_world ? m->d_T : nullptr, nullptr, m->stream);
     if (rc < 0) return rc;
     // the staging buffers and the caller's frame are free again on return
     HIP_TRY(hipStreamSynchronize(m->stream));
+    return YOUTH_OK;
+}
+
+int youth_map_integrate_device(youth_map* m, const int16_t* d_depth, const uint8_t* d_rgb,
+                               int n_frames, int W, int H, const youth_intrinsics* K,
+                               const float* d_T_world, void* stream)
+{
+    return map_launch(m, "youth_map_integrate_device", kAdd, d_depth, d_rgb, n_frames, W, H, K,
+                      d_T_world, nullptr, stream);
+}
+
+int youth_map_integrate_host(youth_map* m, const int16_t* depth, const uint8_t* rgb, int W, int H,
+                             const youth_intrinsics* K, const double* T_world)
+{
+    return map_host_frame(m, "youth_map_integrate_host", kAdd, depth, rgb, W, H, K, T_world);
+}
+
+int youth_map_remove_device(youth_map* m, const int16_t* d_depth, const uint8_t* d_rgb, int n_frames,
+                            int W, int H, const youth_intrinsics* K, const float* d_T_world,
+                            void* stream)
+{
+    return map_launch(m, "youth_map_remove_device", kRemoveLeg, d_depth, d_rgb, n_frames, W, H, K,
+                      d_T_world, nullptr, stream);
+}
+
+int youth_map_remove_host(youth_map* m, const int16_t* depth, const uint8_t* rgb, int W, int H,
+                          const youth_intrinsics* K, const double* T_world)
+{
+    return map_host_frame(m, "youth_map_remove_host", kRemoveLeg, depth, rgb, W, H, K, T_world);
+}
+
+int youth_map_move_device(youth_map* m, const int16_t* d_depth, const uint8_t* d_rgb, int n_frames,
+                          int W, int H, const youth_intrinsics* K, const float* d_T_old,
+                          const float* d_T_new, void* stream)
+{
+    if (!d_T_old || !d_T_new)
+        return g_map_err.set(YOUTH_EINVAL, "youth_map_move_device: null argument");
+    // removal first: a voxel's count never passes through a value it did not
+    // have, so an underflow still means a frame that was not in the map
+    const int rc = map_launch(m, "youth_map_move_device", kRemoveLeg, d_depth, d_rgb, n_frames, W, H,
+                              K, d_T_old, d_T_new, stream);
+    if (rc < 0) return rc;
+    return map_launch(m, "youth_map_move_device", kAddLeg, d_depth, d_rgb, n_frames, W, H, K, d_T_new,
+                      d_T_old, stream);
+}
+
+int youth_map_compact(youth_map* m)
+{
+    if (!m) return g_map_err.set(YOUTH_EINVAL, "youth_map_compact: null map");
+    HIP_TRY(hipSetDevice(m->device));
+    unsigned long long* keys = nullptr;
+    uint32_t* vals = nullptr;
+    if (hipMalloc(&keys, (size_t)m->cap * sizeof(unsigned long long)) != hipSuccess ||
+        hipMalloc(&vals, (size_t)m->cap * kValWords * sizeof(uint32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(keys);
+        return g_map_err.set(YOUTH_ENOMEM, "youth_map_compact: device allocation failed (%lld slots)",
+                             m->cap);
+    }
+    auto fail = [&](int rc) {
+        (void)hipStreamSynchronize(m->stream);
+        (void)hipFree(keys);
+        (void)hipFree(vals);
+        return rc;
+    };
+    const unsigned blocks = (unsigned)((m->cap + kMapThreads - 1) / kMapThreads);
+    unsigned long long st[kStN];
+    if (hipMemsetAsync(keys, 0xff, (size_t)m->cap * sizeof(unsigned long long), m->stream) != hipSuccess ||
+        hipMemsetAsync(vals, 0, (size_t)m->cap * kValWords * sizeof(uint32_t), m->stream) != hipSuccess ||
+        hipMemsetAsync(m->t.stats + kStLive, 0, (kStN - kStLive) * sizeof(unsigned long long),
+                       m->stream) != hipSuccess)
+        return fail(youth::hip_failed(g_map_err, hipGetLastError(), __FILE_NAME__, __LINE__));
+    k_map_rehash<<<blocks, kMapThreads, 0, m->stream>>>(m->t, keys, vals);
+    if (hipGetLastError() != hipSuccess || map_read_stats(m, st) < 0)
+        return fail(g_map_err.set(YOUTH_EHIP, "youth_map_compact: the rehash did not run"));
+    if (st[kStRehashFail] != 0)   // all or nothing: the old table was only read
+        return fail(g_map_err.set(YOUTH_ENOMEM,
+                                  "youth_map_compact: %llu voxels found no slot within the probe "
+                                  "bound; the map is unchanged",
+                                  st[kStRehashFail]));
+    std::swap(m->t.keys, keys);
+    std::swap(m->t.vals, vals);
+    (void)hipFree(keys);
+    (void)hipFree(vals);
+    // occupied becomes live; nothing is vacant in the fresh table
+    HIP_TRY(hipMemcpyAsync(m->t.stats + kStOccupied, &st[kStLive], sizeof(unsigned long long),
+                           hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    return YOUTH_OK;
+}
+
+int youth_map_remove_stats(youth_map* m, struct youth_map_remove_stats* out)
+{
+    if (!m || !out) return g_map_err.set(YOUTH_EINVAL, "youth_map_remove_stats: null argument");
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipMemsetAsync(m->t.stats + kStLive, 0, 3 * sizeof(unsigned long long), m->stream));
+    const unsigned blocks = (unsigned)((m->cap + kMapThreads - 1) / kMapThreads);
+    k_map_scan<<<blocks, kMapThreads, 0, m->stream>>>(m->t);
+    HIP_TRY(hipGetLastError());
+    unsigned long long st[kStN];
+    const int rc = map_read_stats(m, st);
+    if (rc < 0) return rc;
+    out->removed = st[kStRemoved];
+    out->missing = st[kStMissing];
+    out->underflow = st[kStUnderflow];
+    out->live = st[kStLive];
+    out->vacant = st[kStVacant];
+    out->stale = st[kStStale];
     return YOUTH_OK;
 }
 
@@ -554,7 +724,7 @@ int youth_map_extract(youth_map* m, youth_voxel* out, int cap)
     unsigned long long st[kStN];
     int rc = map_read_stats(m, st);
     if (rc < 0) return rc;
-    const size_t n = (size_t)st[kStOccupied];
+    size_t n = (size_t)st[kStOccupied];
     if (n > (size_t)cap)
         return g_map_err.set(YOUTH_EINVAL, "youth_map_extract: %zu voxels, room for %d", n, cap);
     if (n == 0) return 0;
@@ -564,6 +734,15 @@ int youth_map_extract(youth_map* m, youth_voxel* out, int cap)
     const unsigned blocks = (unsigned)((m->cap + kMapThreads - 1) / kMapThreads);
     k_map_extract<<<blocks, kMapThreads, 0, m->stream>>>(m->t, m->d_rec, (uint32_t)n);
     HIP_TRY(hipGetLastError());
+    // n bounds the records; their exact number (slots vacated by a removal hold
+    // none) is what the kernel counted
+    unsigned long long live = 0;
+    HIP_TRY(hipMemcpyAsync(&live, m->t.stats + kStExtracted, sizeof(live), hipMemcpyDeviceToHost,
+                           m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    if (live > n) return g_map_err.set(YOUTH_EHIP, "youth_map_extract: %llu records of %zu slots", live, n);
+    n = (size_t)live;
+    if (n == 0) return 0;
     HIP_TRY(hipMemcpyAsync(out, m->d_rec, n * sizeof(youth_voxel), hipMemcpyDeviceToHost, m->stream));
     HIP_TRY(hipStreamSynchronize(m->stream));
     // the slot order depends on which wave won an insert: never leaves here

@@ -23,6 +23,7 @@ import youth_icp
 from youth_icp import YOUTH_EHIP, YOUTH_EINVAL, YOUTH_ENODEV, YOUTH_ENOMEM, IcpError, Intrinsics
 
 HEADER_PATH = os.path.join(os.path.dirname(youth_icp.HERE), "include", "youth_map.h")
+REMOVE_HEADER_PATH = os.path.join(os.path.dirname(youth_icp.HERE), "include", "youth_map_remove.h")
 
 # youth_voxel
 VOXEL_DTYPE = np.dtype([("ix", "<i4"), ("iy", "<i4"), ("iz", "<i4"), ("count", "<u4"),
@@ -34,6 +35,15 @@ class MapStats(ctypes.Structure):
     """struct youth_map_stats."""
     _fields_ = [("integrated", c_uint64), ("out_of_range", c_uint64), ("dropped", c_uint64),
                 ("occupied", c_uint64), ("direct", c_uint64), ("capacity", c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class MapRemoveStats(ctypes.Structure):
+    """struct youth_map_remove_stats."""
+    _fields_ = [("removed", c_uint64), ("missing", c_uint64), ("underflow", c_uint64),
+                ("live", c_uint64), ("vacant", c_uint64), ("stale", c_uint64)]
 
     def as_dict(self) -> dict:
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -55,6 +65,15 @@ _SIGS = {
                                            c_void_p, c_void_p]),
     "youth_map_integrate_host": (c_int, [c_void_p, POINTER(c_int16), POINTER(c_uint8), c_int,
                                          c_int, _PI, POINTER(c_double)]),
+    # youth_map_remove.h
+    "youth_map_remove_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, _PI,
+                                        c_void_p, c_void_p]),
+    "youth_map_remove_host": (c_int, [c_void_p, POINTER(c_int16), POINTER(c_uint8), c_int, c_int,
+                                      _PI, POINTER(c_double)]),
+    "youth_map_move_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, _PI,
+                                      c_void_p, c_void_p, c_void_p]),
+    "youth_map_compact": (c_int, [c_void_p]),
+    "youth_map_remove_stats": (c_int, [c_void_p, POINTER(MapRemoveStats)]),
     "youth_map_voxels": (c_longlong, [c_void_p]),
     "youth_map_extract": (c_int, [c_void_p, c_void_p, c_int]),
     "youth_map_stats": (c_int, [c_void_p, POINTER(MapStats)]),
@@ -64,6 +83,8 @@ _SIGS = {
     "youth_slam_map_voxels": (c_longlong, []),
     "youth_slam_map_extract": (c_int, [c_void_p, c_int]),
     "youth_slam_map_vpm": (c_float, []),
+    "youth_slam_map_reintegrate": (c_int, [c_int, POINTER(c_double)]),
+    "youth_slam_map_kept": (c_int, []),
     # youth_map_render.h
     "youth_map_view_from_pose": (c_int, [POINTER(c_double), POINTER(c_float)]),
     "youth_map_render_device": (c_int, [c_void_p, c_int, _PV, _PI, c_void_p, c_void_p, c_void_p,
@@ -126,6 +147,20 @@ def slam_map_extract() -> np.ndarray:
         if m == YOUTH_EINVAL and int(lib.youth_slam_map_voxels()) > n:
             continue   # the worker integrated a frame in between
         return out[:_check(lib, m)]
+
+
+def slam_map_kept() -> int:
+    """Frames in the SLAM module's frame store (YOUTH_SLAM_MAP_KEEP; 0 when off)."""
+    return int(load_library().youth_slam_map_kept())
+
+
+def slam_map_reintegrate(T_wc) -> int:
+    """youth_slam_map_reintegrate: the kept frames i < n moved to T_wc[i] (n poses,
+    4x4 fp64, e.g. youth_loop.slam_loop_trajectory); returns the number of frames
+    whose pose changed (0 when the map or the store is off)."""
+    lib = load_library()
+    T = np.ascontiguousarray(T_wc, np.float64).reshape(-1, 16)
+    return _check(lib, lib.youth_slam_map_reintegrate(T.shape[0], T.ctypes.data_as(POINTER(c_double))))
 
 
 def _pose16(T_world) -> np.ndarray:
@@ -205,6 +240,16 @@ class VoxelMap:
                   K: Intrinsics | None = None, T_world: np.ndarray | None = None) -> None:
         """One host frame with its camera -> world pose (4x4 or 3x4, fp64; None =
         identity); synchronous."""
+        self._host_frame(self._lib.youth_map_integrate_host, depth, rgb, K, T_world)
+
+    def remove(self, depth: np.ndarray, rgb: np.ndarray | None = None,
+               K: Intrinsics | None = None, T_world: np.ndarray | None = None) -> None:
+        """youth_map_remove_host: takes out a frame that went in with the same
+        arguments (exact iff they are bit-identical and nothing was dropped);
+        synchronous."""
+        self._host_frame(self._lib.youth_map_remove_host, depth, rgb, K, T_world)
+
+    def _host_frame(self, fn, depth, rgb, K, T_world) -> None:
         d = np.ascontiguousarray(depth, np.int16)
         H, W = d.shape
         c = None if rgb is None else np.ascontiguousarray(rgb, np.uint8).reshape(H, W, 3)
@@ -213,7 +258,7 @@ class VoxelMap:
             T = np.zeros(16, np.float64)
             T[:12] = np.asarray(T_world, np.float64).reshape(-1)[:12]
             T[15] = 1.0
-        _check(self._lib, self._lib.youth_map_integrate_host(
+        _check(self._lib, fn(
             self._map, d.ctypes.data_as(POINTER(c_int16)),
             None if c is None else c.ctypes.data_as(POINTER(c_uint8)), W, H,
             None if K is None else ctypes.byref(K),
@@ -228,6 +273,33 @@ class VoxelMap:
         _check(self._lib, self._lib.youth_map_integrate_device(
             self._map, d_depth or None, d_rgb or None, n_frames, W, H,
             None if K is None else ctypes.byref(K), d_T_world or None, stream or None))
+
+    def remove_device(self, d_depth: int, d_rgb: int, n_frames: int, W: int, H: int,
+                      d_T_world: int = 0, K: Intrinsics | None = None, stream: int = 0) -> None:
+        """youth_map_remove_device: as integrate_device, taking the frames out."""
+        _check(self._lib, self._lib.youth_map_remove_device(
+            self._map, d_depth or None, d_rgb or None, n_frames, W, H,
+            None if K is None else ctypes.byref(K), d_T_world or None, stream or None))
+
+    def move_device(self, d_depth: int, d_rgb: int, n_frames: int, W: int, H: int, d_T_old: int,
+                    d_T_new: int, K: Intrinsics | None = None, stream: int = 0) -> None:
+        """youth_map_move_device: the frames from the poses d_T_old to d_T_new (device
+        [n_frames][12] fp32 each); a frame with bitwise equal poses is skipped."""
+        _check(self._lib, self._lib.youth_map_move_device(
+            self._map, d_depth or None, d_rgb or None, n_frames, W, H,
+            None if K is None else ctypes.byref(K), d_T_old or None, d_T_new or None,
+            stream or None))
+
+    def compact(self) -> None:
+        """youth_map_compact: rebuild the table without the slots removal vacated."""
+        _check(self._lib, self._lib.youth_map_compact(self._map))
+
+    def remove_stats(self) -> dict:
+        """youth_map_remove_stats: removed / missing / underflow since the last clear,
+        live / vacant / stale from a scan of the table."""
+        st = MapRemoveStats()
+        _check(self._lib, self._lib.youth_map_remove_stats(self._map, ctypes.byref(st)))
+        return st.as_dict()
 
     def render(self, T_world=None, W: int = 640, H: int = 480, K: Intrinsics | None = None,
                max_splat: int = 0, min_count: int = 0, want_rgb: bool = True):

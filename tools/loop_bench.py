@@ -22,9 +22,18 @@ numbers, run by hand (not part of bench.py), at 640x480:
                 trajectory against T_wc at frames 627, 800 and 999 before and
                 after optimising and re-hanging; close time per keyframe
 
+  (4) c5map     (on request only) C5 tracked with colour as in (3), every frame
+                integrated into a voxel map at 100 voxels per metre with its
+                tracked pose, the frames kept on the device in chunks of 64 as
+                the drop-in keeps them; then moved to the corrected trajectory
+                (youth_map_move_device per chunk) and compacted.  Reported: the
+                Jaccard index of the map's voxel key set, before and after,
+                against the map integrated with the ground-truth poses, and the
+                time of the re-integration
+
 The last line is one JSON object.
-usage: python tools/loop_bench.py [kernels] [gates] [c5] [dump=DIR]   (default: all three;
-dump=DIR also writes every verified pair and every loop edge as JSON files into DIR)"""
+usage: python tools/loop_bench.py [kernels] [gates] [c5] [c5map] [dump=DIR]   (default: the
+first three; dump=DIR also writes every verified pair and every loop edge as JSON files into DIR)"""
 import json
 import os
 import sys
@@ -38,6 +47,7 @@ import numpy as np  # noqa: E402
 
 import youth_icp  # noqa: E402
 import youth_loop  # noqa: E402
+import youth_map  # noqa: E402
 import youth_rgbd  # noqa: E402
 import youth_synth  # noqa: E402
 
@@ -168,6 +178,46 @@ def rel_motion(A, B):
     return pose_error(B, A)   # (degrees, mm) of A^-1 B
 
 
+def track_rgbd(fr, rgb):
+    """The trajectory of the sequence tracked with colour, frame 0 the origin."""
+    n = len(fr)
+    traj = [np.eye(4)]
+    with youth_rgbd.RgbdContext(W, H, 100) as ctx:
+        for s in range(0, n - 1, 100):
+            T_rel, st = ctx.track_host_sequence(fr[s:s + 101], rgb[s:s + 101])
+            T_rel[:, 3, :] = (0.0, 0.0, 0.0, 1.0)
+            for T in T_rel:
+                traj.append(traj[-1] @ T)
+    return np.array(traj)
+
+
+def close_trajectory(fr, rgb, T):
+    """Keyframes as the drop-in picks them, stored and closed in order, the pose
+    graph optimised and the trajectory re-hung: (keyframes, loop edges, close ms
+    per keyframe, optimise ms, cost before and after, corrected trajectory)."""
+    n = len(fr)
+    kf = [0]
+    for f in range(1, n):
+        deg, mm = rel_motion(T[kf[-1]], T[f])
+        if mm > 100.0 or deg > 10.0:
+            kf.append(f)
+    kf = kf[:youth_loop.MAX_KEYFRAMES]
+    t_close = []
+    with youth_loop.LoopCloser(W, H, max(2, len(kf))) as lc:
+        for i, f in enumerate(kf):
+            lc.add_keyframe(fr[f], rgb[f], T[f], tag=f)
+            t0 = time.perf_counter()
+            lc.close(i)
+            t_close.append((time.perf_counter() - t0) * 1e3)
+        loops = lc.edges()
+    odo = [(i - 1, i, np.linalg.inv(T[kf[i - 1]]) @ T[kf[i]], 1.0) for i in range(1, len(kf))]
+    edges = np.concatenate([youth_loop.make_edges(odo), loops])
+    t0 = time.perf_counter()
+    Xo, c0, c1 = youth_loop.optimize_pose_graph(T[kf], edges)
+    t_opt = (time.perf_counter() - t0) * 1e3
+    return kf, loops, t_close, t_opt, (c0, c1), youth_loop.interpolate(T, kf, T[kf], Xo)
+
+
 def c5(n=1000):
     fr, X, rgb = youth_synth.sequence_rgb(0, n, W, H)
     gt = np.array([np.linalg.inv(X[0]) @ X[k] for k in range(n)])
@@ -180,37 +230,11 @@ def c5(n=1000):
     for k in range(n - 1):
         traj.append(traj[-1] @ T_rel[k])
     trajs["depth"] = np.array(traj)
-    traj = [np.eye(4)]
-    with youth_rgbd.RgbdContext(W, H, 100) as ctx:
-        for s in range(0, n - 1, 100):
-            T_rel, st = ctx.track_host_sequence(fr[s:s + 101], rgb[s:s + 101])
-            T_rel[:, 3, :] = (0.0, 0.0, 0.0, 1.0)
-            for T in T_rel:
-                traj.append(traj[-1] @ T)
-    trajs["rgbd"] = np.array(traj)
+    trajs["rgbd"] = track_rgbd(fr, rgb)
     out = {}
     for name, T in trajs.items():
-        kf = [0]
-        for f in range(1, n):
-            deg, mm = rel_motion(T[kf[-1]], T[f])
-            if mm > 100.0 or deg > 10.0:
-                kf.append(f)
-        kf = kf[:youth_loop.MAX_KEYFRAMES]
-        t_close = []
-        with youth_loop.LoopCloser(W, H, max(2, len(kf))) as lc:
-            for i, f in enumerate(kf):
-                lc.add_keyframe(fr[f], rgb[f], T[f], tag=f)
-                t0 = time.perf_counter()
-                lc.close(i)
-                t_close.append((time.perf_counter() - t0) * 1e3)
-            loops = lc.edges()
-        odo = [(i - 1, i, np.linalg.inv(T[kf[i - 1]]) @ T[kf[i]], 1.0) for i in range(1, len(kf))]
-        edges = np.concatenate([youth_loop.make_edges(odo), loops])
+        kf, loops, t_close, t_opt, (c0, c1), closed = close_trajectory(fr, rgb, T)
         edge_err = [pose_error(e["Z"], np.linalg.inv(gt[kf[e["i"]]]) @ gt[kf[e["j"]]]) for e in loops]
-        t0 = time.perf_counter()
-        Xo, c0, c1 = youth_loop.optimize_pose_graph(T[kf], edges)
-        t_opt = (time.perf_counter() - t0) * 1e3
-        closed = youth_loop.interpolate(T, kf, T[kf], Xo)
         res = {"keyframes": len(kf), "loop_edges": int(loops.shape[0]),
                "loop_edge_error_max_deg_mm": [round(max(e[0] for e in edge_err), 4),
                                               round(max(e[1] for e in edge_err), 3)] if edge_err else None,
@@ -233,6 +257,72 @@ def c5(n=1000):
     return out
 
 
+# ---------------------------------------------------------------------- C5 map --
+MAP_VPM, MAP_SLOTS, MAP_CHUNK = 100.0, 1 << 25, 64
+
+
+def c5map(n=1000):
+    fr, X, rgb = youth_synth.sequence_rgb(0, n, W, H)
+    gt = np.array([np.linalg.inv(X[0]) @ X[k] for k in range(n)])
+    T = track_rgbd(fr, rgb)
+    kf, loops, _, _, _, closed = close_trajectory(fr, rgb, T)
+    # the frames on the device in chunks of 64, as the drop-in's store keeps them
+    chunks = []
+    for c0 in range(0, n, MAP_CHUNK):
+        c1 = min(n, c0 + MAP_CHUNK)
+        chunks.append((c0, c1, torch.from_numpy(np.stack(fr[c0:c1])).cuda(),
+                       torch.from_numpy(np.stack(rgb[c0:c1])).cuda()))
+
+    def poses(P):
+        return [torch.from_numpy(np.ascontiguousarray(P[c0:c1].reshape(-1, 16)[:, :12], np.float32)).cuda()
+                for c0, c1, _, _ in chunks]
+
+    def keys(rec):
+        return ((rec["iz"].astype(np.int64) + (1 << 20)) << 42) | \
+               ((rec["iy"].astype(np.int64) + (1 << 20)) << 21) | (rec["ix"].astype(np.int64) + (1 << 20))
+
+    def jaccard(a, b):
+        both = np.intersect1d(a, b, assume_unique=True).shape[0]
+        return both / max(1, a.shape[0] + b.shape[0] - both)
+
+    P_gt, P_live, P_closed = poses(gt), poses(T), poses(closed)
+    torch.cuda.synchronize()
+    with youth_map.VoxelMap(MAP_VPM, MAP_SLOTS) as m:
+        for (c0, c1, d, c), P in zip(chunks, P_gt):
+            m.integrate_device(d.data_ptr(), c.data_ptr(), c1 - c0, W, H, P.data_ptr())
+        k_gt = keys(m.extract())
+        dropped = m.stats()["dropped"]
+        m.clear()
+        for (c0, c1, d, c), P in zip(chunks, P_live):
+            m.integrate_device(d.data_ptr(), c.data_ptr(), c1 - c0, W, H, P.data_ptr())
+        k_live = keys(m.extract())
+        m.sync()
+        t0 = time.perf_counter()
+        for (c0, c1, d, c), P0, P1 in zip(chunks, P_live, P_closed):
+            m.move_device(d.data_ptr(), c.data_ptr(), c1 - c0, W, H, P0.data_ptr(), P1.data_ptr())
+        m.sync()
+        t_move = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        m.compact()
+        t_compact = (time.perf_counter() - t0) * 1e3
+        k_closed = keys(m.extract())
+        st, rs = m.stats(), m.remove_stats()
+    moved = int(sum(not np.array_equal(a.reshape(-1)[:12].astype(np.float32),
+                                       b.reshape(-1)[:12].astype(np.float32)) for a, b in zip(T, closed)))
+    res = {"frames": n, "vpm": MAP_VPM, "slots": MAP_SLOTS, "keyframes": len(kf),
+           "loop_edges": int(loops.shape[0]), "frames_moved": moved,
+           "voxels_gt": int(k_gt.shape[0]), "voxels_before": int(k_live.shape[0]),
+           "voxels_after": int(k_closed.shape[0]),
+           "jaccard_before": round(jaccard(k_live, k_gt), 4),
+           "jaccard_after": round(jaccard(k_closed, k_gt), 4),
+           "reintegrate_ms": round(t_move, 2), "reintegrate_us_per_moved_frame": round(t_move * 1e3 / max(1, moved), 1),
+           "compact_ms": round(t_compact, 2),
+           "dropped": int(dropped + st["dropped"]), "missing": rs["missing"], "underflow": rs["underflow"],
+           "stale": rs["stale"]}
+    print(f"C5 map, rgbd tracking: {res}", flush=True)
+    return res
+
+
 DUMP = None   # dump=DIR: every verified pair and every loop edge as JSON files there
 
 
@@ -252,6 +342,8 @@ def main():
                         "survey_noise": gate_table(youth_synth.SURVEY_FLAGS, "SURVEY_FLAGS")}
     if "c5" in parts:
         res["c5"] = c5()
+    if "c5map" in parts:
+        res["c5map"] = c5map()
     print(json.dumps(res))
     return 0
 
