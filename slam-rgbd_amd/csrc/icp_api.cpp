@@ -269,8 +269,8 @@ youth_icp_ctx* youth_icp_create(int device, int W, int H, int max_frames,
         c->ident_first = ident_first_ok(Kd) && !(nif && *nif && *nif != '0');
         const char* ifm = getenv("YOUTH_ICP_IDENT_FIRST");  // "icp": not inside the prep pass
         c->ident_prep = !(ifm && strcmp(ifm, "icp") == 0);
-        const char* pst = getenv("YOUTH_ICP_PREP_STRIP");   // tuning knob
-        if (pst && atoi(pst) >= 1) c->prep_strip = atoi(pst);
+        const char* pbd = getenv("YOUTH_ICP_PREP_BAND");    // tuning knob
+        if (pbd && atoi(pbd) >= 1) c->prep_band = atoi(pbd);
         const char* cth = getenv("YOUTH_ICP_COOP_THREADS");
         if (cth && atoi(cth) == 256) c->coop_threads = 256;
         const char* nc = getenv("YOUTH_ICP_NO_COOP");

@@ -55,6 +55,9 @@ constexpr int kPrepThreads = 512;
 #endif
 constexpr int kPrepTW = YOUTH_PREP_TW;
 constexpr int kPrepTH = YOUTH_PREP_TH;
+// k_prep_ident: one wave per unit of 64 columns (one per lane) x a band of rows
+constexpr int kPrepColW = 64;
+constexpr int kPrepBand = 96;  // rows per unit at large batches (launch_prep_ident)
 constexpr int kLdsW = kTileW + 2;
 
 constexpr int kRedThreads = 256;
@@ -281,6 +284,59 @@ __device__ __forceinline__ void backproject_c(int d, float uc, float vc, const I
     x = bp_div<kFast>(uc * zz, K.fx, F.hfx, F.lfx);
     y = bp_div<kFast>(vc * zz, K.fy, F.hfy, F.lfy);
     z = zz;
+}
+
+// One pixel's target record {z, nx, ny, nz} (spec a6) from its back-projected
+// point (px, py, pz) and its four neighbours' points: left (u - 1), right
+// (u + 1), up (v - 1), down (v + 1); inner: the pixel is off the 1-px border.
+// The one text for prep_tile (points read from its LDS planes) and
+// k_prep_ident (points in registers), so their records are the same bits.
+// Branch-free but for the rare fallback: every lane forms the normal (a caller
+// has a point for every neighbour, 0 outside the image) and the record is
+// selected at the end.  Every z is >= +0 (back-projection of max(d, 0), 0
+// outside the image), so the five z > 0 tests are one test of their minimum,
+// taken on the bits (the same order for non-negative floats; +0 is bits 0).
+__device__ __forceinline__ float4 prep_record(float px, float py, float pz, float lx, float ly,
+                                              float lz, float rx, float ry, float rz, float ux,
+                                              float uy, float uz, float dx, float dy, float dz,
+                                              bool inner)
+{
+    const unsigned zmin = min(min(min(__float_as_uint(pz), __float_as_uint(lz)),
+                                  min(__float_as_uint(rz), __float_as_uint(uz))),
+                              __float_as_uint(dz));
+    const float ax = rx - lx;
+    const float ay = ry - ly;
+    const float az = rz - lz;
+    const float bx = dx - ux;
+    const float by = dy - uy;
+    const float bz = dz - uz;
+    const float cx = ay * bz - az * by;
+    const float cy = az * bx - ax * bz;
+    const float cz = ax * by - ay * bx;
+    const float len2 = (cx * cx + cy * cy) + cz * cz;
+    const bool has_n = inner & (zmin != 0u) & (len2 > 0.0f);
+    const float len = sqrt_rn_mid(len2);
+    const float r = proj_recip(len);
+    float nx = norm_div(cx, len, r);
+    float ny = norm_div(cy, len, r);
+    float nz = norm_div(cz, len, r);
+    if (__builtin_expect(has_n & !norm_fast_ok_bits(len2, cx, cy, cz), 0)) {
+        const float l = sqrtf(len2);  // correctly rounded (checked in .s)
+        nx = cx / l;
+        ny = cy / l;
+        nz = cz / l;
+    }
+    // oriented so n.P <= 0
+    if (((nx * px + ny * py) + nz * pz) > 0.0f) {
+        nx = -nx;
+        ny = -ny;
+        nz = -nz;
+    }
+    if (!has_n) nx = ny = nz = 0.0f;
+    // a target without a normal is stored as z = 0 ("invalid target"): the
+    // spec's two tests "target valid" and "normal valid" become the one
+    // tz > 0 test in the pixel loop (a stored Z plane keeps pz)
+    return make_float4(has_n ? pz : 0.0f, nx, ny, nz);
 }
 
 // ------------------------------------------------------------ solve (a10) --

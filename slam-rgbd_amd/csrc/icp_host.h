@@ -89,7 +89,7 @@ struct youth_icp_ctx {
     // targets, unless YOUTH_ICP_IDENT_FIRST=icp keeps it in k_icp.
     bool ident_first = true;
     bool ident_prep = true;
-    int prep_strip = 0;              // tiles per k_prep_ident workgroup (YOUTH_ICP_PREP_STRIP; 0: by batch size)
+    int prep_band = 0;               // rows per k_prep_ident unit (YOUTH_ICP_PREP_BAND; 0: by batch size)
     int last_first_form = 0;         // the last align's (youth_icp_get_first_iter)
     int reduce = YOUTH_REDUCE_EXACT; // spec a9 (youth_icp_set_reduce, YOUTH_ICP_REDUCE)
     youth_lanes lanes{};             // lane partition of the last align's iterations

@@ -263,16 +263,11 @@ __global__ void k_selftest_normalize(unsigned long long n, unsigned long long se
 // buffer stores) for an in-launch hand-off (k_icp_coop).  Contains a
 // workgroup barrier (every thread must call it); a caller reusing the LDS
 // planes for another tile adds one more before it.
-// prep_tile_with: per_record(k, px, py, pz, rec) runs for every pixel of the
-// frame right after its record is stored: k the step of the record loop
-// (pixel (x0 + tx, y0 + ty + (kThreads / kTW) k)), (px, py, pz) its point from
-// the planes, rec its record.  prep_tile passes nothing.
-template <bool kFast, bool kWide, bool kSc1, int kThreads, int kTH, int kTW = kTileW, typename Fn>
-__device__ __forceinline__ void prep_tile_with(const int16_t* __restrict__ dep,
-                                               float4* __restrict__ R, int W, int H, size_t P,
-                                               const Intr& K, const FastK& F,
-                                               float* __restrict__ X, int x0, int y0, float* sX,
-                                               float* sY, float* sZ, Fn&& per_record)
+template <bool kFast, bool kWide, bool kSc1, int kThreads, int kTH, int kTW = kTileW>
+__device__ __forceinline__ void prep_tile(const int16_t* __restrict__ dep, float4* __restrict__ R,
+                                          int W, int H, size_t P, const Intr& K, const FastK& F,
+                                          float* __restrict__ X, int x0, int y0, float* sX,
+                                          float* sY, float* sZ)
 {
     constexpr int kLH = kTH + 2;
     constexpr int kLW = kTW + 2;
@@ -398,51 +393,16 @@ __device__ __forceinline__ void prep_tile_with(const int16_t* __restrict__ dep,
             X[P + i] = py;
             X[2 * P + i] = pz;
         }
-        // branch-free: every lane forms the normal from its LDS neighbours
-        // (the halo exists for every pixel of the tile) and the record is
-        // selected at the end.  Every z is >= +0 (back-projection of
-        // max(d, 0), 0 outside the image), so the five z > 0 tests are one
-        // test of their minimum, taken on the bits (the same order for
-        // non-negative floats; +0 is bits 0)
+        // every lane forms the record from its LDS neighbours (the halo
+        // exists for every pixel of the tile): prep_record, icp_device.h
         const bool inner = (gx > 0) & (gy > 0) & (gx < W - 1) & (gy < H - 1);
         const float zl = sZ[o - 1], zr = sZ[o + 1];
         const float zu = sZ[o - kLW], zd = sZ[o + kLW];
-        const unsigned zmin = min(min(min(__float_as_uint(pz), __float_as_uint(zl)),
-                                      min(__float_as_uint(zr), __float_as_uint(zu))),
-                                  __float_as_uint(zd));
-        const float ax = sX[o + 1] - sX[o - 1];
-        const float ay = sY[o + 1] - sY[o - 1];
-        const float az = zr - zl;
-        const float bx = sX[o + kLW] - sX[o - kLW];
-        const float by = sY[o + kLW] - sY[o - kLW];
-        const float bz = zd - zu;
-        const float cx = ay * bz - az * by;
-        const float cy = az * bx - ax * bz;
-        const float cz = ax * by - ay * bx;
-        const float len2 = (cx * cx + cy * cy) + cz * cz;
-        const bool has_n = inner & (zmin != 0u) & (len2 > 0.0f);
-        const float len = sqrt_rn_mid(len2);
-        const float r = proj_recip(len);
-        float nx = norm_div(cx, len, r);
-        float ny = norm_div(cy, len, r);
-        float nz = norm_div(cz, len, r);
-        if (__builtin_expect(has_n & !norm_fast_ok_bits(len2, cx, cy, cz), 0)) {
-            const float l = sqrtf(len2);  // correctly rounded (checked in .s)
-            nx = cx / l;
-            ny = cy / l;
-            nz = cz / l;
-        }
-        // oriented so n.P <= 0
-        if (((nx * px + ny * py) + nz * pz) > 0.0f) {
-            nx = -nx;
-            ny = -ny;
-            nz = -nz;
-        }
-        if (!has_n) nx = ny = nz = 0.0f;
-        // a target without a normal is stored as z = 0 ("invalid target"):
-        // the spec's two tests "target valid" and "normal valid" become the
-        // one tz > 0 test in the pixel loop (the Z plane keeps pz)
-        const float4 rec = make_float4(has_n ? pz : 0.0f, nx, ny, nz);
+        const float xr = sX[o + 1], xl = sX[o - 1];
+        const float yr = sY[o + 1], yl = sY[o - 1];
+        const float xd = sX[o + kLW], xu = sX[o - kLW];
+        const float yd = sY[o + kLW], yu = sY[o - kLW];
+        const float4 rec = prep_record(px, py, pz, xl, yl, zl, xr, yr, zr, xu, yu, zu, xd, yd, zd, inner);
         if (kSc1) {
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, rec), rrec,
                                                    (int)(i * sizeof(float4)), 0, 16);
@@ -455,19 +415,7 @@ __device__ __forceinline__ void prep_tile_with(const int16_t* __restrict__ dep,
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, rec), rrec,
                                                    (int)(i * sizeof(float4)), 0, 2);
         }
-        per_record(k, px, py, pz, rec);
     }
-}
-
-template <bool kFast, bool kWide, bool kSc1, int kThreads, int kTH, int kTW = kTileW>
-__device__ __forceinline__ void prep_tile(const int16_t* __restrict__ dep, float4* __restrict__ R,
-                                          int W, int H, size_t P, const Intr& K, const FastK& F,
-                                          float* __restrict__ X, int x0, int y0, float* sX,
-                                          float* sY, float* sZ)
-{
-    prep_tile_with<kFast, kWide, kSc1, kThreads, kTH, kTW>(
-        dep, R, W, H, P, K, F, X, x0, y0, sX, sY, sZ,
-        [](int, float, float, float, const float4&) __attribute__((always_inline)) {});
 }
 
 // The persistent path's per-call state, set by k_prep's tile-(0,0) blocks
@@ -1276,11 +1224,24 @@ __global__ __launch_bounds__(kRedThreads, 4) void k_icp(const int16_t* __restric
 // bound by its 16 B/px store stream also loads the pair's source depth at
 // the pixel (2 B/px) and runs the gate, r, J and the 29 sums on its idle VALU,
 // and k_icp runs iterations 1 .. iters - 1 only.
-//   * A workgroup walks a STRIP of `strip` consecutive tiles of one frame
-//     (prep_tile_with, one more barrier per further tile) with its fp64 sums
-//     in registers, then reduces once: wave_reduce_scatter, the eight waves
-//     through LDS (the planes, after a barrier), one partial row published and
-//     one ticket on arrivals[p] (handoff_publish).
+//   * A UNIT is one wave (a 64-thread workgroup) on 64 adjacent columns and a
+//     band of `band` consecutive rows of one frame, lane l on column x0 + l:
+//     no LDS planes and no barrier.  The wave walks down its columns with the
+//     points of rows y - 1, y, y + 1 in registers (the vertical neighbours) and
+//     takes the horizontal neighbours' points from lanes l - 1 and l + 1 by
+//     whole-wave DPP shifts; lanes 0 and 63 take columns x0 - 1 and x0 + 64
+//     from one more 2-byte load per row.  prep_record (icp_device.h) forms the
+//     record, as in prep_tile.  Rows y0 - 1 and y0 + band are the band's halo:
+//     loaded like any row, no record stored.
+//   * Memory order: every iteration requests the depth words of the row two
+//     ahead BEFORE it stores its record, so the wait for a row's words is a
+//     counted one that leaves the younger loads and every record store in
+//     flight; the loop never drains the memory counter (checked in the .s).
+//     Each wave is an independent stream of loads and stores, 16 per CU.
+//   * Units are ordered frame-major, then by band, then by column block:
+//     waves that run together write adjacent 1-KB row segments.  At its end a
+//     unit reduces once (wave_reduce_scatter), publishes one partial row and
+//     takes one ticket on arrivals[p] (handoff_publish).
 //   * The pair's last arriver adds the rows in fixed order (handoff_sum),
 //     solves from the identity pose and writes everything k_init would have
 //     written and iteration 0 would have left: T64 / T32, status,
@@ -1294,7 +1255,7 @@ struct IdentArgs {
     PairMap pm;           // pair p: source frame src0 + p, target record frame tgt0 + p
     int n_pairs, iters;
     float thr2;
-    double* partials;     // [pair][strips][kPartStride]
+    double* partials;     // [pair][units per frame][kPartStride]
     double* T64;          // [pair][16]
     float* T32;           // [pair][12]
     int32_t* status;      // [pair]
@@ -1306,106 +1267,166 @@ struct IdentArgs {
     unsigned* head_err;   // queue words, zeroed by workgroup 0
 };
 
-template <int kSp, bool kFast, bool kWide>
-__global__ __launch_bounds__(kPrepThreads) void k_prep_ident(const int16_t* __restrict__ depth,
-                                                            int out0, int W, int H, size_t P,
-                                                            Intr K, FastK F,
-                                                            float4* __restrict__ recs, IdentArgs ia,
-                                                            int tiles_x, int tiles_y, int strip)
+// Lane l takes v of lane l - 1 (from_left: wave_shr:1) or l + 1 (from_right:
+// wave_shl:1); the lane without that neighbour (0, 63) keeps `edge`.  Every
+// lane of the wave must be active: a disabled source lane leaves `edge` too.
+__device__ __forceinline__ float from_left(float v, float edge)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v),
+                                                      0x138, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float from_right(float v, float edge)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v),
+                                                      0x130, 0xf, 0xf, false));
+}
+
+// What a unit loads for the iteration of row y, two iterations ahead of it.
+// The words as loaded (int16 bits, one register each): converted where they
+// are used, so nothing touches a word between its request and its use.
+struct PrepRowIn {
+    unsigned t;  // target depth at (x, y + 1): the row that enters the window
+    unsigned e;  // lanes 0 / 63: target depth at (x0 - 1, y) / (x0 + 64, y)
+    unsigned s;  // source depth at (x, y)
+};
+
+template <int kSp, bool kFast>
+__global__ __launch_bounds__(kPrepColW) void k_prep_ident(const int16_t* depth, int out0, int W,
+                                                         int H, size_t P, Intr K, FastK F,
+                                                         float4* recs, IdentArgs ia, int blocks_x,
+                                                         int bands, int band)
 {
     static_assert(!sp_lane32(kSp), "exact sums only");
-    constexpr int kRows = kPrepThreads / kPrepTW;  // rows of a tile per record-loop step
-    constexpr int kSteps = kPrepTH / kRows;
-    constexpr int kWaves = kPrepThreads / 64;
-    __shared__ float sX[(kPrepTH + 2) * (kPrepTW + 2)];
-    __shared__ float sY[(kPrepTH + 2) * (kPrepTW + 2)];
-    __shared__ float sZ[(kPrepTH + 2) * (kPrepTW + 2)];
-    static_assert(sizeof(sX) >= kWaves * kNeq * sizeof(double), "the waves' sums fit a plane");
-    static_assert(sizeof(sY) >= (32 + 16) * sizeof(double) + 12 * sizeof(float), "solve scratch");
-    const int per = tiles_x * tiles_y;
-    const int strips = (per + strip - 1) / strip;
-    const int f = (int)blockIdx.x / strips;
-    const int sidx = (int)blockIdx.x - f * strips;
-    if (blockIdx.x == 0 && threadIdx.x < kMaxQueues && ia.head_err) {
-        if (threadIdx.x == 0) {
+    static_assert(kPrepColW == 64 && kMaxQueues <= kPrepColW, "one wave per unit");
+    __shared__ double sh_neq[32 + 16];  // the last arriver's solve: [kNeq] sums, [16] T64
+    __shared__ float sh_T32[12];
+    const int lane = threadIdx.x;
+    const int per = blocks_x * bands;  // units per frame
+    const int f = (int)blockIdx.x / per;
+    const int unit = (int)blockIdx.x - f * per;
+    const int bi = unit / blocks_x;
+    const int x0 = (unit - bi * blocks_x) * kPrepColW;
+    const int y0 = bi * band, y1 = min(y0 + band, H);
+    if (blockIdx.x == 0 && lane < kMaxQueues && ia.head_err) {
+        if (lane == 0) {
             ia.head_err[kQHead] = 0u;
             ia.head_err[kQError] = 0u;
             ia.head_err[kQSpins] = 0u;
             ia.head_err[kQWaited] = 0u;
         }
-        ia.head_err[kQHeads + kQHeadStride * threadIdx.x] = 0u;
+        ia.head_err[kQHeads + kQHeadStride * lane] = 0u;
     }
     const int N = W * H;
     const int p = out0 + f - ia.pm.tgt0;  // the pair whose target this frame is
-    const bool paired = (unsigned)p < (unsigned)ia.n_pairs;  // workgroup-uniform
-    // the pair's source depth through a buffer descriptor: a pixel outside
-    // the frame (ragged tile) takes the offset N 2, which reads as 0
+    const bool paired = (unsigned)p < (unsigned)ia.n_pairs;  // wave-uniform
+    // Depth words load through buffer descriptors over the frame: a row or a
+    // column outside the image takes an offset >= N 2 (the descriptor's size),
+    // which the range check returns as 0 with no branch: an outside pixel
+    // back-projects d = 0 at its own (u, v), as in prep_tile.  A frame that is
+    // no pair's target has an empty source descriptor: every source depth is
+    // 0, nothing matches and the sums stay untouched.
+    const __amdgpu_buffer_rsrc_t rdep = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<int16_t*>(depth + (size_t)f * N), (short)0, N * (int)sizeof(int16_t), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<int16_t*>(ia.dsrc + (size_t)(ia.pm.src0 + (paired ? p : 0)) * N), (short)0,
-        N * (int)sizeof(int16_t), 0x00020000);
-    const int tx = threadIdx.x % kPrepTW;
-    const int tyw = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kPrepTW);
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
+        paired ? N * (int)sizeof(int16_t) : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rrec = __builtin_amdgcn_make_buffer_rsrc(
+        recs + (size_t)(out0 + f) * P, (short)0, (int)(P * sizeof(float4)), 0x00020000);
+    const int oob = N * 2;
+    const int gx = x0 + lane;
+    const int col2 = gx < W ? gx * 2 : oob;
+    // the column beside the block: x0 - 1 in lane 0, x0 + 64 in lane 63 (the
+    // other lanes load nothing and never use what they back-project from it)
+    const int ex = lane == 0 ? x0 - 1 : x0 + kPrepColW;
+    const bool eload = ((lane == 0) | (lane == kPrepColW - 1)) & ((unsigned)ex < (unsigned)W);
+    const int ecol2 = eload ? ex * 2 : oob;
+    // a column >= W stores nothing: its offset is past the record descriptor
+    const int rcol = gx < W ? gx * (int)sizeof(float4) : (int)(P * sizeof(float4));
+
+    // the row tests are wave-uniform: they and the row offsets stay scalar
+    auto row2 = [&](int y, bool want) { return (want & ((unsigned)y < (unsigned)H)) ? y * W * 2 : oob; };
+    auto load_tgt = [&](int off) {
+        return (unsigned)__builtin_amdgcn_raw_buffer_load_b16(rdep, off, 0, 0);
+    };
+    auto load_row = [&](int y) {
+        const int rd = row2(y + 1, y < y1), rc = row2(y, y < y1);
+        PrepRowIn r;
+        r.t = load_tgt(col2 + rd);
+        r.e = load_tgt(ecol2 + rc);
+        r.s = (unsigned)__builtin_amdgcn_raw_buffer_load_b16(rsrc, col2 + rc, 0, 0);
+        return r;
+    };
+
     double acc[kNeq];
 #pragma unroll
     for (int q = 0; q < kNeq; ++q) acc[q] = 0.0;
     int cnt = 0;  // this lane's matches (exact in the fp64 sum, whatever the order)
 
-    const int t0 = sidx * strip, t1 = min(t0 + strip, per);
-    for (int r = t0; r < t1; ++r) {
-        const int tyi = r / tiles_x;
-        const int x0 = (r - tyi * tiles_x) * kPrepTW, y0 = tyi * kPrepTH;
-        // this thread's source depths, requested ahead of the tile's own loads
-        int sd[kSteps];
-#pragma unroll
-        for (int k = 0; k < kSteps; ++k) {
-            const int gx = x0 + tx, gy = y0 + tyw + kRows * k;
-            const bool in = paired & (gx < W) & (gy < H);
-            sd[k] = (short)__builtin_amdgcn_raw_buffer_load_b16(rsrc, in ? (gy * W + gx) * 2 : N * 2,
-                                                                0, 0);
-        }
-        if (r > t0) __syncthreads();  // the planes are reused
-        prep_tile_with<kFast, kWide, false, kPrepThreads, kPrepTH, kPrepTW>(
-            depth + (size_t)f * N, recs + (size_t)(out0 + f) * P, W, H, P, K, F, nullptr, x0, y0, sX,
-            sY, sZ,
-            [&](int k, float px, float py, float pz, const float4& rec)
-                __attribute__((always_inline)) {
-                    if (!paired) return;
-                    float sx, sy, sz;
-                    backproject<kFast>(sd[k], x0 + tx, y0 + tyw + kRows * k, K, F, sx, sy, sz);
-                    const f4v t = {rec.x, rec.y, rec.z, rec.w};
-                    const LaneMask okm = ident_accumulate_xy<kSp, true>(sx, sy, sz, px, py, t,
-                                                                        ia.thr2, acc);
-                    cnt += lane_in(okm) ? 1 : 0;
-                });
+    // the window: rows y - 1 (u*), y (c*), y + 1 (d*) of this lane's column
+    const int t_up = (short)load_tgt(col2 + row2(y0 - 1, true));
+    const int t_c = (short)load_tgt(col2 + row2(y0, true));
+    PrepRowIn in0 = load_row(y0), in1 = load_row(y0 + 1);
+    float ux, uy, uz, cx, cy, cz;
+    backproject<kFast>(t_up, gx, y0 - 1, K, F, ux, uy, uz);
+    backproject<kFast>(t_c, gx, y0, K, F, cx, cy, cz);
+    // One row: `in` holds the words of row y, requested two rows ago.  Once
+    // they are taken, the same registers are requested for row y + 2, BEFORE
+    // this row's record is stored: the wait for `in` is then a counted one that
+    // covers neither the younger loads nor any store.  The loop runs two rows
+    // per iteration so that in0 / in1 keep their registers (a copy from one to
+    // the other would wait for the younger request).
+    auto row = [&](int y, PrepRowIn& in) __attribute__((always_inline)) {
+        // taken through an empty asm: the values below are new ones to the
+        // compiler, so the request for row y + 2 lands in the registers of
+        // `in` itself and the loop ends without copying a word still in flight
+        int dt = (short)in.t, de = (short)in.e, dsr = (short)in.s;
+        asm volatile("" : "+v"(dt), "+v"(de), "+v"(dsr));
+        in = load_row(y + 2);
+        float dx, dy, dz, ox, oy, oz;
+        backproject<kFast>(dt, gx, y + 1, K, F, dx, dy, dz);
+        backproject<kFast>(de, ex, y, K, F, ox, oy, oz);
+        const bool inner = (gx > 0) & (y > 0) & (gx < W - 1) & (y < H - 1);
+        const float4 rec =
+            prep_record(cx, cy, cz, from_left(cx, ox), from_left(cy, oy), from_left(cz, oz),
+                        from_right(cx, ox), from_right(cy, oy), from_right(cz, oz), ux, uy, uz, dx,
+                        dy, dz, inner);
+        // non-temporal, through the frame's descriptor (as prep_tile's)
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, rec), rrec,
+                                               rcol + y * W * (int)sizeof(float4), 0, 2);
+        float sx, sy, sz;
+        backproject<kFast>(dsr, gx, y, K, F, sx, sy, sz);
+        const f4v t = {rec.x, rec.y, rec.z, rec.w};
+        const LaneMask okm = ident_accumulate_xy<kSp, true>(sx, sy, sz, cx, cy, t, ia.thr2, acc);
+        cnt += lane_in(okm) ? 1 : 0;
+        ux = cx, uy = cy, uz = cz;
+        cx = dx, cy = dy, cz = dz;
+    };
+    // Everything requested so far has landed before the loop is entered
+    // (vmcnt(0), once per unit): with requests still in flight on entry the
+    // compiler sizes the loop's waits for the entry edge, where no store
+    // stands between the requests, and every iteration would wait for the
+    // previous row's store.
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    int y = y0;
+    for (; y + 1 < y1; y += 2) {
+        row(y, in0);
+        row(y + 1, in1);
     }
+    if (y < y1) row(y, in0);  // the last row of a band of odd length
     if (!paired) return;
     acc[28] = (double)cnt;
     double tot;
     wave_reduce_scatter<kNeq>(acc, lane, tot);
-    __syncthreads();  // every wave has left the planes
-    double(*red)[kNeq] = reinterpret_cast<double(*)[kNeq]>(sX);
-    if (!(lane & 1) && (lane >> 1) < kNeq) red[wave][lane >> 1] = tot;
-    __syncthreads();
-    if (threadIdx.x >= 64) return;  // wave 0 publishes (and, if last, solves)
-    double s = 0.0;
-    if (lane < kNeq) {
-        double w[kWaves];
-#pragma unroll
-        for (int q = 0; q < kWaves; ++q) w[q] = red[q][lane];
-        s = tree_sum<kWaves>(w);
-    }
+    // lanes 2q and 2q + 1 hold the sum of value q: lane q takes it
+    const double s = __shfl(tot, (2 * lane) & 63, 64);
     PoseState ps{};
     ps.arrivals = ia.arrivals;
-    if (!handoff_publish<kNeq>(ia.partials + ((size_t)p * strips + sidx) * kPartStride, ps, p, strips,
-                               lane, s))
+    if (!handoff_publish<kNeq>(ia.partials + ((size_t)p * per + unit) * kPartStride, ps, p, per, lane,
+                               s))
         return;
     double neq[kNeq];
-    handoff_sum<kNeq, kPartStride>(ia.partials, p, strips, lane, neq);
-    double* sh_neq = reinterpret_cast<double*>(sY);  // [kNeq] (wave 0 alone is left)
-    double* sh_T64 = sh_neq + 32;                    // [16]
-    float* sh_T32 = reinterpret_cast<float*>(sh_T64 + 16);  // [12]
+    handoff_sum<kNeq, kPartStride>(ia.partials, p, per, lane, neq);
+    double* sh_T64 = sh_neq + 32;  // [16]
     if (lane == 0) {
 #pragma unroll
         for (int q = 0; q < kNeq; ++q) sh_neq[q] = neq[q];
@@ -2175,16 +2196,14 @@ static int launch_prep_with(youth_icp_ctx* c, hipStream_t s, const int16_t* dept
     return ev_end(c, s, &ep);
 }
 
-// k_prep_ident<spec, fast, wide> by index spec 4 + fast 2 + wide
+// k_prep_ident<spec, fast> by index spec 2 + fast
 typedef void (*PrepIdentKernel)(const int16_t*, int, int, int, size_t, Intr, FastK, float4*,
                                 IdentArgs, int, int, int);
 static PrepIdentKernel prep_ident_kernel(int idx)
 {
-    static const PrepIdentKernel tab[8] = {
-        k_prep_ident<0, false, false>, k_prep_ident<0, false, true>, k_prep_ident<0, true, false>,
-        k_prep_ident<0, true, true>,   k_prep_ident<1, false, false>, k_prep_ident<1, false, true>,
-        k_prep_ident<1, true, false>,  k_prep_ident<1, true, true>};
-    return tab[idx & 7];
+    static const PrepIdentKernel tab[4] = {k_prep_ident<0, false>, k_prep_ident<0, true>,
+                                           k_prep_ident<1, false>, k_prep_ident<1, true>};
+    return tab[idx & 3];
 }
 
 // The prep job with iteration 0 of every pair inside it (k_prep_ident); nb:
@@ -2193,36 +2212,38 @@ static int launch_prep_ident(youth_icp_ctx* c, hipStream_t s, const PrepJob* job
                              const int16_t* dsrc, PairMap pm, int n_pairs, int iters, float thr2,
                              int nb, float* d_T_out)
 {
-    const int tiles_x = (c->W + kPrepTW - 1) / kPrepTW, tiles_y = (c->H + kPrepTH - 1) / kPrepTH;
-    const int per = tiles_x * tiles_y;
-    // Tiles per workgroup: a longer strip means fewer reductions and
-    // publishes (one tile per workgroup would be 51,200 of them at 512 frames
-    // of 640x480) but fewer workgroups to balance over the chip.  Measured at
-    // 512 pairs (profiles/ident/strip_sweep.txt): 2 tiles 88.3 K aligns/s, 4
-    // 90.3, 5 90.5, 10 91.2, 20 91.6, 25 91.7, 50 91.3, 100 91.1.  So 25,
-    // shortened for small batches until the grid holds about four rounds of
-    // the two resident workgroups per CU, but not below 5.
-    int strip = c->prep_strip;
-    if (strip <= 0) {
-        strip = (int)std::min<long long>(25, (long long)per * job->n / (8LL * c->n_cu));
-        strip = std::max(strip, 5);
+    const int blocks_x = (c->W + kPrepColW - 1) / kPrepColW;
+    // Rows per unit: a longer band means fewer halo rows, unit starts (one
+    // memory round trip before the first row), reductions and publishes, but
+    // fewer waves to balance over the chip.  Measured at 640x480
+    // (profiles/colprep/band_sweep.txt): at 512 pairs 24 rows 87.4 K aligns/s,
+    // 48 88.3, 96 88.5, 120 88.4, 160 88.5, 240 88.2, 480 88.4; at 64, 128 and
+    // 256 pairs the long bands win too (64 pairs: 24 rows 79.1, 48 81.4, 96
+    // 81.5, 160 81.6, with 1,920 units on 4,096 wave slots), so a small batch
+    // does not shorten its bands to fill the chip as the tile form shortened
+    // its strips.  Below 64 pairs nothing is measured: there the band shortens
+    // until the grid holds one wave per SIMD, but not below 24 rows.
+    int band = c->prep_band;
+    if (band <= 0) {
+        const long long rows = (long long)c->H * blocks_x * job->n / (4LL * c->n_cu);
+        band = (int)std::max<long long>(std::min<long long>(kPrepBand, rows), 24);
     }
-    strip = std::min(strip, per);
-    const int strips = (per + strip - 1) / strip;
-    const long long blocks = (long long)strips * job->n;
-    if (blocks > 0x7fffffffLL) return g_icp_err.set(YOUTH_EINVAL, "launch_prep: %lld strips", blocks);
-    int rc = ensure_partials(c, (size_t)std::max(nb, strips) * n_pairs * kPartStride);
+    band = std::min(band, c->H);
+    const int bands = (c->H + band - 1) / band;
+    const int per = blocks_x * bands;  // units, and partial rows, per frame
+    const long long blocks = (long long)per * job->n;
+    if (blocks > 0x7fffffffLL) return g_icp_err.set(YOUTH_EINVAL, "launch_prep: %lld units", blocks);
+    int rc = ensure_partials(c, (size_t)std::max(nb, per) * n_pairs * kPartStride);
     if (rc) return rc;
     EventPair ep{};
     rc = ev_begin(c, s, &ep, 2);
     if (rc) return rc;
-    const bool wide = (c->W % 4 == 0) && (reinterpret_cast<uintptr_t>(job->depth) % 8 == 0);
     const IdentArgs ia{dsrc,      pm,        n_pairs,     iters,      thr2,
                        c->d_partials, c->d_T64, c->d_T32,  c->d_status, c->d_stats,
                        c->d_epoch, c->d_arr_it, c->d_arrivals, d_T_out,  c->d_head};
-    auto kern = prep_ident_kernel(c->spec * 4 + (c->fast ? 2 : 0) + (wide ? 1 : 0));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kPrepThreads), 0, s, job->depth, job->out0,
-                       c->W, c->H, c->P, c->K, c->F, c->d_rec, ia, tiles_x, tiles_y, strip);
+    auto kern = prep_ident_kernel(c->spec * 2 + (c->fast ? 1 : 0));
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kPrepColW), 0, s, job->depth, job->out0,
+                       c->W, c->H, c->P, c->K, c->F, c->d_rec, ia, blocks_x, bands, band);
     HIP_TRY(hipGetLastError());
     return ev_end(c, s, &ep);
 }
