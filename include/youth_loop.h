@@ -34,6 +34,7 @@
 #include <stdint.h>
 
 #include "youth_icp.h"
+#include "youth_rgbd.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -111,10 +112,21 @@ int youth_loop_candidates(youth_loop* lp, int kf, int k, int* idx, uint32_t* dis
 
 /* Retrieve the candidates of keyframe kf and verify them: one RGB-D batch of
  * every candidate forward (source kf, target k) and backward, from the
- * identity, youth_rgbd_default_params().  A candidate becomes the edge
+ * identity, youth_rgbd_default_params() (or the schedule of
+ * youth_loop_set_levels).  A candidate becomes the edge
  * (k, kf, Z = T_fwd) iff both statuses are 0 and the four gates of
  * youth_loop_params hold.  Returns the number of edges added. */
 int youth_loop_close(youth_loop* lp, int kf);
+
+/* Verify coarse to fine: the level schedule (youth_rgbd.h) of
+ * the object's own RGB-D context; n = 0 (the default) switches it off.  The
+ * last level must have stride 1 and at least one iteration: the four gates
+ * read the last level's statistics, the overlap against W H, and the status
+ * gate the OR of all levels' status words.  YOUTH_EINVAL otherwise, with the
+ * schedule left as it was. */
+int youth_loop_set_levels(youth_loop* lp, const youth_rgbd_level* levels, int n);
+/* At most cap levels into out (nullable with cap 0); returns their number. */
+int youth_loop_get_levels(const youth_loop* lp, youth_rgbd_level* out, int cap);
 
 /* The measures of the candidates the last youth_loop_close verified, accepted
  * or not (i = k, j = kf, w = 1 accepted / 0 rejected): at most cap into out.
@@ -168,7 +180,11 @@ int youth_posegraph_interpolate(int n_frames, double* X, int n_kf, const int32_t
  * module keeps keyframes and closes loops in its worker.  A recorded frame
  * becomes a keyframe when it has moved YOUTH_SLAM_LOOP_KF_M metres (default
  * 0.10) or YOUTH_SLAM_LOOP_KF_DEG degrees (default 10) from the last one; the
- * first frame always is.  YOUTH_SLAM_LOOP_MIN_GAP overrides min_gap.  The live
+ * first frame always is.  YOUTH_SLAM_LOOP_MIN_GAP overrides min_gap.
+ * YOUTH_SLAM_LOOP_LEVELS sets the closer's level schedule: `auto`
+ * (youth_rgbd_default_levels for the frame size) or a list stride:iterations
+ * such as 8:10,1:10; unset: none; a malformed value is logged once and
+ * ignored.  The live
  * trajectory is never rewritten.  saveSlamMap then writes the optimised
  * keyframe poses to <map_file>_keyframes.txt and the corrected trajectory to
  * <map_file>_trajectory_closed.txt.  Without the variable the module behaves

@@ -101,7 +101,66 @@ int youth_rgbd_get_poses(youth_rgbd_ctx* ctx, int n, double* T64, float* T32, in
  * stats [n][iters][4] = sum r^2, geometric count, sum rp^2, photometric count. */
 int youth_rgbd_get_stats(youth_rgbd_ctx* ctx, int n, int iters, double* stats);
 
+/* --- Level schedule: coarse to fine -----------------------
+ * The align converges only from nearby; run first on a sub-sampled copy of
+ * the frames it converges from much further.  A level (s, iters), s one of
+ * 1, 2, 4, 8, 16, is the align above, unchanged, on
+ *
+ *   frames   W_s = (W + s - 1) / s, H_s likewise;
+ *            depth_s[j][i] = depth[s j][s i], gray_s[j][i] = gray[s j][s i]
+ *            (plain decimation, no averaging)
+ *   camera   K_s = {fx / s, fy / s, cx / s, cy / s, depth_scale}: fp32
+ *            divisions by a power of two, hence exact, so the back-projected
+ *            point of level pixel (i, j) is bit for bit the full-resolution
+ *            point of pixel (s i, s j)
+ *
+ * with normals and intensity gradients formed on the level's own grid by the
+ * rules above.  A schedule is 1 .. YOUTH_RGBD_MAX_LEVELS levels of strictly
+ * decreasing stride, every W_s, H_s >= 3, iters >= 0.  Level 0 starts from
+ * T_init (or the identity), level l from level l - 1's final fp64 pose; each
+ * level runs with the context's dist_thresh and lambda; the result is the last
+ * level's pose (its stride need not be 1) and the status the OR of all levels'
+ * status words.  Numpy restatement: tests/rgbd_levels_truth.py. */
+typedef struct youth_rgbd_level { int stride; int iters; } youth_rgbd_level;
+#define YOUTH_RGBD_MAX_LEVELS 4
+
+/* The schedule the measurements of §16 were made with: the largest s of 8, 4, 2
+ * with W / s >= 80 and H / s >= 60 at 10 iterations, then 1:10 (8 at 640x480,
+ * 4 at 320x240, 2 at 160x120); 1:10 alone for smaller frames.  Returns the
+ * number of levels written to out. */
+int youth_rgbd_default_levels(int W, int H, youth_rgbd_level out[YOUTH_RGBD_MAX_LEVELS]);
+
+/* Set the context's schedule (n = 0: off, the default).  With one set,
+ * youth_rgbd_align_pairs_device and youth_rgbd_align_sequence_device run it
+ * (one decimation launch for all coarse levels and frames of the call, every
+ * frame prepped once per level, no host synchronisation between levels) and
+ * params.iters is not used; youth_rgbd_get_poses and youth_rgbd_get_stats
+ * report the last level, the former with the OR status.  The streaming
+ * tracker does not run schedules: youth_rgbd_track_submit is YOUTH_EINVAL
+ * while one is set, and this call while frames are pending.  YOUTH_EINVAL
+ * leaves the schedule as it was.  Allocates one workspace per coarse level. */
+int youth_rgbd_set_levels(youth_rgbd_ctx* ctx, const youth_rgbd_level* levels, int n);
+
+/* At most cap levels into out (nullable with cap 0); returns their number. */
+int youth_rgbd_get_levels(const youth_rgbd_ctx* ctx, youth_rgbd_level* out, int cap);
+
+/* One level of the last scheduled align (synchronises): its final poses T64
+ * [n][16] and its own status words [n]; each nullable. */
+int youth_rgbd_get_level_poses(youth_rgbd_ctx* ctx, int level, int n, double* T64, int32_t* status);
+
+/* youth_rgbd_get_stats of one level; iters: that level's. */
+int youth_rgbd_get_level_stats(youth_rgbd_ctx* ctx, int level, int n, int iters, double* stats);
+
 /* --- Stage-level entry points (validation / parity tests) --------------- */
+
+/* The decimation alone (k_rgbd_decimate, the single-stride case of the
+ * schedule's launch): n frames depth [n][H][W] int16 and intensity [n][H][W]
+ * uint8 on `device` -> d_depth_out / d_gray_out [n][H_s][W_s], nothing written
+ * outside them.  stride 2, 4, 8 or 16; 0 <= n <= 65535; asynchronous on
+ * `stream`. */
+int youth_rgbd_decimate_device(int device, const int16_t* d_depth, const uint8_t* d_gray, int n,
+                               int W, int H, int stride, int16_t* d_depth_out, uint8_t* d_gray_out,
+                               void* stream);
 
 /* The target preparation alone: n frames of `channels` = 3 (RGB [n][H][W][3])
  * or 1 (intensity [n][H][W]) on the device -> d_gray (nullable) [n][H][W] uint8

@@ -435,6 +435,29 @@ youth_loop* youth_loop_create(int device, int W, int H, int max_keyframes, const
     return lp;
 }
 
+int youth_loop_set_levels(youth_loop* lp, const youth_rgbd_level* levels, int n)
+{
+    static const char* who = "youth_loop_set_levels";
+    if (!lp) return g_loop_err.set(YOUTH_EINVAL, "%s: null object", who);
+    if (n > 0 && !levels) return g_loop_err.set(YOUTH_EINVAL, "%s: null levels", who);
+    if (n > 0 && n <= YOUTH_RGBD_MAX_LEVELS && (levels[n - 1].stride != 1 || levels[n - 1].iters < 1))
+        return g_loop_err.set(YOUTH_EINVAL,
+                              "%s: the last level is %d:%d (the gates need stride 1 and an iteration)",
+                              who, levels[n - 1].stride, levels[n - 1].iters);
+    int rc = loop_bind(lp);
+    if (rc) return rc;
+    rc = youth_rgbd_set_levels(lp->rgbd, levels, n);
+    if (rc < 0) return g_loop_err.set(rc, "%s: %s", who, youth_rgbd_last_error());
+    return YOUTH_OK;
+}
+
+int youth_loop_get_levels(const youth_loop* lp, youth_rgbd_level* out, int cap)
+{
+    if (!lp || cap < 0 || (cap > 0 && !out))
+        return g_loop_err.set(YOUTH_EINVAL, "youth_loop_get_levels: bad arguments");
+    return youth_rgbd_get_levels(lp->rgbd, out, cap);
+}
+
 int youth_loop_keyframes(const youth_loop* lp) { return lp ? (int)lp->kfs.size() : 0; }
 
 int youth_loop_clear(youth_loop* lp)
@@ -566,7 +589,10 @@ int youth_loop_close(youth_loop* lp, int kf)
         HIP_TRY(hipMemcpyAsync(lp->b_dg + p * N, lp->d_gray + dst * N, N, hipMemcpyDeviceToDevice,
                                lp->stream));
     }
-    const int iters = lp->rp.iters;
+    // the gates read the last level's statistics where a schedule is set
+    youth_rgbd_level lv[YOUTH_RGBD_MAX_LEVELS];
+    const int n_lv = youth_rgbd_get_levels(lp->rgbd, lv, YOUTH_RGBD_MAX_LEVELS);
+    const int iters = n_lv > 0 ? lv[n_lv - 1].iters : lp->rp.iters;
     double T[2 * YOUTH_LOOP_MAX_CANDIDATES][16];
     int32_t st[2 * YOUTH_LOOP_MAX_CANDIDATES];
     std::vector<double> stats((size_t)2 * K * iters * 4);

@@ -27,6 +27,10 @@
 //                  arrival ticket; the pair's last workgroup adds the rows in a
 //                  fixed order and runs the a10 solve and update.
 //                  23 B/px/iteration: depth 2, Y 1, record 16, word 4.
+//   k_rgbd_decimate  the level schedule's frames: every
+//                  coarse level's plainly decimated depth and intensity of
+//                  every frame of a call in one launch; a level then runs the
+//                  kernels above, unchanged, on a context of its own size.
 //
 // Always the survey arithmetic of a7/a8 (no FMA, IEEE division) and the exact
 // reduction of a9, whatever the ICP context's spec and reduce modes are.
@@ -447,6 +451,130 @@ __global__ __launch_bounds__(kRedThreads) void k_rgbd_reduce(
     }
 }
 
+// The level schedule's frames: plain decimation, out[j][i] =
+// in[s j][s i], of both planes, for every coarse level of a schedule and every
+// frame of a call in one launch.  Strides are powers of two, so a pixel of a
+// coarser level is a pixel of every finer one: a thread takes a unit of 16
+// pixels of a row the finest coarse level keeps (rows y = smin ky), reads it
+// once and emits each level whose stride divides y from the same registers.
+// Two frame sets (a pair call's sources and targets) share the launch.
+// kVec: W % 16 == 0 and every base 16-byte aligned, so a unit lies in one row
+// and moves as three 16-byte loads (the rows' cache lines are fetched whole
+// either way) and a level's 16 / s pixels as one aligned store per plane; else
+// guarded element loads of the kept pixels and element stores.  3 B/px of the
+// kept rows in, 3 B per level pixel out.  No LDS, no atomics.
+constexpr int kDecThreads = 256;
+constexpr int kDecUnit = 16;
+constexpr int kDecMaxLv = YOUTH_RGBD_MAX_LEVELS;
+
+struct DecimJob {
+    const int16_t* depth[2];  // set k: [n[k]][H][W]
+    const uint8_t* gray[2];
+    int n[2];
+    int n_lv;                 // levels to emit, strides decreasing
+    int stride[kDecMaxLv];    // each of 2, 4, 8, 16
+    int16_t* dout[2][kDecMaxLv];  // [set][level]: [n[set]][H_s][W_s]
+    uint8_t* gout[2][kDecMaxLv];
+};
+
+// dw: the unit's depths, pixel p in half p % 2 of word p / 2; gw: its
+// intensities, pixel p in byte p % 4 of word p / 4.  Emits pixels 0, S, 2 S, ...
+template <int S, bool kVec>
+__device__ __forceinline__ void decim_emit(const unsigned (&dw)[8], const unsigned (&gw)[4], int x0,
+                                           int y, int W, int H, int frame,
+                                           int16_t* __restrict__ dout, uint8_t* __restrict__ gout)
+{
+    constexpr int C = kDecUnit / S;  // level pixels of the unit
+    const int Ws = (W + S - 1) / S, Hs = (H + S - 1) / S;
+    const size_t at = ((size_t)frame * Hs + y / S) * Ws + x0 / S;
+    unsigned d[C], g[C];
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        const int p = k * S;
+        d[k] = (dw[p >> 1] >> (16 * (p & 1))) & 0xffffu;
+        g[k] = (gw[p >> 2] >> (8 * (p & 3))) & 0xffu;
+    }
+    if constexpr (!kVec) {
+#pragma unroll
+        for (int k = 0; k < C; ++k)
+            if (x0 + k * S < W) {  // so column (x0 + k S) / S < W_s
+                dout[at + k] = (int16_t)d[k];
+                gout[at + k] = (uint8_t)g[k];
+            }
+    } else if constexpr (C == 8) {
+        *reinterpret_cast<uint4*>(dout + at) = uint4{d[0] | (d[1] << 16), d[2] | (d[3] << 16),
+                                                     d[4] | (d[5] << 16), d[6] | (d[7] << 16)};
+        *reinterpret_cast<uint2*>(gout + at) =
+            uint2{g[0] | (g[1] << 8) | (g[2] << 16) | (g[3] << 24),
+                  g[4] | (g[5] << 8) | (g[6] << 16) | (g[7] << 24)};
+    } else if constexpr (C == 4) {
+        *reinterpret_cast<uint2*>(dout + at) = uint2{d[0] | (d[1] << 16), d[2] | (d[3] << 16)};
+        *reinterpret_cast<unsigned*>(gout + at) = g[0] | (g[1] << 8) | (g[2] << 16) | (g[3] << 24);
+    } else if constexpr (C == 2) {
+        *reinterpret_cast<unsigned*>(dout + at) = d[0] | (d[1] << 16);
+        *reinterpret_cast<unsigned short*>(gout + at) = (unsigned short)(g[0] | (g[1] << 8));
+    } else {
+        dout[at] = (int16_t)d[0];
+        gout[at] = (uint8_t)g[0];
+    }
+}
+
+// grid (bpf (n[0] + n[1])): bpf workgroups per frame, over ceil(W / 16) units x
+// ceil(H / smin) kept rows; smin: the job's last (smallest) stride.
+template <bool kVec>
+__global__ __launch_bounds__(kDecThreads) void k_rgbd_decimate(DecimJob job, int W, int H, int smin,
+                                                               int bpf)
+{
+    const int upr = (W + kDecUnit - 1) / kDecUnit;
+    const int rows = (H + smin - 1) / smin;
+    const int fb = (int)(blockIdx.x / (unsigned)bpf);
+    const int idx = ((int)blockIdx.x - fb * bpf) * kDecThreads + (int)threadIdx.x;
+    if (idx >= upr * rows) return;
+    const int ky = idx / upr;
+    const int x0 = (idx - ky * upr) * kDecUnit;
+    const int y = ky * smin;
+    // the job's arrays are read at constant indices only (they stay in SGPRs)
+    const bool second = fb >= job.n[0];
+    const int frame = second ? fb - job.n[0] : fb;
+    const int16_t* __restrict__ dp = second ? job.depth[1] : job.depth[0];
+    const uint8_t* __restrict__ gp = second ? job.gray[1] : job.gray[0];
+    const size_t in = ((size_t)frame * H + y) * W + x0;
+    unsigned dw[8], gw[4];
+    if (kVec) {
+        const uint4 da = *reinterpret_cast<const uint4*>(dp + in);
+        const uint4 db = *reinterpret_cast<const uint4*>(dp + in + 8);
+        const uint4 ga = *reinterpret_cast<const uint4*>(gp + in);
+        dw[0] = da.x, dw[1] = da.y, dw[2] = da.z, dw[3] = da.w;
+        dw[4] = db.x, dw[5] = db.y, dw[6] = db.z, dw[7] = db.w;
+        gw[0] = ga.x, gw[1] = ga.y, gw[2] = ga.z, gw[3] = ga.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) dw[k] = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gw[k] = 0u;
+#pragma unroll
+        for (int p = 0; p < kDecUnit; p += 2)  // odd pixels belong to no level
+            if ((p & (smin - 1)) == 0 && x0 + p < W) {
+                dw[p >> 1] = (unsigned)(unsigned short)dp[in + p];
+                gw[p >> 2] |= (unsigned)gp[in + p] << (8 * (p & 3));
+            }
+    }
+#pragma unroll
+    for (int l = 0; l < kDecMaxLv; ++l) {
+        if (l >= job.n_lv) break;
+        const int s = job.stride[l];
+        if (y & (s - 1)) continue;  // the level does not keep this row
+        int16_t* __restrict__ dq = second ? job.dout[1][l] : job.dout[0][l];
+        uint8_t* __restrict__ gq = second ? job.gout[1][l] : job.gout[0][l];
+        switch (s) {
+        case 2: decim_emit<2, kVec>(dw, gw, x0, y, W, H, frame, dq, gq); break;
+        case 4: decim_emit<4, kVec>(dw, gw, x0, y, W, H, frame, dq, gq); break;
+        case 8: decim_emit<8, kVec>(dw, gw, x0, y, W, H, frame, dq, gq); break;
+        default: decim_emit<16, kVec>(dw, gw, x0, y, W, H, frame, dq, gq); break;
+        }
+    }
+}
+
 }  // namespace
 
 // =============================================================== host side ==
@@ -467,6 +595,23 @@ struct youth_rgbd_ctx {
     double* d_neq = nullptr;       // [kRgbdNeq]
     int last_pairs = 0, last_iters = 0;
     hipStream_t last_stream = nullptr;
+
+    // level schedule (youth_rgbd_set_levels).  A level's
+    // workspace is a context of its own, W_s x H_s under K_s (this one for
+    // stride 1); a coarse level's frames are decimated into depth / gray: the
+    // call's sources (or its sequence) from element 0, its targets from
+    // element off.
+    struct Level {
+        youth_rgbd_level lv{};
+        youth_rgbd_ctx* ctx = nullptr;
+        int16_t* depth = nullptr;
+        uint8_t* gray = nullptr;
+        size_t off = 0;  // elements, a multiple of 16
+    };
+    struct Schedule {
+        int n = 0;
+        Level at[YOUTH_RGBD_MAX_LEVELS];
+    } sched;
 
     // streaming tracker (youth_rgbd_track_*).  Depth and
     // intensity: two banks of trk_b frame slots, a submission's frames in the
@@ -497,6 +642,8 @@ struct youth_rgbd_ctx {
     } sub[2];
     int sub_head = 0, sub_n = 0;  // oldest submission in flight, submissions in flight
 };
+
+static int rgbd_track_pending(const youth_rgbd_ctx* r);
 
 static int rgbd_size_ok(const char* who, int n, int W, int H)
 {
@@ -538,11 +685,11 @@ static int rgbd_ensure_stats(youth_rgbd_ctx* r, int iters)
     return grow_device_buffer(g_icp_err, &r->d_stats, &r->stats_iters, iters, (size_t)r->frames * 4);
 }
 
-// One k_rgbd_reduce launch over n_pairs pairs: iteration `it` with its fused
-// solve, or (neq_out) the sums alone.
+// One k_rgbd_reduce launch over n_pairs pairs: iteration `it` of `iters` with
+// its fused solve, or (neq_out) the sums alone.
 // geo_pairs: the pair count the chunks are planned for (0: n_pairs).
 static int rgbd_launch_reduce(youth_rgbd_ctx* r, hipStream_t s, const int16_t* dsrc,
-                              const uint8_t* gsrc, PairMap pm, int n_pairs, int it,
+                              const uint8_t* gsrc, PairMap pm, int n_pairs, int it, int iters,
                               double* neq_out, int geo_pairs = 0)
 {
     youth_icp_ctx* c = r->icp;
@@ -556,7 +703,7 @@ static int rgbd_launch_reduce(youth_rgbd_ctx* r, hipStream_t s, const int16_t* d
                          (reinterpret_cast<uintptr_t>(gsrc) % 4 == 0) && (c->W % 4 == 0) &&
                          c->centred_exact;
     const RgbdState ps{{c->d_T64, c->d_T32, c->d_status, neq_out ? nullptr : r->d_stats,
-                        c->d_arrivals, it, r->prm.iters},
+                        c->d_arrivals, it, iters},
                        neq_out};
     auto kern = c->fast ? (aligned ? k_rgbd_reduce<true, true> : k_rgbd_reduce<true, false>)
                         : (aligned ? k_rgbd_reduce<false, true> : k_rgbd_reduce<false, false>);
@@ -567,18 +714,15 @@ static int rgbd_launch_reduce(youth_rgbd_ctx* r, hipStream_t s, const int16_t* d
 }
 
 // Targets prepped (records by k_prep, words by k_rgbd_prep) into workspace
-// frames [0, n_tgt); then the initial poses and prm.iters launches.
-static int rgbd_align(youth_rgbd_ctx* r, hipStream_t s, const int16_t* dsrc, const uint8_t* gsrc,
-                      const int16_t* dtgt, const uint8_t* gtgt, int n_tgt, PairMap pm, int n_pairs,
-                      const double* T_init_host, float* d_T_out)
+// frames [0, n_tgt); then the initial poses (dTi: device, or null for the
+// identity) and `iters` launches.
+static int rgbd_align_from(youth_rgbd_ctx* r, hipStream_t s, const int16_t* dsrc,
+                           const uint8_t* gsrc, const int16_t* dtgt, const uint8_t* gtgt, int n_tgt,
+                           PairMap pm, int n_pairs, const double* dTi, int iters, float* d_T_out)
 {
     youth_icp_ctx* c = r->icp;
     r->trk_ref = -1;  // the workspace is shared: the streaming tracker starts anew
-    const double* dTi = nullptr;
-    int rc = upload_T_init(c, s, T_init_host, n_pairs, &dTi);
-    if (rc) return rc;
-    const int iters = r->prm.iters;
-    rc = rgbd_ensure_stats(r, iters > 0 ? iters : 1);
+    int rc = rgbd_ensure_stats(r, iters > 0 ? iters : 1);
     if (rc) return rc;
     rc = launch_prep(c, s, dtgt, n_tgt, 0, false);
     if (rc) return rc;
@@ -588,7 +732,7 @@ static int rgbd_align(youth_rgbd_ctx* r, hipStream_t s, const int16_t* dsrc, con
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(c->d_arrivals, 0, (size_t)c->max_frames * sizeof(unsigned), s));
     for (int it = 0; it < iters; ++it) {
-        rc = rgbd_launch_reduce(r, s, dsrc, gsrc, pm, n_pairs, it, nullptr);
+        rc = rgbd_launch_reduce(r, s, dsrc, gsrc, pm, n_pairs, it, iters, nullptr);
         if (rc) return rc;
     }
     r->last_pairs = n_pairs;
@@ -597,6 +741,114 @@ static int rgbd_align(youth_rgbd_ctx* r, hipStream_t s, const int16_t* dsrc, con
     if (!d_T_out) return YOUTH_OK;
     return export_poses(c, s, n_pairs, d_T_out, false);
 }
+
+// k_rgbd_decimate over the job's frames, W x H each
+static int rgbd_launch_decimate(hipStream_t s, const DecimJob& job, int W, int H)
+{
+    const int nf = job.n[0] + job.n[1];
+    if (nf <= 0 || job.n_lv <= 0) return YOUTH_OK;
+    const int smin = job.stride[job.n_lv - 1];
+    uintptr_t bits = 0;
+    for (int k = 0; k < 2; ++k) {
+        if (job.n[k] <= 0) continue;
+        bits |= reinterpret_cast<uintptr_t>(job.depth[k]) | reinterpret_cast<uintptr_t>(job.gray[k]);
+        for (int l = 0; l < job.n_lv; ++l)
+            bits |= reinterpret_cast<uintptr_t>(job.dout[k][l]) |
+                    reinterpret_cast<uintptr_t>(job.gout[k][l]);
+    }
+    const bool vec = W % kDecUnit == 0 && (bits & 15) == 0;
+    const long long units = (long long)((W + kDecUnit - 1) / kDecUnit) * ((H + smin - 1) / smin);
+    const long long bpf = (units + kDecThreads - 1) / kDecThreads;
+    if (bpf * nf >= (1LL << 24))  // a launch's threads fit 32 bits
+        return g_icp_err.set(YOUTH_EINVAL, "decimation: %d frames of %dx%d are too many for one launch",
+                             nf, W, H);
+    hipLaunchKernelGGL(vec ? k_rgbd_decimate<true> : k_rgbd_decimate<false>,
+                       dim3((unsigned)(bpf * nf)), dim3(kDecThreads), 0, s, job, W, H, smin, (int)bpf);
+    HIP_TRY(hipGetLastError());
+    return YOUTH_OK;
+}
+
+// The schedule's align: the frames of every coarse level in one decimation
+// (set 0: n_src source frames, set 1: n_tgt target frames, or none where the
+// targets are the sources' buffer, the sequence), then level after level on
+// its workspace, each from the pose the level before it left on the device.
+static int rgbd_align_levels(youth_rgbd_ctx* r, hipStream_t s, const int16_t* dsrc,
+                             const uint8_t* gsrc, int n_src, const int16_t* dtgt,
+                             const uint8_t* gtgt, int n_tgt, PairMap pm, int n_pairs,
+                             const double* T_init_host, float* d_T_out)
+{
+    const bool same = dtgt == dsrc && gtgt == gsrc;
+    DecimJob job{};
+    job.depth[0] = dsrc, job.gray[0] = gsrc, job.n[0] = n_src;
+    job.depth[1] = dtgt, job.gray[1] = gtgt, job.n[1] = same ? 0 : n_tgt;
+    const youth_rgbd_ctx::Schedule& S = r->sched;
+    for (int l = 0; l < S.n; ++l) {
+        const youth_rgbd_ctx::Level& L = S.at[l];
+        if (L.lv.stride == 1) continue;
+        const int k = job.n_lv++;
+        job.stride[k] = L.lv.stride;
+        job.dout[0][k] = L.depth, job.gout[0][k] = L.gray;
+        job.dout[1][k] = L.depth + L.off, job.gout[1][k] = L.gray + L.off;
+    }
+    int rc = rgbd_launch_decimate(s, job, r->icp->W, r->icp->H);
+    if (rc) return rc;
+    const double* dTi = nullptr;
+    for (int l = 0; l < S.n; ++l) {
+        const youth_rgbd_ctx::Level& L = S.at[l];
+        if (L.ctx != r) {
+            rc = bind_device(L.ctx->icp);
+            if (rc) return rc;
+        }
+        if (l == 0) {
+            rc = upload_T_init(L.ctx->icp, s, T_init_host, n_pairs, &dTi);
+            if (rc) return rc;
+        }
+        const bool full = L.lv.stride == 1;
+        const int16_t* ds = full ? dsrc : L.depth;
+        const uint8_t* gs = full ? gsrc : L.gray;
+        const int16_t* dt = full ? dtgt : same ? ds : L.depth + L.off;
+        const uint8_t* gt = full ? gtgt : same ? gs : L.gray + L.off;
+        rc = rgbd_align_from(L.ctx, s, ds, gs, dt, gt, n_tgt, pm, n_pairs, dTi, L.lv.iters,
+                             l == S.n - 1 ? d_T_out : nullptr);
+        if (rc) return rc;
+        dTi = L.ctx->icp->d_T64;
+    }
+    r->trk_ref = -1;
+    r->last_pairs = n_pairs;
+    r->last_stream = s;
+    return YOUTH_OK;
+}
+
+// The align of the context: its schedule where one is set, else prm.iters
+// iterations at full resolution.
+static int rgbd_align(youth_rgbd_ctx* r, hipStream_t s, const int16_t* dsrc, const uint8_t* gsrc,
+                      int n_src, const int16_t* dtgt, const uint8_t* gtgt, int n_tgt, PairMap pm,
+                      int n_pairs, const double* T_init_host, float* d_T_out)
+{
+    if (r->sched.n > 0)
+        return rgbd_align_levels(r, s, dsrc, gsrc, n_src, dtgt, gtgt, n_tgt, pm, n_pairs, T_init_host,
+                                 d_T_out);
+    const double* dTi = nullptr;
+    int rc = upload_T_init(r->icp, s, T_init_host, n_pairs, &dTi);
+    if (rc) return rc;
+    return rgbd_align_from(r, s, dsrc, gsrc, dtgt, gtgt, n_tgt, pm, n_pairs, dTi, r->prm.iters,
+                           d_T_out);
+}
+
+// A schedule of `owner` emptied: its child workspaces (which wait for their
+// streams) and its frames released.
+static void rgbd_drop_schedule(youth_rgbd_ctx::Schedule& S, const youth_rgbd_ctx* owner)
+{
+    for (youth_rgbd_ctx::Level& L : S.at) {
+        if (L.ctx && L.ctx != owner) youth_rgbd_destroy(L.ctx);
+        if (L.depth) (void)hipFree(L.depth);
+        if (L.gray) (void)hipFree(L.gray);
+        L = youth_rgbd_ctx::Level{};
+    }
+    S.n = 0;
+}
+
+static bool rgbd_stride_ok(int s) { return s == 1 || s == 2 || s == 4 || s == 8 || s == 16; }
 
 extern "C" {
 
@@ -614,6 +866,8 @@ youth_rgbd_params youth_rgbd_default_params(void)
 void youth_rgbd_destroy(youth_rgbd_ctx* r)
 {
     if (!r) return;
+    if (r->icp) (void)hipSetDevice(r->icp->device);
+    rgbd_drop_schedule(r->sched, r);
     if (r->icp) {
         (void)hipSetDevice(r->icp->device);
         if (r->last_stream) (void)hipStreamSynchronize(r->last_stream);
@@ -729,7 +983,7 @@ int youth_rgbd_align_pairs_device(youth_rgbd_ctx* r, const int16_t* d_src_depth,
                              r->frames - 1);
     int rc = bind_device(r->icp);
     if (rc) return rc;
-    return rgbd_align(r, pick_stream(r->icp, stream), d_src_depth, d_src_gray, d_dst_depth,
+    return rgbd_align(r, pick_stream(r->icp, stream), d_src_depth, d_src_gray, n_pairs, d_dst_depth,
                       d_dst_gray, n_pairs, PairMap{0, 0}, n_pairs, T_init, d_T_out);
 }
 
@@ -747,7 +1001,7 @@ int youth_rgbd_align_sequence_device(youth_rgbd_ctx* r, const int16_t* d_depth,
     if (rc) return rc;
     // every frame but the last is a target, prepped once; pair k: source frame
     // k + 1, target frame k
-    return rgbd_align(r, pick_stream(r->icp, stream), d_depth, d_gray, d_depth, d_gray,
+    return rgbd_align(r, pick_stream(r->icp, stream), d_depth, d_gray, n_frames, d_depth, d_gray,
                       n_frames - 1, PairMap{1, 0}, n_frames - 1, nullptr, d_T_out);
 }
 
@@ -760,7 +1014,8 @@ int youth_rgbd_sync(youth_rgbd_ctx* r, void* stream)
     return YOUTH_OK;
 }
 
-int youth_rgbd_get_poses(youth_rgbd_ctx* r, int n, double* T64, float* T32, int32_t* status)
+// youth_rgbd_get_poses on one workspace (a context without a schedule, or a level's)
+static int rgbd_get_poses_of(youth_rgbd_ctx* r, int n, double* T64, float* T32, int32_t* status)
 {
     if (!r || n < 0 || n > r->frames - 1)
         return g_icp_err.set(YOUTH_EINVAL, "youth_rgbd_get_poses: bad arguments (%d poses)", n);
@@ -788,7 +1043,7 @@ int youth_rgbd_get_poses(youth_rgbd_ctx* r, int n, double* T64, float* T32, int3
     return YOUTH_OK;
 }
 
-int youth_rgbd_get_stats(youth_rgbd_ctx* r, int n, int iters, double* stats)
+static int rgbd_get_stats_of(youth_rgbd_ctx* r, int n, int iters, double* stats)
 {
     if (!r || !stats || n < 0 || n > r->last_pairs || iters != r->last_iters || iters < 1 ||
         iters > r->stats_iters)
@@ -802,6 +1057,150 @@ int youth_rgbd_get_stats(youth_rgbd_ctx* r, int n, int iters, double* stats)
                                hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return YOUTH_OK;
+}
+
+int youth_rgbd_get_poses(youth_rgbd_ctx* r, int n, double* T64, float* T32, int32_t* status)
+{
+    if (!r || r->sched.n == 0) return rgbd_get_poses_of(r, n, T64, T32, status);
+    // the last level's poses; the status words of all levels ORed
+    int rc = rgbd_get_poses_of(r->sched.at[r->sched.n - 1].ctx, n, T64, T32, status);
+    if (rc || !status || n == 0) return rc;
+    std::vector<int32_t> st((size_t)n);
+    for (int l = 0; l < r->sched.n - 1; ++l) {
+        rc = rgbd_get_poses_of(r->sched.at[l].ctx, n, nullptr, nullptr, st.data());
+        if (rc) return rc;
+        for (int p = 0; p < n; ++p) status[p] |= st[p];
+    }
+    return YOUTH_OK;
+}
+
+int youth_rgbd_get_stats(youth_rgbd_ctx* r, int n, int iters, double* stats)
+{
+    if (!r || r->sched.n == 0) return rgbd_get_stats_of(r, n, iters, stats);
+    return rgbd_get_stats_of(r->sched.at[r->sched.n - 1].ctx, n, iters, stats);
+}
+
+int youth_rgbd_default_levels(int W, int H, youth_rgbd_level out[YOUTH_RGBD_MAX_LEVELS])
+{
+    if (!out) return g_icp_err.set(YOUTH_EINVAL, "youth_rgbd_default_levels: null output");
+    int n = 0;
+    for (int s = 8; s >= 2; s /= 2)
+        if (W / s >= 80 && H / s >= 60) {
+            out[n++] = youth_rgbd_level{s, 10};
+            break;
+        }
+    out[n++] = youth_rgbd_level{1, 10};
+    return n;
+}
+
+int youth_rgbd_set_levels(youth_rgbd_ctx* r, const youth_rgbd_level* levels, int n)
+{
+    static const char* who = "youth_rgbd_set_levels";
+    if (!r) return g_icp_err.set(YOUTH_EINVAL, "%s: null context", who);
+    if (n < 0 || n > YOUTH_RGBD_MAX_LEVELS)
+        return g_icp_err.set(YOUTH_EINVAL, "%s: %d levels (need 0 .. %d)", who, n,
+                             YOUTH_RGBD_MAX_LEVELS);
+    if (n > 0 && !levels) return g_icp_err.set(YOUTH_EINVAL, "%s: null levels", who);
+    if (r->sub_n > 0)
+        return g_icp_err.set(YOUTH_EINVAL, "%s: %d frames pending (collect them first)", who,
+                             rgbd_track_pending(r));
+    youth_icp_ctx* c = r->icp;
+    for (int l = 0; l < n; ++l) {
+        const int s = levels[l].stride;
+        if (!rgbd_stride_ok(s))
+            return g_icp_err.set(YOUTH_EINVAL, "%s: level %d has stride %d (need 1, 2, 4, 8 or 16)", who,
+                                 l, s);
+        if (l > 0 && s >= levels[l - 1].stride)
+            return g_icp_err.set(YOUTH_EINVAL, "%s: strides %d, %d of levels %d, %d do not decrease",
+                                 who, levels[l - 1].stride, s, l - 1, l);
+        if (levels[l].iters < 0)
+            return g_icp_err.set(YOUTH_EINVAL, "%s: level %d has %d iterations (need >= 0)", who, l,
+                                 levels[l].iters);
+        if ((c->W + s - 1) / s < 3 || (c->H + s - 1) / s < 3)
+            return g_icp_err.set(YOUTH_EINVAL, "%s: level %d of stride %d is %dx%d (need >= 3x3)", who,
+                                 l, s, (c->W + s - 1) / s, (c->H + s - 1) / s);
+    }
+    int rc = bind_device(c);
+    if (rc) return rc;
+    // the new schedule beside the old one, which stays if anything fails
+    youth_rgbd_ctx::Schedule next;
+    for (int l = 0; l < n; ++l) {
+        youth_rgbd_ctx::Level& L = next.at[l];
+        const int s = levels[l].stride;
+        L.lv = levels[l];
+        L.ctx = r;
+        if (s == 1) continue;  // this context itself, the caller's frames
+        const int Ws = (c->W + s - 1) / s, Hs = (c->H + s - 1) / s;
+        // fp32 divisions by a power of two: exact
+        const youth_intrinsics Ks{c->K.fx / (float)s, c->K.fy / (float)s, c->K.cx / (float)s,
+                                  c->K.cy / (float)s, c->K.ds};
+        const youth_rgbd_params P{levels[l].iters, r->prm.dist_thresh, r->prm.lambda};
+        L.ctx = youth_rgbd_create(c->device, Ws, Hs, r->frames - 1, &Ks, &P);
+        if (!L.ctx) {
+            rgbd_drop_schedule(next, r);
+            return g_icp_err.code();  // youth_rgbd_create's text stands
+        }
+        L.off = ((size_t)r->frames * Ws * Hs + 15) / 16 * 16;
+        hipError_t e = hipMalloc(&L.depth, 2 * L.off * sizeof(int16_t));
+        if (e == hipSuccess) e = hipMalloc(&L.gray, 2 * L.off);
+        if (e != hipSuccess) {
+            rgbd_drop_schedule(next, r);
+            return g_icp_err.set(e == hipErrorOutOfMemory ? YOUTH_ENOMEM : YOUTH_EHIP,
+                                 "%s: hipMalloc: %s", who, hipGetErrorString(e));
+        }
+    }
+    // nothing of the old schedule is in flight once its streams are idle
+    if (r->last_stream) HIP_TRY(hipStreamSynchronize(r->last_stream));
+    rgbd_drop_schedule(r->sched, r);
+    next.n = n;
+    r->sched = next;
+    return YOUTH_OK;
+}
+
+int youth_rgbd_get_levels(const youth_rgbd_ctx* r, youth_rgbd_level* out, int cap)
+{
+    if (!r || cap < 0 || (cap > 0 && !out))
+        return g_icp_err.set(YOUTH_EINVAL, "youth_rgbd_get_levels: bad arguments");
+    for (int l = 0; l < std::min(cap, r->sched.n); ++l) out[l] = r->sched.at[l].lv;
+    return r->sched.n;
+}
+
+int youth_rgbd_get_level_poses(youth_rgbd_ctx* r, int level, int n, double* T64, int32_t* status)
+{
+    if (!r || level < 0 || level >= r->sched.n)
+        return g_icp_err.set(YOUTH_EINVAL, "youth_rgbd_get_level_poses: level %d of %d", level,
+                             r ? r->sched.n : 0);
+    return rgbd_get_poses_of(r->sched.at[level].ctx, n, T64, nullptr, status);
+}
+
+int youth_rgbd_get_level_stats(youth_rgbd_ctx* r, int level, int n, int iters, double* stats)
+{
+    if (!r || level < 0 || level >= r->sched.n)
+        return g_icp_err.set(YOUTH_EINVAL, "youth_rgbd_get_level_stats: level %d of %d", level,
+                             r ? r->sched.n : 0);
+    return rgbd_get_stats_of(r->sched.at[level].ctx, n, iters, stats);
+}
+
+int youth_rgbd_decimate_device(int device, const int16_t* d_depth, const uint8_t* d_gray, int n, int W,
+                               int H, int stride, int16_t* d_depth_out, uint8_t* d_gray_out,
+                               void* stream)
+{
+    static const char* who = "youth_rgbd_decimate_device";
+    if (!d_depth || !d_gray || !d_depth_out || !d_gray_out)
+        return g_icp_err.set(YOUTH_EINVAL, "%s: null buffer", who);
+    if (stride == 1 || !rgbd_stride_ok(stride))
+        return g_icp_err.set(YOUTH_EINVAL, "%s: stride %d (need 2, 4, 8 or 16)", who, stride);
+    int rc = rgbd_size_ok(who, n, W, H);
+    if (rc) return rc;
+    rc = youth::check_device(g_icp_err, who, device);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(device));
+    DecimJob job{};
+    job.depth[0] = d_depth, job.gray[0] = d_gray, job.n[0] = n;
+    job.n_lv = 1;
+    job.stride[0] = stride;
+    job.dout[0][0] = d_depth_out, job.gout[0][0] = d_gray_out;
+    return rgbd_launch_decimate((hipStream_t)stream, job, W, H);
 }
 
 int youth_rgbd_reduce_host(youth_rgbd_ctx* r, const int16_t* src_depth, const uint8_t* src_gray,
@@ -831,7 +1230,7 @@ int youth_rgbd_reduce_host(youth_rgbd_ctx* r, const int16_t* src_depth, const ui
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(c->d_T32, T12, 12 * sizeof(float), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(c->d_arrivals, 0, sizeof(unsigned), s));
-    rc = rgbd_launch_reduce(r, s, c->d_depth, r->d_gray, PairMap{0, 1}, 1, 0, r->d_neq);
+    rc = rgbd_launch_reduce(r, s, c->d_depth, r->d_gray, PairMap{0, 1}, 1, 0, r->prm.iters, r->d_neq);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(neq31, r->d_neq, kRgbdNeq * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1052,7 +1451,8 @@ static int rgbd_track_enqueue(youth_rgbd_ctx* r, youth_rgbd_ctx::Sub& q,
         HIP_TRY(hipMemsetAsync(c->d_arrivals, 0, (size_t)pairs * sizeof(unsigned), s));
         const PairMap pm{ref >= 0 ? d0 : d0 + 1, ref >= 0 ? 0 : 1};
         for (int it = 0; it < iters; ++it) {
-            rc = rgbd_launch_reduce(r, s, c->d_depth, r->d_gray, pm, pairs, it, nullptr, r->trk_b);
+            rc = rgbd_launch_reduce(r, s, c->d_depth, r->d_gray, pm, pairs, it, iters, nullptr,
+                                    r->trk_b);
             if (rc) return rc;
         }
         HIP_TRY(hipMemcpyAsync(q.res, c->d_T64, (size_t)pairs * 16 * sizeof(double),
@@ -1109,6 +1509,11 @@ int youth_rgbd_track_submit(youth_rgbd_ctx* r, const int16_t* const* depth,
 {
     static const char* who = "youth_rgbd_track_submit";
     if (!r) return g_icp_err.set(YOUTH_EINVAL, "%s: null context", who);
+    if (r->sched.n > 0)
+        return g_icp_err.set(YOUTH_EINVAL,
+                             "%s: the context has a level schedule, which the streaming tracker "
+                             "does not run (youth_rgbd_set_levels with 0 levels switches it off)",
+                             who);
     int rc = rgbd_check_frames(who, depth, rgb, n_frames, r->trk_b);
     if (rc) return rc;
     if (r->sub_n >= 2)

@@ -21,6 +21,7 @@ from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int16, c_int32
 import numpy as np
 
 import youth_icp
+import youth_rgbd
 from youth_icp import YOUTH_EHIP, YOUTH_EINVAL, YOUTH_ENODEV, YOUTH_ENOMEM, IcpError, Intrinsics
 
 HEADER_PATH = os.path.join(os.path.dirname(youth_icp.HERE), "include", "youth_loop.h")
@@ -65,6 +66,8 @@ _SIGS = {
                                              c_uint32]),
     "youth_loop_candidates": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), _PU32]),
     "youth_loop_close": (c_int, [c_void_p, c_int]),
+    "youth_loop_set_levels": (c_int, [c_void_p, POINTER(youth_rgbd.RgbdLevel), c_int]),
+    "youth_loop_get_levels": (c_int, [c_void_p, POINTER(youth_rgbd.RgbdLevel), c_int]),
     "youth_loop_last_verified": (c_int, [c_void_p, c_void_p, c_int]),
     "youth_loop_keyframes": (c_int, [c_void_p]),
     "youth_loop_edges": (c_int, [c_void_p, c_void_p, c_int]),
@@ -264,6 +267,17 @@ class LoopCloser:
     def close(self, kf: int) -> int:
         """Retrieve and verify keyframe kf's candidates; returns the edges added."""
         return _check(self._lib, self._lib.youth_loop_close(self._lp, kf))
+
+    def set_levels(self, levels) -> None:
+        """Verify coarse to fine: [(stride, iters), ...] ending at stride 1
+        (DESIGN.md §16); empty or None: off."""
+        arr, n = youth_rgbd.level_array(levels)
+        _check(self._lib, self._lib.youth_loop_set_levels(self._lp, arr, n))
+
+    def levels(self) -> list[tuple[int, int]]:
+        out = (youth_rgbd.RgbdLevel * youth_rgbd.MAX_LEVELS)()
+        n = _check(self._lib, self._lib.youth_loop_get_levels(self._lp, out, youth_rgbd.MAX_LEVELS))
+        return [(out[k].stride, out[k].iters) for k in range(n)]
 
     def last_verified(self) -> np.ndarray:
         """The measures of every candidate the last close verified (w: 1 accepted)."""

@@ -27,8 +27,22 @@ class RgbdParams(ctypes.Structure):
     _fields_ = [("iters", c_int), ("dist_thresh", c_float), ("lam", c_float)]
 
 
+class RgbdLevel(ctypes.Structure):
+    """youth_rgbd_level."""
+    _fields_ = [("stride", c_int), ("iters", c_int)]
+
+
+MAX_LEVELS = 4  # YOUTH_RGBD_MAX_LEVELS
+
 _PD = POINTER(c_double)
 _SIGS = {
+    "youth_rgbd_default_levels": (c_int, [c_int, c_int, POINTER(RgbdLevel)]),
+    "youth_rgbd_set_levels": (c_int, [c_void_p, POINTER(RgbdLevel), c_int]),
+    "youth_rgbd_get_levels": (c_int, [c_void_p, POINTER(RgbdLevel), c_int]),
+    "youth_rgbd_get_level_poses": (c_int, [c_void_p, c_int, c_int, _PD, POINTER(c_int32)]),
+    "youth_rgbd_get_level_stats": (c_int, [c_void_p, c_int, c_int, c_int, _PD]),
+    "youth_rgbd_decimate_device": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                           c_void_p, c_void_p, c_void_p]),
     "youth_rgbd_default_params": (RgbdParams, []),
     "youth_rgbd_last_error": (c_char_p, []),
     "youth_rgbd_create": (c_void_p, [c_int, c_int, c_int, c_int, POINTER(Intrinsics),
@@ -110,6 +124,42 @@ def luma_device(d_rgb, d_gray=None, stream: int = 0):
     _check(lib, lib.youth_rgbd_luma_device(d_rgb.device.index or 0, _ptr(d_rgb), _ptr(d_gray), n,
                                            W, H, stream or None))
     return d_gray
+
+
+def level_array(levels):
+    """[(stride, iters), ...] -> (a ctypes array of youth_rgbd_level or None, its length)."""
+    lv = [tuple(int(v) for v in l) for l in (levels or ())]
+    if not lv:
+        return None, 0
+    return (RgbdLevel * len(lv))(*[RgbdLevel(s, it) for s, it in lv]), len(lv)
+
+
+def parse_levels(text: str, W: int, H: int):
+    """``auto`` -> default_levels(W, H); ``8:10,1:10`` -> [(8, 10), (1, 10)];
+    empty or ``none`` -> [] (the tools' --levels option)."""
+    if not text or text == "none":
+        return []
+    if text == "auto":
+        return default_levels(W, H)
+    return [tuple(int(v) for v in item.split(":")) for item in text.split(",")]
+
+
+def default_levels(W: int, H: int) -> list[tuple[int, int]]:
+    """youth_rgbd_default_levels -> [(stride, iters), ...]."""
+    lib = load_library()
+    out = (RgbdLevel * MAX_LEVELS)()
+    n = _check(lib, lib.youth_rgbd_default_levels(W, H, out))
+    return [(out[k].stride, out[k].iters) for k in range(n)]
+
+
+def decimate_device(d_depth, d_gray, n: int, W: int, H: int, stride: int, d_depth_out,
+                    d_gray_out, device: int = 0, stream: int = 0) -> None:
+    """youth_rgbd_decimate_device on device pointers (ints): [n][H][W] int16 /
+    uint8 -> [n][H_s][W_s]; asynchronous on ``stream``."""
+    lib = load_library()
+    _check(lib, lib.youth_rgbd_decimate_device(device, d_depth or None, d_gray or None, n, W, H,
+                                               stride, d_depth_out or None, d_gray_out or None,
+                                               stream or None))
 
 
 class PinnedColor:
@@ -221,6 +271,34 @@ class RgbdContext:
         out = np.zeros((n, iters, 4), np.float64)
         _check(self._lib, self._lib.youth_rgbd_get_stats(self._ctx, n, iters,
                                                          out.ctypes.data_as(POINTER(c_double))))
+        return out
+
+    # ---- level schedule (DESIGN.md §16) ----
+    def set_levels(self, levels) -> None:
+        """[(stride, iters), ...], coarse to fine; empty or None: off."""
+        arr, n = level_array(levels)
+        _check(self._lib, self._lib.youth_rgbd_set_levels(self._ctx, arr, n))
+
+    def levels(self) -> list[tuple[int, int]]:
+        out = (RgbdLevel * MAX_LEVELS)()
+        n = _check(self._lib, self._lib.youth_rgbd_get_levels(self._ctx, out, MAX_LEVELS))
+        return [(out[k].stride, out[k].iters) for k in range(n)]
+
+    def level_poses(self, level: int, n: int):
+        """-> (T64 [n,4,4], status [n]) of one level of the last scheduled align."""
+        T64 = np.zeros((n, 4, 4), np.float64)
+        st = np.zeros(n, np.int32)
+        _check(self._lib, self._lib.youth_rgbd_get_level_poses(
+            self._ctx, level, n, T64.ctypes.data_as(POINTER(c_double)),
+            st.ctypes.data_as(POINTER(c_int32))))
+        T64[:, 3, :] = (0.0, 0.0, 0.0, 1.0)
+        return T64, st
+
+    def level_stats(self, level: int, n: int, iters: int):
+        """-> [n, iters, 4] of one level, as ``stats``."""
+        out = np.zeros((n, iters, 4), np.float64)
+        _check(self._lib, self._lib.youth_rgbd_get_level_stats(
+            self._ctx, level, n, iters, out.ctypes.data_as(POINTER(c_double))))
         return out
 
     # ---- host entry points (numpy frames) ----

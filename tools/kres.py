@@ -34,5 +34,6 @@ for name, r in rows.items():
     if flt in name:
         print(f"{name:45s} VGPR {r.get('VGPRs','?'):>4s} AGPR {r.get('AGPRs','?'):>3s} "
               f"SGPR {r.get('SGPRs','?'):>4s} spillV {r.get('VGPRs Spill','?'):>4s} "
-              f"spillS {r.get('SGPRs Spill','?'):>4s} LDS {r.get('LDS Size','?'):>6s} "
+              f"spillS {r.get('SGPRs Spill','?'):>4s} scratch {r.get('ScratchSize','?'):>4s} "
+              f"LDS {r.get('LDS Size','?'):>6s} "
               f"occ {r.get('Occupancy','?')}")

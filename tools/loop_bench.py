@@ -31,9 +31,16 @@ numbers, run by hand (not part of bench.py), at 640x480:
                 against the map integrated with the ground-truth poses, and the
                 time of the re-integration
 
+With --levels SPEC (`auto`, or stride:iterations items such as 8:10,1:10 ending
+at stride 1) parts (2) and (3) run twice in the same process,
+without a schedule and with the closer verifying through that one, and report
+both ("none" and "levels"; in (3) the tracking is shared, the rows with the
+schedule are named depth+levels and rgbd+levels).
+
 The last line is one JSON object.
-usage: python tools/loop_bench.py [kernels] [gates] [c5] [c5map] [dump=DIR]   (default: the
-first three; dump=DIR also writes every verified pair and every loop edge as JSON files into DIR)"""
+usage: python tools/loop_bench.py [kernels] [gates] [c5] [c5map] [dump=DIR] [--levels SPEC]
+(default: the first three; dump=DIR also writes every verified pair and every loop edge as
+JSON files into DIR)"""
 import json
 import os
 import sys
@@ -113,7 +120,7 @@ def kernel_times(rounds=3, reps=5):
 
 
 # ---------------------------------------------------------------------- gates --
-def gate_table(flags, name, step=10, n_kf=100):
+def gate_table(flags, name, step=10, n_kf=100, levels=None):
     frames = [k * step for k in range(n_kf)]
     fr, X, rgb = [], [], []
     for f in frames:
@@ -121,7 +128,10 @@ def gate_table(flags, name, step=10, n_kf=100):
         fr.append(a[0]), X.append(T[0]), rgb.append(c[0])
     rows = []
     with youth_loop.LoopCloser(W, H, 17, min_gap=1, max_candidates=16, max_cell_dist=65535) as lc:
+        lc.set_levels(levels)
         for q in range(2, n_kf):
+            if q % 10 == 0:
+                print(f"gates, {name}: keyframe {q} of {n_kf}", file=sys.stderr, flush=True)
             for c0 in range(0, q - 1, 16):             # candidates 0 .. q - 2, 16 at a time
                 ks = list(range(c0, min(c0 + 16, q - 1)))
                 lc.clear()
@@ -163,6 +173,10 @@ def gate_table(flags, name, step=10, n_kf=100):
         "fb_mm": {"true_max": span(true, "fb_mm", max), "wrong_min": span(wrong, "fb_mm", min)},
         "accepted": len(acc), "accepted_true": sum(1 for r in acc if r in true),
         "accepted_wrong": sum(1 for r in acc if r in wrong),
+        "accepted_not_true": [dict(k=r["k"], q=r["q"], err=[round(v, 4) for v in r["err"]],
+                                   overlap=round(r["overlap"], 3), rms=round(r["rms"], 3),
+                                   fb_deg=round(r["fb_deg"], 4), fb_mm=round(r["fb_mm"], 3))
+                              for r in acc if r not in true],
         "accepted_error_max_deg_mm": [span([dict(v=r["err"][0]) for r in acc], "v", max),
                                       span([dict(v=r["err"][1]) for r in acc], "v", max)],
     }
@@ -191,7 +205,7 @@ def track_rgbd(fr, rgb):
     return np.array(traj)
 
 
-def close_trajectory(fr, rgb, T):
+def close_trajectory(fr, rgb, T, levels=None):
     """Keyframes as the drop-in picks them, stored and closed in order, the pose
     graph optimised and the trajectory re-hung: (keyframes, loop edges, close ms
     per keyframe, optimise ms, cost before and after, corrected trajectory)."""
@@ -204,6 +218,7 @@ def close_trajectory(fr, rgb, T):
     kf = kf[:youth_loop.MAX_KEYFRAMES]
     t_close = []
     with youth_loop.LoopCloser(W, H, max(2, len(kf))) as lc:
+        lc.set_levels(levels)
         for i, f in enumerate(kf):
             lc.add_keyframe(fr[f], rgb[f], T[f], tag=f)
             t0 = time.perf_counter()
@@ -218,7 +233,7 @@ def close_trajectory(fr, rgb, T):
     return kf, loops, t_close, t_opt, (c0, c1), youth_loop.interpolate(T, kf, T[kf], Xo)
 
 
-def c5(n=1000):
+def c5(n=1000, levels=None):
     fr, X, rgb = youth_synth.sequence_rgb(0, n, W, H)
     gt = np.array([np.linalg.inv(X[0]) @ X[k] for k in range(n)])
     trajs = {}
@@ -232,8 +247,11 @@ def c5(n=1000):
     trajs["depth"] = np.array(traj)
     trajs["rgbd"] = track_rgbd(fr, rgb)
     out = {}
-    for name, T in trajs.items():
-        kf, loops, t_close, t_opt, (c0, c1), closed = close_trajectory(fr, rgb, T)
+    runs = [(name, T, None) for name, T in trajs.items()]
+    if levels:
+        runs += [(name + "+levels", T, levels) for name, T in trajs.items()]
+    for name, T, lv in runs:
+        kf, loops, t_close, t_opt, (c0, c1), closed = close_trajectory(fr, rgb, T, lv)
         edge_err = [pose_error(e["Z"], np.linalg.inv(gt[kf[e["i"]]]) @ gt[kf[e["j"]]]) for e in loops]
         res = {"keyframes": len(kf), "loop_edges": int(loops.shape[0]),
                "loop_edge_error_max_deg_mm": [round(max(e[0] for e in edge_err), 4),
@@ -329,6 +347,11 @@ DUMP = None   # dump=DIR: every verified pair and every loop edge as JSON files 
 def main():
     global DUMP
     args = sys.argv[1:]
+    levels = None
+    if "--levels" in args:
+        k = args.index("--levels")
+        levels = youth_rgbd.parse_levels(args[k + 1], W, H)
+        del args[k:k + 2]
     for a in args:
         if a.startswith("dump="):
             DUMP = a[5:]
@@ -337,11 +360,15 @@ def main():
     res = {"size": [W, H], "params": youth_loop.default_params().as_dict()}
     if "kernels" in parts:
         res["kernels"] = kernel_times()
+    if levels:
+        res["levels"] = [list(l) for l in levels]
     if "gates" in parts:
-        res["gates"] = {"default_noise": gate_table(youth_synth.DEFAULT_FLAGS, "DEFAULT_FLAGS"),
-                        "survey_noise": gate_table(youth_synth.SURVEY_FLAGS, "SURVEY_FLAGS")}
+        def both(lv, tag):
+            return {"default_noise": gate_table(youth_synth.DEFAULT_FLAGS, "DEFAULT_FLAGS" + tag, levels=lv),
+                    "survey_noise": gate_table(youth_synth.SURVEY_FLAGS, "SURVEY_FLAGS" + tag, levels=lv)}
+        res["gates"] = {"none": both(None, ""), "levels": both(levels, "_levels")} if levels else both(None, "")
     if "c5" in parts:
-        res["c5"] = c5()
+        res["c5"] = c5(levels=levels)
     if "c5map" in parts:
         res["c5map"] = c5map()
     print(json.dumps(res))

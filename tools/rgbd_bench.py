@@ -18,8 +18,14 @@ alternating within every round:
                 raw and at SURVEY §8d noise with every frame through
                 youth_depth_filter_device
 
+With --levels SPEC (`auto`, or stride:iterations items such as 8:10,1:10;
+DESIGN.md §16) part (1) also times the same align on a context with that level
+schedule (rgbd_levels) and k_rgbd_decimate alone at the schedule's first
+stride (per frame; a scheduled pair call decimates two frames per pair), in
+the same rounds, and part (2) is left out.
+
 The last line is one JSON object.
-usage: python tools/rgbd_bench.py [rounds] [reps]"""
+usage: python tools/rgbd_bench.py [rounds] [reps] [--levels SPEC]"""
 import json
 import os
 import sys
@@ -45,7 +51,7 @@ def stats(v):
             "max": round(float(np.max(v)), 3)}
 
 
-def rate(rounds, reps):
+def rate(rounds, reps, levels=None):
     src, dst, _, srgb, drgb = youth_synth.pairs_rgb(0, 8, W, H)
     sg, dg = youth_synth.luma(srgb), youth_synth.luma(drgb)
     s = torch.cuda.Stream()
@@ -72,6 +78,20 @@ def rate(rounds, reps):
             "rgbd_prep": lambda: rgbd.prep_device(d[3], 1, n, None, words, stream=s.cuda_stream),
         }
         words = torch.empty((n, H * W), dtype=torch.int32, device="cuda")
+        ctxs = [rgbd, rgbd0, icp_iter, icp]
+        if levels:
+            rgbd_lv = youth_rgbd.RgbdContext(W, H, max(n, 2))
+            rgbd_lv.set_levels(levels)
+            ctxs.append(rgbd_lv)
+            s0 = levels[0][0]
+            lo = [torch.empty((n, (H + s0 - 1) // s0, (W + s0 - 1) // s0), dtype=dt, device="cuda")
+                  for dt in (torch.int16, torch.uint8)]
+            run["rgbd_levels"] = lambda: rgbd_lv.align_pairs_device(d[0], d[1], d[2], d[3], n,
+                                                                    stream=s.cuda_stream)
+            if s0 > 1:
+                run["decimate"] = lambda: youth_rgbd.decimate_device(
+                    d[0].data_ptr(), d[1].data_ptr(), n, W, H, s0, lo[0].data_ptr(), lo[1].data_ptr(),
+                    stream=s.cuda_stream)
         calls = max(1, 32 // n)
         t = {k: [] for k in run}
         for r in range(rounds + 1):                    # round 0 warms up
@@ -99,11 +119,14 @@ def rate(rounds, reps):
         res["k_rgbd_reduce_us_per_pair"] = round(k_us, 3)
         res["k_rgbd_reduce_fraction_of_8TBs"] = round(
             BYTES_PER_PX_ITER * W * H / (k_us * 1e-6) / HBM_BYTES_PER_S, 4)
+        if levels:
+            res["levels"] = [list(l) for l in levels]
+            res["rgbd_levels_over_rgbd"] = round(res["rgbd_levels"]["median"] / us, 3)
         out[str(n)] = res
         print(f"{n:4d} pairs: {res}", flush=True)
-        for c in (rgbd, rgbd0, icp_iter, icp):
+        for c in ctxs:
             c.close()
-        del d, words
+        del d, words, run
     return out
 
 
@@ -145,10 +168,18 @@ def pose_error(T, T_gt):
 
 
 def main():
-    rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 3
-    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+    args = sys.argv[1:]
+    levels = None
+    if "--levels" in args:
+        k = args.index("--levels")
+        levels = youth_rgbd.parse_levels(args[k + 1], W, H)
+        del args[k:k + 2]
+    rounds = int(args[0]) if len(args) > 0 else 3
+    reps = int(args[1]) if len(args) > 1 else 3
     res = {"size": [W, H], "params": list(youth_rgbd.default_params()),
-           "us_per_align": rate(rounds, reps), "accuracy_deg_mm": accuracy()}
+           "us_per_align": rate(rounds, reps, levels)}
+    if not levels:
+        res["accuracy_deg_mm"] = accuracy()
     print(json.dumps(res))
     return 0
 
