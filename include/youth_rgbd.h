@@ -136,9 +136,10 @@ int youth_rgbd_default_levels(int W, int H, youth_rgbd_level out[YOUTH_RGBD_MAX_
  * frame prepped once per level, no host synchronisation between levels) and
  * params.iters is not used; youth_rgbd_get_poses and youth_rgbd_get_stats
  * report the last level, the former with the OR status.  The streaming
- * tracker does not run schedules: youth_rgbd_track_submit is YOUTH_EINVAL
- * while one is set, and this call while frames are pending.  YOUTH_EINVAL
- * leaves the schedule as it was.  Allocates one workspace per coarse level. */
+ * tracker runs a schedule of its own (youth_rgbd_track_set_levels below), not
+ * this one: youth_rgbd_track_submit is YOUTH_EINVAL while this one is set, and
+ * this call while frames are pending.  YOUTH_EINVAL leaves the schedule as it
+ * was.  Allocates one workspace per coarse level. */
 int youth_rgbd_set_levels(youth_rgbd_ctx* ctx, const youth_rgbd_level* levels, int n);
 
 /* At most cap levels into out (nullable with cap 0); returns their number. */
@@ -205,6 +206,25 @@ int youth_rgbd_track_set_batch(youth_rgbd_ctx* ctx, int b);
 /* Filter every ingested depth frame once (youth_filter.h) before anything else
  * reads it; NULL (the default) switches it off.  No frame pending. */
 int youth_rgbd_track_set_depth_filter(youth_rgbd_ctx* ctx, const youth_filter_params* P);
+
+/* The streaming tracker's own schedule (n = 0: off, the default).  Rules of
+ * youth_rgbd_set_levels, and the last level has stride 1.  With one set every
+ * tracked pair is the scheduled align of that pair from the identity: level l
+ * on the plainly decimated frames (with the depth filter on: of the filtered
+ * frame), from level l - 1's fp64 pose read on the device; params.iters is not
+ * used; youth_rgbd_track_collect returns the last level's pose and the OR of
+ * all levels' status words.  No frame pending.  The next frame starts a new
+ * sequence.  YOUTH_EINVAL leaves it as it was.  Allocates one workspace per
+ * coarse level; youth_rgbd_track_set_batch keeps the schedule. */
+int youth_rgbd_track_set_levels(youth_rgbd_ctx* ctx, const youth_rgbd_level* levels, int n);
+
+/* At most cap levels into out (nullable with cap 0); returns their number. */
+int youth_rgbd_track_get_levels(const youth_rgbd_ctx* ctx, youth_rgbd_level* out, int cap);
+
+/* Of the frame youth_rgbd_track_collect returned last: every level's final
+ * pose T64 [n_levels][16] and own status word [n_levels] (each nullable).
+ * Returns n_levels, 0 if that frame had no reference or no schedule is set. */
+int youth_rgbd_track_last_levels(youth_rgbd_ctx* ctx, double* T64, int32_t* status);
 
 /* 1 <= n_frames <= b frames, asynchronous; frame i is aligned to frame i - 1,
  * the first to the last frame submitted before.  At most two submissions may be

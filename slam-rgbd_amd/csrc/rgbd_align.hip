@@ -612,6 +612,14 @@ struct youth_rgbd_ctx {
         int n = 0;
         Level at[YOUTH_RGBD_MAX_LEVELS];
     } sched;
+    // the streaming tracker's own schedule (youth_rgbd_track_set_levels): the
+    // same workspaces, without the decimated frames: a coarse level's banks
+    // and slots are its context's own, at the parent's bank and slot indices
+    Schedule trk_sched;
+    // of the frame youth_rgbd_track_collect returned last
+    int last_lv_n = 0;
+    double last_lv_T[YOUTH_RGBD_MAX_LEVELS][16] = {};
+    int32_t last_lv_st[YOUTH_RGBD_MAX_LEVELS] = {};
 
     // streaming tracker (youth_rgbd_track_*).  Depth and
     // intensity: two banks of trk_b frame slots, a submission's frames in the
@@ -633,8 +641,11 @@ struct youth_rgbd_ctx {
     struct Sub {
         int m = 0, next = 0;      // frames of the submission, the next to collect
         int first_has_ref = 0;
-        double* res = nullptr;    // pinned: [trk_b][16] poses, then [trk_b] status words
-        int res_cap = 0;          // frames `res` holds
+        double* res = nullptr;    // pinned: [res_lv][res_cap][16] poses, then [res_lv][res_cap]
+                                  // status words; without a schedule one level
+        int res_cap = 0;          // frames `res` holds per level
+        int res_lv = 0;           // levels `res` holds
+        int n_lv = 0;             // levels of the submission (0: no schedule)
         int16_t* stage_d = nullptr;  // pinned staging of pageable frames [stage_cap][N]
         uint8_t* stage_c = nullptr;  //                                   [stage_cap][N][3]
         int stage_cap = 0;
@@ -867,7 +878,12 @@ void youth_rgbd_destroy(youth_rgbd_ctx* r)
 {
     if (!r) return;
     if (r->icp) (void)hipSetDevice(r->icp->device);
+    if (r->icp && r->trk_sched.n > 0) {  // its levels ran on this context's streams
+        (void)hipStreamSynchronize(r->icp->stream);
+        if (r->icp->xfer) (void)hipStreamSynchronize(r->icp->xfer);
+    }
     rgbd_drop_schedule(r->sched, r);
+    rgbd_drop_schedule(r->trk_sched, r);
     if (r->icp) {
         (void)hipSetDevice(r->icp->device);
         if (r->last_stream) (void)hipStreamSynchronize(r->last_stream);
@@ -1093,9 +1109,11 @@ int youth_rgbd_default_levels(int W, int H, youth_rgbd_level out[YOUTH_RGBD_MAX_
     return n;
 }
 
-int youth_rgbd_set_levels(youth_rgbd_ctx* r, const youth_rgbd_level* levels, int n)
+// The rules of a schedule for context r (`who` speaks); full_last: the last
+// level has stride 1 (the tracker's).
+static int rgbd_check_levels(const char* who, const youth_rgbd_ctx* r, const youth_rgbd_level* levels,
+                             int n, bool full_last)
 {
-    static const char* who = "youth_rgbd_set_levels";
     if (!r) return g_icp_err.set(YOUTH_EINVAL, "%s: null context", who);
     if (n < 0 || n > YOUTH_RGBD_MAX_LEVELS)
         return g_icp_err.set(YOUTH_EINVAL, "%s: %d levels (need 0 .. %d)", who, n,
@@ -1104,7 +1122,7 @@ int youth_rgbd_set_levels(youth_rgbd_ctx* r, const youth_rgbd_level* levels, int
     if (r->sub_n > 0)
         return g_icp_err.set(YOUTH_EINVAL, "%s: %d frames pending (collect them first)", who,
                              rgbd_track_pending(r));
-    youth_icp_ctx* c = r->icp;
+    const youth_icp_ctx* c = r->icp;
     for (int l = 0; l < n; ++l) {
         const int s = levels[l].stride;
         if (!rgbd_stride_ok(s))
@@ -1120,10 +1138,21 @@ int youth_rgbd_set_levels(youth_rgbd_ctx* r, const youth_rgbd_level* levels, int
             return g_icp_err.set(YOUTH_EINVAL, "%s: level %d of stride %d is %dx%d (need >= 3x3)", who,
                                  l, s, (c->W + s - 1) / s, (c->H + s - 1) / s);
     }
-    int rc = bind_device(c);
-    if (rc) return rc;
-    // the new schedule beside the old one, which stays if anything fails
-    youth_rgbd_ctx::Schedule next;
+    if (full_last && n > 0 && levels[n - 1].stride != 1)
+        return g_icp_err.set(YOUTH_EINVAL,
+                             "%s: the last level has stride %d (the tracker's schedule ends at "
+                             "stride 1)",
+                             who, levels[n - 1].stride);
+    return YOUTH_OK;
+}
+
+// A checked schedule's workspaces into `next` (emptied again on failure): per
+// coarse level a context of W_s x H_s under K_s for r's max_frames and, with
+// `frames`, room for the decimated frames of a call.
+static int rgbd_build_schedule(const char* who, youth_rgbd_ctx* r, const youth_rgbd_level* levels,
+                               int n, bool frames, youth_rgbd_ctx::Schedule& next)
+{
+    youth_icp_ctx* c = r->icp;
     for (int l = 0; l < n; ++l) {
         youth_rgbd_ctx::Level& L = next.at[l];
         const int s = levels[l].stride;
@@ -1140,6 +1169,7 @@ int youth_rgbd_set_levels(youth_rgbd_ctx* r, const youth_rgbd_level* levels, int
             rgbd_drop_schedule(next, r);
             return g_icp_err.code();  // youth_rgbd_create's text stands
         }
+        if (!frames) continue;
         L.off = ((size_t)r->frames * Ws * Hs + 15) / 16 * 16;
         hipError_t e = hipMalloc(&L.depth, 2 * L.off * sizeof(int16_t));
         if (e == hipSuccess) e = hipMalloc(&L.gray, 2 * L.off);
@@ -1149,10 +1179,24 @@ int youth_rgbd_set_levels(youth_rgbd_ctx* r, const youth_rgbd_level* levels, int
                                  "%s: hipMalloc: %s", who, hipGetErrorString(e));
         }
     }
+    next.n = n;
+    return YOUTH_OK;
+}
+
+int youth_rgbd_set_levels(youth_rgbd_ctx* r, const youth_rgbd_level* levels, int n)
+{
+    static const char* who = "youth_rgbd_set_levels";
+    int rc = rgbd_check_levels(who, r, levels, n, false);
+    if (rc) return rc;
+    rc = bind_device(r->icp);
+    if (rc) return rc;
+    // the new schedule beside the old one, which stays if anything fails
+    youth_rgbd_ctx::Schedule next;
+    rc = rgbd_build_schedule(who, r, levels, n, true, next);
+    if (rc) return rc;
     // nothing of the old schedule is in flight once its streams are idle
     if (r->last_stream) HIP_TRY(hipStreamSynchronize(r->last_stream));
     rgbd_drop_schedule(r->sched, r);
-    next.n = n;
     r->sched = next;
     return YOUTH_OK;
 }
@@ -1280,8 +1324,16 @@ int youth_rgbd_track_host_sequence(youth_rgbd_ctx* r, const int16_t* depth, cons
 //                    trk_b pairs; poses and statuses to the submission's
 //                    pinned result slot; event
 //
+// With the tracker's own level schedule (trk_sched) the
+// transfer stream also decimates the bank's (filtered) frames into every
+// coarse level's bank, one k_rgbd_decimate launch, and the context stream runs
+// its part level by level, coarse to fine, each level on its own workspace at
+// the same bank and slot indices, from the poses the level before it left on
+// the device; every level's poses and statuses go to the result slot.
+//
 // Every frame is prepped once, as a new frame; what a pair computes depends on
-// its two frames and on trk_b alone, not on the submission it travelled in.
+// its two frames, on trk_b and on the schedule, not on the submission it
+// travelled in.
 // k_rgbd_reduce holds no wait (its last arriver sums, handoff_publish /
 // handoff_sum), so no status here carries YOUTH_STATUS_TIMEOUT.
 
@@ -1384,13 +1436,15 @@ static int rgbd_ensure_track(youth_rgbd_ctx* r)
     for (auto& q : r->sub) {
         if (!q.h2d) HIP_TRY(hipEventCreateWithFlags(&q.h2d, hipEventDisableTiming));
         if (!q.done) HIP_TRY(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
-        if (q.res_cap < r->trk_b) {
+        const int n_lv = std::max(1, r->trk_sched.n);
+        if (q.res_cap < r->trk_b || q.res_lv < n_lv) {
             if (q.res) (void)hipHostFree(q.res);
             q.res = nullptr;
-            q.res_cap = 0;
-            HIP_TRY(hipHostMalloc((void**)&q.res, (size_t)r->trk_b * 17 * sizeof(double),
+            q.res_cap = q.res_lv = 0;
+            HIP_TRY(hipHostMalloc((void**)&q.res, (size_t)n_lv * r->trk_b * 17 * sizeof(double),
                                   hipHostMallocDefault));
             q.res_cap = r->trk_b;
+            q.res_lv = n_lv;
         }
     }
     return YOUTH_OK;
@@ -1410,6 +1464,47 @@ static hipError_t rgbd_track_wait(hipEvent_t ev)
     return hipEventSynchronize(ev);
 }
 
+// One level's share of a submission on the context stream: Lr the level's
+// workspace (the context itself at stride 1), whose banks hold the m new
+// frames; dTi the level's initial poses on the device (null: the identity).
+static int rgbd_track_level(youth_rgbd_ctx* r, youth_rgbd_ctx* Lr, hipStream_t s, int m, int iters,
+                            const double* dTi)
+{
+    youth_icp_ctx* c = Lr->icp;
+    const size_t N = (size_t)c->N;
+    const int d0 = r->trk_bank * r->trk_b;  // first depth / intensity slot of the bank
+    const int ref = r->trk_ref;
+    if (ref > 0) {
+        HIP_TRY(hipMemcpyAsync(c->d_rec, c->d_rec + (size_t)ref * c->P, c->P * sizeof(float4),
+                               hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(Lr->d_photo, Lr->d_photo + (size_t)ref * N, N * sizeof(unsigned),
+                               hipMemcpyDeviceToDevice, s));
+    }
+    int rc = launch_prep(c, s, c->d_depth + (size_t)d0 * N, m, 1, false);
+    if (rc) return rc;
+    rc = rgbd_launch_prep(s, Lr->d_gray + (size_t)d0 * N, 1, m, c->W, c->H, nullptr, Lr->d_photo + N);
+    if (rc) return rc;
+    // without a reference the first frame is prepped only
+    const int pairs = ref >= 0 ? m : m - 1;
+    if (pairs > 0) {
+        rc = rgbd_ensure_stats(Lr, iters > 0 ? iters : 1);
+        if (rc) return rc;
+        rc = launch_init(c, s, dTi, pairs, iters, false);
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(c->d_arrivals, 0, (size_t)pairs * sizeof(unsigned), s));
+        const PairMap pm{ref >= 0 ? d0 : d0 + 1, ref >= 0 ? 0 : 1};
+        for (int it = 0; it < iters; ++it) {
+            rc = rgbd_launch_reduce(Lr, s, c->d_depth, Lr->d_gray, pm, pairs, it, iters, nullptr,
+                                    r->trk_b);
+            if (rc) return rc;
+        }
+        Lr->last_pairs = pairs;
+        Lr->last_iters = iters;
+    }
+    Lr->last_stream = s;
+    return YOUTH_OK;
+}
+
 static int rgbd_track_enqueue(youth_rgbd_ctx* r, youth_rgbd_ctx::Sub& q,
                               const int16_t* const* depth, const uint8_t* const* rgb, int m)
 {
@@ -1419,6 +1514,7 @@ static int rgbd_track_enqueue(youth_rgbd_ctx* r, youth_rgbd_ctx::Sub& q,
     const int d0 = r->trk_bank * r->trk_b;  // first depth / intensity slot of the bank
     int16_t* const dbank = c->d_depth + (size_t)d0 * N;
     uint8_t* const gbank = r->d_gray + (size_t)d0 * N;
+    const youth_rgbd_ctx::Schedule& S = r->trk_sched;
     // the bank's last reader is the submission that used this entry before
     if (q.m > 0) HIP_TRY(hipStreamWaitEvent(xs, q.done, 0));
     int rc = rgbd_launch_pull(r, xs, depth, rgb, m, r->flt_on ? r->d_raw : dbank, gbank, nullptr);
@@ -1427,40 +1523,40 @@ static int rgbd_track_enqueue(youth_rgbd_ctx* r, youth_rgbd_ctx::Sub& q,
         rc = youth_depth_filter_device(c->device, r->d_raw, dbank, m, c->W, c->H, &r->flt, xs);
         if (rc) return g_icp_err.set(rc, "depth filter: %s", youth_depth_filter_last_error());
     }
+    // every coarse level's frames in one decimation of the bank's (filtered)
+    // frames, into the same slots of the level's own banks
+    DecimJob job{};
+    job.depth[0] = dbank, job.gray[0] = gbank, job.n[0] = m;
+    for (int l = 0; l < S.n; ++l) {
+        const youth_rgbd_ctx::Level& L = S.at[l];
+        if (L.ctx == r) continue;
+        const size_t Ns = (size_t)L.ctx->icp->N;
+        const int k = job.n_lv++;
+        job.stride[k] = L.lv.stride;
+        job.dout[0][k] = L.ctx->icp->d_depth + (size_t)d0 * Ns;
+        job.gout[0][k] = L.ctx->d_gray + (size_t)d0 * Ns;
+    }
+    rc = rgbd_launch_decimate(xs, job, c->W, c->H);
+    if (rc) return rc;
     HIP_TRY(hipEventRecord(q.h2d, xs));
     HIP_TRY(hipStreamWaitEvent(s, q.h2d, 0));
-    const int ref = r->trk_ref;
-    if (ref > 0) {
-        HIP_TRY(hipMemcpyAsync(c->d_rec, c->d_rec + (size_t)ref * c->P, c->P * sizeof(float4),
-                               hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(r->d_photo, r->d_photo + (size_t)ref * N, N * sizeof(unsigned),
-                               hipMemcpyDeviceToDevice, s));
-    }
-    rc = launch_prep(c, s, dbank, m, 1, false);
-    if (rc) return rc;
-    rc = rgbd_launch_prep(s, gbank, 1, m, c->W, c->H, nullptr, r->d_photo + N);
-    if (rc) return rc;
-    // without a reference the first frame is prepped only
-    const int pairs = ref >= 0 ? m : m - 1;
-    if (pairs > 0) {
-        const int iters = r->prm.iters;
-        rc = rgbd_ensure_stats(r, iters > 0 ? iters : 1);
+    const int pairs = r->trk_ref >= 0 ? m : m - 1;
+    const int n_lv = std::max(1, S.n);
+    int32_t* const res_st = reinterpret_cast<int32_t*>(q.res + (size_t)q.res_lv * q.res_cap * 16);
+    const double* dTi = nullptr;
+    for (int l = 0; l < n_lv; ++l) {
+        youth_rgbd_ctx* Lr = S.n > 0 ? S.at[l].ctx : r;
+        const int iters = S.n > 0 ? S.at[l].lv.iters : r->prm.iters;
+        rc = rgbd_track_level(r, Lr, s, m, iters, dTi);
         if (rc) return rc;
-        rc = launch_init(c, s, nullptr, pairs, iters, false);
-        if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(c->d_arrivals, 0, (size_t)pairs * sizeof(unsigned), s));
-        const PairMap pm{ref >= 0 ? d0 : d0 + 1, ref >= 0 ? 0 : 1};
-        for (int it = 0; it < iters; ++it) {
-            rc = rgbd_launch_reduce(r, s, c->d_depth, r->d_gray, pm, pairs, it, iters, nullptr,
-                                    r->trk_b);
-            if (rc) return rc;
-        }
-        HIP_TRY(hipMemcpyAsync(q.res, c->d_T64, (size_t)pairs * 16 * sizeof(double),
-                               hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(q.res + (size_t)q.res_cap * 16, c->d_status,
+        youth_icp_ctx* lc = Lr->icp;
+        dTi = lc->d_T64;
+        if (pairs <= 0) continue;
+        // every level's poses and status words to the pinned result slot
+        HIP_TRY(hipMemcpyAsync(q.res + (size_t)l * q.res_cap * 16, lc->d_T64,
+                               (size_t)pairs * 16 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(res_st + (size_t)l * q.res_cap, lc->d_status,
                                (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        r->last_pairs = pairs;
-        r->last_iters = iters;
     }
     r->last_stream = s;
     HIP_TRY(hipEventRecord(q.done, s));
@@ -1511,8 +1607,9 @@ int youth_rgbd_track_submit(youth_rgbd_ctx* r, const int16_t* const* depth,
     if (!r) return g_icp_err.set(YOUTH_EINVAL, "%s: null context", who);
     if (r->sched.n > 0)
         return g_icp_err.set(YOUTH_EINVAL,
-                             "%s: the context has a level schedule, which the streaming tracker "
-                             "does not run (youth_rgbd_set_levels with 0 levels switches it off)",
+                             "%s: the context has an align schedule (youth_rgbd_set_levels; 0 levels "
+                             "switch it off); the streaming tracker runs its own, "
+                             "youth_rgbd_track_set_levels",
                              who);
     int rc = rgbd_check_frames(who, depth, rgb, n_frames, r->trk_b);
     if (rc) return rc;
@@ -1547,6 +1644,7 @@ int youth_rgbd_track_submit(youth_rgbd_ctx* r, const int16_t* const* depth,
     }
     q.m = n_frames;
     q.next = 0;
+    q.n_lv = r->trk_sched.n;
     q.first_has_ref = r->trk_ref >= 0 ? 1 : 0;
     r->trk_ref = n_frames;  // the last new frame's record / word slot
     r->trk_bank ^= 1;
@@ -1572,12 +1670,24 @@ int youth_rgbd_track_collect(youth_rgbd_ctx* r, double* T_rel, int* has_ref)
     const int has = (i > 0 || q.first_has_ref) ? 1 : 0;
     if (has_ref) *has_ref = has;
     for (int k = 0; k < 16; ++k) T_rel[k] = (k % 5) == 0 ? 1.0 : 0.0;
+    r->last_lv_n = 0;
     if (!has) return 0;
     const int p = q.first_has_ref ? i : i - 1;
-    for (int k = 0; k < 12; ++k) T_rel[k] = q.res[(size_t)p * 16 + k];
-    int32_t st;
-    memcpy(&st, reinterpret_cast<const char*>(q.res + (size_t)q.res_cap * 16) + (size_t)p * sizeof(st),
-           sizeof(st));
+    const int n_lv = std::max(1, q.n_lv);
+    const int32_t* res_st = reinterpret_cast<const int32_t*>(q.res + (size_t)q.res_lv * q.res_cap * 16);
+    int32_t st = 0;  // the OR of all levels' status words
+    for (int l = 0; l < n_lv; ++l) {
+        const double* Tl = q.res + ((size_t)l * q.res_cap + p) * 16;
+        const int32_t sl = res_st[(size_t)l * q.res_cap + p];
+        st |= sl;
+        if (q.n_lv > 0) {
+            memcpy(r->last_lv_T[l], Tl, 16 * sizeof(double));
+            r->last_lv_st[l] = sl;
+        }
+        if (l == n_lv - 1)
+            for (int k = 0; k < 12; ++k) T_rel[k] = Tl[k];
+    }
+    r->last_lv_n = q.n_lv;
     return st;
 }
 
@@ -1592,6 +1702,48 @@ int youth_rgbd_track_reset(youth_rgbd_ctx* r)
                              rgbd_track_pending(r));
     r->trk_ref = -1;
     return YOUTH_OK;
+}
+
+int youth_rgbd_track_set_levels(youth_rgbd_ctx* r, const youth_rgbd_level* levels, int n)
+{
+    static const char* who = "youth_rgbd_track_set_levels";
+    int rc = rgbd_check_levels(who, r, levels, n, true);
+    if (rc) return rc;
+    rc = bind_device(r->icp);
+    if (rc) return rc;
+    // the new schedule beside the old one, which stays if anything fails
+    youth_rgbd_ctx::Schedule next;
+    rc = rgbd_build_schedule(who, r, levels, n, false, next);
+    if (rc) return rc;
+    // no frame pending: the old levels' work on this context's streams has run
+    rgbd_drop_schedule(r->trk_sched, r);
+    r->trk_sched = next;
+    r->trk_ref = -1;  // the next frame starts a new sequence, at every level
+    r->last_lv_n = 0;
+    return YOUTH_OK;
+}
+
+int youth_rgbd_track_get_levels(const youth_rgbd_ctx* r, youth_rgbd_level* out, int cap)
+{
+    if (!r || cap < 0 || (cap > 0 && !out))
+        return g_icp_err.set(YOUTH_EINVAL, "youth_rgbd_track_get_levels: %s",
+                             r ? "bad arguments" : "null context");
+    for (int l = 0; l < std::min(cap, r->trk_sched.n); ++l) out[l] = r->trk_sched.at[l].lv;
+    return r->trk_sched.n;
+}
+
+int youth_rgbd_track_last_levels(youth_rgbd_ctx* r, double* T64, int32_t* status)
+{
+    if (!r) return g_icp_err.set(YOUTH_EINVAL, "youth_rgbd_track_last_levels: null context");
+    for (int l = 0; l < r->last_lv_n; ++l) {
+        if (T64) {
+            memcpy(T64 + (size_t)l * 16, r->last_lv_T[l], 12 * sizeof(double));
+            const double row[4] = {0.0, 0.0, 0.0, 1.0};
+            memcpy(T64 + (size_t)l * 16 + 12, row, sizeof(row));
+        }
+        if (status) status[l] = r->last_lv_st[l];
+    }
+    return r->last_lv_n;
 }
 
 int youth_rgbd_pull_host(youth_rgbd_ctx* r, const int16_t* const* depth, const uint8_t* const* rgb,

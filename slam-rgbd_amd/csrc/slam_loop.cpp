@@ -21,6 +21,7 @@
 #include <mutex>
 #include <vector>
 
+#include "slam_levels.h"
 #include "slam_loop_hooks.h"
 #include "youth_loop.h"
 
@@ -31,9 +32,7 @@ bool g_on = false;             // YOUTH_SLAM_LOOP=1 and nothing has switched it 
 int g_device = 0;
 double g_kf_m = 0.10, g_kf_deg = 10.0;
 int g_min_gap = 0;             // 0: the default of youth_loop_default_params
-// YOUTH_SLAM_LOOP_LEVELS: -1 `auto` (the default schedule of the frame size), 0 none, else a list
-int g_n_levels = 0;
-youth_rgbd_level g_levels[YOUTH_RGBD_MAX_LEVELS];
+youth_slam_levels g_levels;    // YOUTH_SLAM_LOOP_LEVELS (slam_levels.h)
 youth_loop* g_lp = nullptr;    // made with the first frame, for its size
 int g_w = 0, g_h = 0;
 bool g_full = false;           // the store is full: no further keyframes
@@ -57,34 +56,6 @@ void forget()
     if (g_lp) youth_loop_clear(g_lp);
 }
 
-// "auto" or "s:n,s:n,..." (1 .. YOUTH_RGBD_MAX_LEVELS items of two non-negative
-// integers) -> g_n_levels / g_levels; false: malformed, nothing set.  The
-// schedule's own rules are youth_loop_set_levels'.
-bool parse_levels(const char* text)
-{
-    if (strcmp(text, "auto") == 0) {
-        g_n_levels = -1;
-        return true;
-    }
-    youth_rgbd_level lv[YOUTH_RGBD_MAX_LEVELS] = {};
-    int n = 0;
-    const char* p = text;
-    for (;;) {
-        int s = 0, it = 0, used = 0;
-        if (n == YOUTH_RGBD_MAX_LEVELS || sscanf(p, "%9d:%9d%n", &s, &it, &used) != 2 || s < 0 || it < 0)
-            return false;
-        for (int k = 0; k < used; ++k)
-            if (!strchr("0123456789:", p[k])) return false;
-        lv[n++] = youth_rgbd_level{s, it};
-        p += used;
-        if (*p == '\0') break;
-        if (*p++ != ',') return false;
-    }
-    memcpy(g_levels, lv, sizeof(lv));
-    g_n_levels = n;
-    return true;
-}
-
 void loop_start(int device)
 {
     std::lock_guard<std::mutex> lk(g_loop_mu);
@@ -100,9 +71,9 @@ void loop_start(int device)
     if (const char* e = getenv("YOUTH_SLAM_LOOP_KF_M")) g_kf_m = atof(e);
     if (const char* e = getenv("YOUTH_SLAM_LOOP_KF_DEG")) g_kf_deg = atof(e);
     if (const char* e = getenv("YOUTH_SLAM_LOOP_MIN_GAP")) g_min_gap = atoi(e);
-    g_n_levels = 0;
+    g_levels = youth_slam_levels{};
     if (const char* e = getenv("YOUTH_SLAM_LOOP_LEVELS"))
-        if (*e && !parse_levels(e))
+        if (*e && !youth_slam_parse_levels(e, &g_levels))
             fprintf(stderr, "youth_icp: YOUTH_SLAM_LOOP_LEVELS=%s is not `auto` or a list like 8:10,1:10; "
                             "ignored\n", e);
     fprintf(stderr, "youth_icp: loop closing on (a keyframe every %g m / %g deg)\n", g_kf_m, g_kf_deg);
@@ -160,16 +131,12 @@ void loop_frame(const int16_t* depth, const uint8_t* rgb, int w, int h, const yo
         }
         g_w = w;
         g_h = h;
-        if (g_n_levels != 0) {
+        if (g_levels.n != 0) {
             youth_rgbd_level lv[YOUTH_RGBD_MAX_LEVELS] = {};
-            int n = g_n_levels;
-            if (n < 0)
-                n = youth_rgbd_default_levels(w, h, lv);
-            else
-                memcpy(lv, g_levels, sizeof(lv));
+            const int n = g_levels.resolve(w, h, lv);
             if (youth_loop_set_levels(g_lp, lv, n) < 0) {
                 fprintf(stderr, "youth_icp: YOUTH_SLAM_LOOP_LEVELS ignored: %s\n", youth_loop_last_error());
-                g_n_levels = 0;   // logged once
+                g_levels.n = 0;   // logged once
             }
         }
     }

@@ -14,6 +14,7 @@
 
 #include <cmath>
 
+#include "slam_levels.h"
 #include "slam_rgbd_hooks.h"
 #include "youth_rgbd.h"
 
@@ -22,6 +23,7 @@ namespace {
 youth_rgbd_params g_prm;
 bool g_flt_on = false;
 youth_filter_params g_flt{8, 96};
+youth_slam_levels g_levels;    // YOUTH_SLAM_RGBD_LEVELS (slam_levels.h)
 
 void rgbd_start(void)
 {
@@ -47,6 +49,11 @@ void rgbd_start(void)
             g_flt_on = true;
         }  // else youth_icp_create has said that it is ignored
     }
+    g_levels = youth_slam_levels{};
+    if (const char* e = getenv("YOUTH_SLAM_RGBD_LEVELS"))
+        if (*e && !youth_slam_parse_levels(e, &g_levels))
+            fprintf(stderr, "youth_icp: YOUTH_SLAM_RGBD_LEVELS=%s is not `auto` or a list like 8:10,1:10; "
+                            "ignored\n", e);
 }
 
 void* rgbd_create(int device, int w, int h, int batch, const youth_intrinsics* K)
@@ -57,6 +64,16 @@ void* rgbd_create(int device, int w, int h, int batch, const youth_intrinsics* K
         (g_flt_on && youth_rgbd_track_set_depth_filter(r, &g_flt) < 0)) {
         youth_rgbd_destroy(r);  // the refusal's text stands
         return nullptr;
+    }
+    if (g_levels.n != 0) {
+        youth_rgbd_level lv[YOUTH_RGBD_MAX_LEVELS] = {};
+        const int n = g_levels.resolve(w, h, lv);
+        if (youth_rgbd_track_set_levels(r, lv, n) < 0) {
+            fprintf(stderr, "youth_icp: YOUTH_SLAM_RGBD_LEVELS=%s ignored: %s\n",
+                    getenv("YOUTH_SLAM_RGBD_LEVELS") ? getenv("YOUTH_SLAM_RGBD_LEVELS") : "",
+                    youth_rgbd_last_error());
+            g_levels.n = 0;  // logged once
+        }
     }
     return r;
 }

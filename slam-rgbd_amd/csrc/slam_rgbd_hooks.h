@@ -12,7 +12,7 @@
 #include "youth_icp.h"
 
 struct youth_slam_rgbd_hooks {
-    // initSlamModule: read YOUTH_SLAM_RGBD_LAMBDA and YOUTH_ICP_DEPTH_FILTER
+    // initSlamModule: read YOUTH_SLAM_RGBD_LAMBDA, YOUTH_ICP_DEPTH_FILTER and YOUTH_SLAM_RGBD_LEVELS
     void (*start)(void);
     // a tracker for W x H frames, `batch` frames per submission at most, two
     // submissions in flight; null on failure (last_error says why)

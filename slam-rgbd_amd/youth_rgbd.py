@@ -74,6 +74,9 @@ _SIGS = {
     "youth_rgbd_track_reset": (c_int, [c_void_p]),
     "youth_rgbd_pull_host": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_int,
                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+    "youth_rgbd_track_set_levels": (c_int, [c_void_p, POINTER(RgbdLevel), c_int]),
+    "youth_rgbd_track_get_levels": (c_int, [c_void_p, POINTER(RgbdLevel), c_int]),
+    "youth_rgbd_track_last_levels": (c_int, [c_void_p, _PD, POINTER(c_int32)]),
 }
 
 
@@ -340,6 +343,26 @@ class RgbdContext:
         """``t0=None`` switches the filter off."""
         P = None if t0 is None else ctypes.byref(youth_icp.FilterParams(t0, t2))
         _check(self._lib, self._lib.youth_rgbd_track_set_depth_filter(self._ctx, P))
+
+    def track_set_levels(self, levels) -> None:
+        """The tracker's own schedule [(stride, iters), ...], coarse to fine, the
+        last stride 1; empty or None: off."""
+        arr, n = level_array(levels)
+        _check(self._lib, self._lib.youth_rgbd_track_set_levels(self._ctx, arr, n))
+
+    def track_levels(self) -> list[tuple[int, int]]:
+        out = (RgbdLevel * MAX_LEVELS)()
+        n = _check(self._lib, self._lib.youth_rgbd_track_get_levels(self._ctx, out, MAX_LEVELS))
+        return [(out[k].stride, out[k].iters) for k in range(n)]
+
+    def track_last_levels(self):
+        """-> (T64 [n_levels,4,4], status [n_levels]) of the frame collected last
+        (n_levels 0: it had no reference, or no schedule is set)."""
+        T64 = np.zeros((MAX_LEVELS, 4, 4), np.float64)
+        st = np.zeros(MAX_LEVELS, np.int32)
+        n = _check(self._lib, self._lib.youth_rgbd_track_last_levels(
+            self._ctx, T64.ctypes.data_as(POINTER(c_double)), st.ctypes.data_as(POINTER(c_int32))))
+        return T64[:n], st[:n]
 
     def track_submit(self, depth, rgb):
         """Lists of [H][W] int16 and [H][W][3] uint8 frames, read in place: they

@@ -38,7 +38,9 @@ both ("none" and "levels"; in (3) the tracking is shared, the rows with the
 schedule are named depth+levels and rgbd+levels).
 
 The last line is one JSON object.
-usage: python tools/loop_bench.py [kernels] [gates] [c5] [c5map] [dump=DIR] [--levels SPEC]
+usage: python tools/loop_bench.py [kernels] [gates] [c5] [c5track] [c5map] [dump=DIR] [--levels SPEC]
+       [--track-levels SPEC]   (c5: a third trajectory tracked by the streaming tracker with its own
+       schedule; c5track, on request only: C5's tracking errors alone, without and with that schedule)
 (default: the first three; dump=DIR also writes every verified pair and every loop edge as
 JSON files into DIR)"""
 import json
@@ -205,6 +207,54 @@ def track_rgbd(fr, rgb):
     return np.array(traj)
 
 
+def track_rgbd_streamed(fr, rgb, track_levels):
+    """The same through the streaming tracker (b = 8, two submissions in flight)
+    with its own level schedule (youth_rgbd_track_set_levels)."""
+    n = len(fr)
+    traj = []
+    with youth_rgbd.RgbdContext(W, H, 16) as ctx:
+        ctx.track_set_batch(8)
+        ctx.track_set_levels(track_levels)
+        sizes = []
+
+        def collect():
+            for _ in range(sizes.pop(0)):
+                T, has, _ = ctx.track_collect()
+                traj.append(traj[-1] @ T if has else np.eye(4))
+
+        for s in range(0, n, 8):
+            if len(sizes) == 2:
+                collect()
+            ctx.track_submit(list(fr[s:s + 8]), list(rgb[s:s + 8]))
+            sizes.append(len(fr[s:s + 8]))
+        while sizes:
+            collect()
+    return np.array(traj)
+
+
+C5_FRAMES = (150, 200, 627, 800, 999)
+
+
+def c5track(track_levels, n=1000):
+    """C5's RGB-D tracking errors alone, without and with the tracker's schedule."""
+    fr, X, rgb = youth_synth.sequence_rgb(0, n, W, H)
+    gt = np.array([np.linalg.inv(X[0]) @ X[k] for k in range(n)])
+    out = {}
+    for name, lv in (("none", None), ("track_levels", track_levels)):
+        t0 = time.perf_counter()
+        T = track_rgbd_streamed(fr, rgb, lv)
+        dt = time.perf_counter() - t0
+        out[name] = {"levels": [list(l) for l in lv or ()], "frames_per_s": round(n / dt, 1)}
+        for f in C5_FRAMES:
+            if f < n:
+                out[name][f"frame_{f}_deg_mm"] = [round(v, 4) for v in pose_error(T[f], gt[f])]
+                if f >= 100:   # against the track from frame 100: the motion since then alone
+                    out[name][f"frame_{f}_since_100_deg_mm"] = [round(v, 4) for v in pose_error(
+                        np.linalg.inv(T[100]) @ T[f], np.linalg.inv(gt[100]) @ gt[f])]
+        print(f"C5 tracking, tracker schedule {name}: {out[name]}", flush=True)
+    return out
+
+
 def close_trajectory(fr, rgb, T, levels=None):
     """Keyframes as the drop-in picks them, stored and closed in order, the pose
     graph optimised and the trajectory re-hung: (keyframes, loop edges, close ms
@@ -233,7 +283,7 @@ def close_trajectory(fr, rgb, T, levels=None):
     return kf, loops, t_close, t_opt, (c0, c1), youth_loop.interpolate(T, kf, T[kf], Xo)
 
 
-def c5(n=1000, levels=None):
+def c5(n=1000, levels=None, track_levels=None):
     fr, X, rgb = youth_synth.sequence_rgb(0, n, W, H)
     gt = np.array([np.linalg.inv(X[0]) @ X[k] for k in range(n)])
     trajs = {}
@@ -246,6 +296,8 @@ def c5(n=1000, levels=None):
         traj.append(traj[-1] @ T_rel[k])
     trajs["depth"] = np.array(traj)
     trajs["rgbd"] = track_rgbd(fr, rgb)
+    if track_levels:
+        trajs["rgbd+track_levels"] = track_rgbd_streamed(fr, rgb, track_levels)
     out = {}
     runs = [(name, T, None) for name, T in trajs.items()]
     if levels:
@@ -258,7 +310,7 @@ def c5(n=1000, levels=None):
                                               round(max(e[1] for e in edge_err), 3)] if edge_err else None,
                "close_ms_per_keyframe": stats(t_close), "optimize_ms": round(t_opt, 2),
                "cost": [c0, c1]}
-        for f in (627, 800, 999):
+        for f in C5_FRAMES:
             if f < n:
                 res[f"frame_{f}_before_deg_mm"] = [round(v, 4) for v in pose_error(T[f], gt[f])]
                 res[f"frame_{f}_after_deg_mm"] = [round(v, 4) for v in pose_error(closed[f], gt[f])]
@@ -352,6 +404,11 @@ def main():
         k = args.index("--levels")
         levels = youth_rgbd.parse_levels(args[k + 1], W, H)
         del args[k:k + 2]
+    track_levels = None
+    if "--track-levels" in args:
+        k = args.index("--track-levels")
+        track_levels = youth_rgbd.parse_levels(args[k + 1], W, H)
+        del args[k:k + 2]
     for a in args:
         if a.startswith("dump="):
             DUMP = a[5:]
@@ -368,7 +425,9 @@ def main():
                     "survey_noise": gate_table(youth_synth.SURVEY_FLAGS, "SURVEY_FLAGS" + tag, levels=lv)}
         res["gates"] = {"none": both(None, ""), "levels": both(levels, "_levels")} if levels else both(None, "")
     if "c5" in parts:
-        res["c5"] = c5(levels=levels)
+        res["c5"] = c5(levels=levels, track_levels=track_levels)
+    if "c5track" in parts:
+        res["c5track"] = c5track(track_levels or youth_rgbd.default_levels(W, H))
     if "c5map" in parts:
         res["c5map"] = c5map()
     print(json.dumps(res))

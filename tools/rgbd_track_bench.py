@@ -14,8 +14,15 @@ iterations, the variants alternating within every round:
                 to pose), with YOUTH_SLAM_RGBD=1 and in default mode; one child
                 process per mode (the module reads its environment at init)
 
+With --levels auto|LIST (the tracker's own schedule, youth_rgbd_track_set_levels):
+
+  (a) ingest    also k_rgbd_pull followed by k_rgbd_decimate for the schedule's
+                coarse strides on the same stream, the scheduled tracker's ingest
+  (b) stream    also submit_b1 / submit_b8 with the schedule set
+  (c) drop-in   also YOUTH_SLAM_RGBD=1 with YOUTH_SLAM_RGBD_LEVELS
+
 The last line is one JSON object.
-usage: python tools/rgbd_track_bench.py [rounds] [reps]"""
+usage: python tools/rgbd_track_bench.py [rounds] [reps] [--levels auto|LIST] [ingest] [stream] [drop-in]"""
 import json
 import os
 import subprocess
@@ -52,8 +59,12 @@ def pinned_frames(fr, rgb):
     return pd, pc
 
 
+LEVELS = []   # --levels: the tracker's schedule
+
+
 def ingest(pd, pc, rounds, reps):
     s = torch.cuda.Stream()
+    strides = [st for st, _ in LEVELS if st > 1]
     out = {}
     with youth_rgbd.RgbdContext(W, H, 16) as ctx:
         for m in (1, 8):
@@ -74,6 +85,18 @@ def ingest(pd, pc, rounds, reps):
             run = {"pull": lambda: ctx.pull_host(dl, cl, d_d, d_g, None, stream=s.cuda_stream),
                    "pull_with_rgb": lambda: ctx.pull_host(dl, cl, d_d, d_g, d_c, stream=s.cuda_stream),
                    "memcpy_and_prep3": memcpy_prep}
+            if strides:
+                shapes = [((H + st - 1) // st, (W + st - 1) // st) for st in strides]
+                lv_d = [torch.empty((m, h, w), dtype=torch.int16, device="cuda") for h, w in shapes]
+                lv_g = [torch.empty((m, h, w), dtype=torch.uint8, device="cuda") for h, w in shapes]
+
+                def pull_then_decimate():
+                    ctx.pull_host(dl, cl, d_d, d_g, None, stream=s.cuda_stream)
+                    for st, od, og in zip(strides, lv_d, lv_g):
+                        youth_rgbd.decimate_device(d_d.data_ptr(), d_g.data_ptr(), m, W, H, st,
+                                                   od.data_ptr(), og.data_ptr(), stream=s.cuda_stream)
+
+                run = {"pull_then_decimate": pull_then_decimate, **run}
             t = {k: [] for k in run}
             for r in range(rounds + 1):                # round 0 warms up
                 for _ in range(reps):
@@ -126,6 +149,13 @@ def stream(pd, pc, fr, rgb, rounds, reps):
     seq = youth_rgbd.RgbdContext(W, H, 16)
     run = {"submit_b1": lambda: tracked(ctxs[1], 1), "submit_b8": lambda: tracked(ctxs[8], 8),
            "host_sequence_9": lambda: pieces(seq)}
+    if LEVELS:
+        for b in (1, 8):
+            ctxs[-b] = youth_rgbd.RgbdContext(W, H, 16)
+            ctxs[-b].track_set_batch(b)
+            ctxs[-b].track_set_levels(LEVELS)
+        run["submit_b1_levels"] = lambda: tracked(ctxs[-1], 1)
+        run["submit_b8_levels"] = lambda: tracked(ctxs[-8], 8)
     t = {k: [] for k in run}
     for r in range(rounds + 1):
         for _ in range(reps):
@@ -183,7 +213,11 @@ print("RESULT " + json.dumps(res))
 
 def drop_in(rounds):
     out = {}
-    for mode, extra in (("default", {}), ("rgbd", {"YOUTH_SLAM_RGBD": "1"})):
+    modes = [("default", {}), ("rgbd", {"YOUTH_SLAM_RGBD": "1"})]
+    if LEVELS:
+        spec = ",".join(f"{st}:{it}" for st, it in LEVELS)
+        modes.append(("rgbd_levels", {"YOUTH_SLAM_RGBD": "1", "YOUTH_SLAM_RGBD_LEVELS": spec}))
+    for mode, extra in modes:
         env = {k: v for k, v in os.environ.items() if not k.startswith("YOUTH_SLAM_")}
         env.update(extra, PYTHONPATH=os.path.join(ROOT, "slam-rgbd_amd"))
         r = subprocess.run([sys.executable, "-c", _SLAM_CHILD, "64", str(rounds)], env=env,
@@ -199,16 +233,28 @@ def drop_in(rounds):
 
 
 def main():
-    rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 3
-    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+    global LEVELS
+    args = sys.argv[1:]
+    if "--levels" in args:
+        k = args.index("--levels")
+        LEVELS = youth_rgbd.parse_levels(args[k + 1], W, H)
+        del args[k:k + 2]
+    parts = [a for a in args if not a.isdigit()] or ["ingest", "stream", "drop-in"]
+    nums = [int(a) for a in args if a.isdigit()]
+    rounds = nums[0] if len(nums) > 0 else 3
+    reps = nums[1] if len(nums) > 1 else 3
     fr, _, rgb = youth_synth.sequence_rgb(0, 33, W, H)
     pd, pc = pinned_frames(fr, rgb)
     res = {"size": [W, H], "params": list(youth_rgbd.default_params()),
-           "ingest_us_per_frame": ingest(pd, pc, rounds, reps),
-           "stream_frames_per_s": stream(pd, pc, fr, rgb, rounds, reps)}
+           "levels": [list(l) for l in LEVELS]}
+    if "ingest" in parts:
+        res["ingest_us_per_frame"] = ingest(pd, pc, rounds, reps)
+    if "stream" in parts:
+        res["stream_frames_per_s"] = stream(pd, pc, fr, rgb, rounds, reps)
     for p in pd + pc:
         p.close()
-    res["drop_in"] = drop_in(rounds)
+    if "drop-in" in parts:
+        res["drop_in"] = drop_in(rounds)
     print(json.dumps(res))
     return 0
 
