@@ -1,8 +1,9 @@
 // Stand-alone driver of the pose graph (pose_graph.cpp) for the sanitizer build
 // of tests/loop_asan: the biased C5 keyframe graph of tests/test_loop.py (17
 // ground-truth poses, every odometry step right-multiplied by a fixed twist,
-// one exact loop edge), the argument errors and the interpolation.  Exits 0
-// only when every check holds.
+// one exact loop edge), the same chain with loop edges between free nodes (the
+// long rows of the envelope solver), the argument errors and the
+// interpolation.  Exits 0 only when every check holds.
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -144,6 +145,55 @@ int main()
         double worst = 0.0;
         for (size_t a = 0; a < Xe.size(); ++a) worst = fmax(worst, fabs(Xe[a] - X[a]));
         CHECK(worst <= 1e-9);
+    }
+
+    // beyond the band: exact loop edges between free nodes, (14, 5) given with
+    // i > j, two sharing node 3, weights other than 1, one edge of weight 0 with
+    // a wrong Z, w_rot != w_trans.  H gets blocks far off the diagonal and the
+    // envelope solver long rows.
+    {
+        const int li[4] = {3, 14, 3, 6}, lj[4] = {12, 5, 9, 10};
+        const double lw[4] = {2.0, 0.5, 1.0, 0.0};
+        std::vector<youth_loop_edge> in(edges.begin(), edges.begin() + (n - 1));
+        for (int k = 0; k < 4; ++k) {
+            youth_loop_edge e;
+            memset(&e, 0, sizeof(e));
+            e.i = li[k];
+            e.j = lj[k];
+            e.w = lw[k];
+            double Ai[16];
+            inv(X.data() + (size_t)li[k] * 16, Ai);
+            mul(Ai, X.data() + (size_t)lj[k] * 16, e.Z);
+            if (lw[k] == 0.0) mul(e.Z, B, e.Z);
+            in.push_back(e);
+        }
+        youth_posegraph_params P = youth_posegraph_default_params();
+        P.w_rot = 3.0;
+        P.w_trans = 0.5;
+        std::vector<double> Xi = Xb;
+        CHECK(youth_posegraph_optimize(n, Xi.data(), (int)in.size(), in.data(), &P, &c0, &c1) == YOUTH_OK);
+        pose_error(Xb.data() + 12 * 16, X.data() + 12 * 16, &d0, &m0);
+        pose_error(Xi.data() + 12 * 16, X.data() + 12 * 16, &d1, &m1);
+        printf("interior loops: cost %.6g -> %.6g; node 12: %.3f deg / %.2f mm -> %.3f deg / %.2f mm\n", c0, c1,
+               d0, m0 * 1e3, d1, m1 * 1e3);
+        CHECK(c1 < c0 && c1 >= 0.0);
+        CHECK(d1 < d0 && m1 < m0);
+        CHECK(memcmp(Xi.data(), Xb.data(), 16 * sizeof(double)) == 0);
+        // the edge of weight 0 counts for nothing
+        std::vector<double> Xw = Xb;
+        double w0, w1, worst = 0.0;
+        CHECK(youth_posegraph_optimize(n, Xw.data(), (int)in.size() - 1, in.data(), &P, &w0, &w1) == YOUTH_OK);
+        for (size_t a = 0; a < Xw.size(); ++a) worst = fmax(worst, fabs(Xw[a] - Xi[a]));
+        CHECK(worst <= 1e-12 && fabs(w0 - c0) <= 1e-12 && fabs(w1 - c1) <= 1e-12);
+        // exact odometry: nothing moves
+        double Bi[16];
+        inv(B, Bi);
+        for (int k = 0; k < n - 1; ++k) mul(in[k].Z, Bi, in[k].Z);
+        std::vector<double> Xe = X;
+        CHECK(youth_posegraph_optimize(n, Xe.data(), (int)in.size(), in.data(), &P, &c0, &c1) == YOUTH_OK);
+        worst = 0.0;
+        for (size_t a = 0; a < Xe.size(); ++a) worst = fmax(worst, fabs(Xe[a] - X[a]));
+        CHECK(worst <= 1e-9 && c0 <= 1e-20 && c1 <= 1e-20);
     }
 
     // the argument errors leave X alone

@@ -2,9 +2,11 @@
 checker of the signature and distance kernels and of the pose graph.  CPU only.
 
 signature / distance follow the integer definitions word for word (Python
-integers where 32 bits would not do).  optimize is an independent
-Gauss-Newton: the same residual and cost, the same move X <- X [exp(w), v] of
-a node, but Jacobians by central differences and numpy's solver.
+integers where 32 bits would not do).  gates restates the four measures of a
+verified pair from the two alignments' poses and statistics.  optimize is an
+independent Gauss-Newton: the same residual and cost, the same move
+X <- X [exp(w), v] of a node, but Jacobians by central differences and numpy's
+solver.
 """
 import numpy as np
 
@@ -58,6 +60,26 @@ def candidates(D_row, q, min_gap, max_cell_dist, max_candidates):
     ks = [k for k in range(0, q - min_gap + 1) if int(D_row[k]) <= max_cell_dist * CELLS]
     ks.sort(key=lambda k: (int(D_row[k]), k))
     return ks[:max_candidates]
+
+
+def gates(T_fwd, stats_fwd, T_bwd, stats_bwd, n_pixels, lam):
+    """The four measures of a verified pair (youth_loop_edge) from the two
+    alignments: poses [4, 4] (or [3, 4]) and statistics rows [sum r^2, cnt_g,
+    sum rp^2, cnt_p]; a [iters, 4] array stands for its last row.
+    -> (overlap, gray_rms, fb_rot_deg, fb_trans_m), fp64."""
+    rows = [np.asarray(s, np.float64).reshape(-1, 4)[-1] for s in (stats_fwd, stats_bwd)]
+    overlap = min(float(s[1]) for s in rows) / float(n_pixels)
+    rms = [(255.0 / float(lam)) * float(np.sqrt(s[2] / s[3])) if s[3] > 0 else float("inf")
+           for s in rows]
+    T = []
+    for P in (T_fwd, T_bwd):
+        M = np.eye(4)
+        M[:3] = np.asarray(P, np.float64).reshape(-1, 4)[:3]   # the last row is (0, 0, 0, 1)
+        T.append(M)
+    E = T[0] @ T[1]
+    v = 0.5 * np.array([E[2, 1] - E[1, 2], E[0, 2] - E[2, 0], E[1, 0] - E[0, 1]])
+    ang = np.arctan2(np.linalg.norm(v), 0.5 * (E[0, 0] + E[1, 1] + E[2, 2] - 1.0))
+    return overlap, max(rms), float(np.degrees(ang)), float(np.linalg.norm(E[:3, 3]))
 
 
 # ---------------------------------------------------------------- SO(3) / SE(3)
