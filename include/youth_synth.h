@@ -85,6 +85,29 @@ void youth_synth_sequence_rgb(uint64_t seed, int first_frame, int n, int W, int 
                               const youth_intrinsics* K, int flags, int16_t* frames,
                               double* T_wc, uint8_t* rgb);
 
+#ifndef YOUTH_DISTORTION_DEFINED
+#define YOUTH_DISTORTION_DEFINED
+/* Lens distortion, OpenCV order and meaning (youth_rectify.h). */
+typedef struct youth_distortion {
+    float k1, k2, p1, p2, k3;
+} youth_distortion;
+#endif
+
+/* youth_synth_render_rgb through a distorting lens (the source the rectifier
+ * of youth_rectify.h is tested on; rgb may be NULL).  The ray of pixel (u, v)
+ * goes through the inverse of the Brown-Conrady model, in fp64: with
+ * (xd, yd) = ((u - cx) / fx, (v - cy) / fy), iterate
+ *   x <- (xd - tx(x, y)) / rad(x, y),  y <- (yd - ty(x, y)) / rad(x, y)
+ * 30 times from (xd, yd), where rad = 1 + r2 (k1 + r2 (k2 + r2 k3)),
+ * tx = 2 p1 x y + p2 (r2 + 2 x^2), ty = p1 (r2 + 2 y^2) + 2 p2 x y,
+ * r2 = x^2 + y^2; the ray is (x, y, 1), so depth stays the hit's Z.  A pixel
+ * whose (x, y) does not map back to within 1e-9 of (xd, yd) under the forward
+ * model gets depth 0 and colour 0.  Noise draws are per pixel as in the other
+ * renders; with D = 0 the output is byte for byte youth_synth_render_rgb's. */
+void youth_synth_render_distorted_rgb(const double T_wc[16], int W, int H,
+                                      const youth_intrinsics* K, const youth_distortion* D,
+                                      uint64_t noise_seed, int flags, int16_t* depth, uint8_t* rgb);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,7 @@
 #include "host_copy.h"
 #include "slam_loop_hooks.h"
 #include "slam_map_hooks.h"
+#include "slam_rectify_hooks.h"
 #include "slam_rgbd_hooks.h"
 #include "youth_map.h"
 #include "youth_icp.h"
@@ -612,6 +613,10 @@ int g_last_points = 0;
 std::atomic<const youth_slam_rgbd_hooks*> g_rgbd_hooks{nullptr};
 std::atomic<bool> g_rgbd{false};
 std::atomic<bool> g_carry_color{false};
+// the lens rectifier's hook table (slam_rectify_hooks.h): null unless
+// slam_rectify.cpp is linked in; off unless YOUTH_SLAM_RECTIFY=1 and the YAML
+// has distortion coefficients
+std::atomic<const youth_slam_rectify_hooks*> g_rectify_hooks{nullptr};
 
 bool env_on(const char* name)
 {
@@ -1002,10 +1007,24 @@ void worker_main(int device, std::unique_ptr<Tracker> trk)
         }
         trace(YOUTH_SLAM_EV_TAKE, m);
         int sent = 0;
+        // lens rectification (slam_rectify_hooks.h), in place and once per
+        // frame: everything downstream sees the ideal-pinhole frame.  A
+        // failure releases the batch like a failed submit.
+        int rect_rc = 0;
+        if (const youth_slam_rectify_hooks* xh = g_rectify_hooks.load()) {
+            int16_t* dp[YOUTH_TRACK_MAX_BATCH];
+            uint8_t* cp[YOUTH_TRACK_MAX_BATCH];
+            for (int i = 0; i < m; ++i) {
+                dp[i] = items[i].d();
+                cp[i] = items[i].rgb();
+            }
+            rect_rc = xh->frames(dp, cp, m, w, h);
+            if (rect_rc < 0) fprintf(stderr, "youth_icp: rectification failed: %s\n", xh->last_error());
+        }
         trace(YOUTH_SLAM_EV_SUBMIT_BEGIN, m);
-        const int rc = trk->submit(items, m, (int)pend.size(), &sent);
+        const int rc = rect_rc < 0 ? rect_rc : trk->submit(items, m, (int)pend.size(), &sent);
         trace(YOUTH_SLAM_EV_SUBMIT_END, rc);
-        if (rc < 0) fprintf(stderr, "youth_icp: tracking failed: %s\n", trk->last_error());
+        if (rc < 0 && rect_rc >= 0) fprintf(stderr, "youth_icp: tracking failed: %s\n", trk->last_error());
         // getSlamMapPoints reports the newest recorded frame: only the last
         // frame of a submission is counted
         int npts = 0;
@@ -1156,6 +1175,8 @@ void initSlamModule(const char* config_file, const char* vocabulary_file)
     g_last_points = 0;
     if (const youth_slam_map_hooks* mh = g_map_hooks.load()) mh->start(device);
     if (const youth_slam_loop_hooks* lh = g_loop_hooks.load()) lh->start(device);
+    if (const youth_slam_rectify_hooks* xh = g_rectify_hooks.load())
+        xh->start(device, g_cfg_has_yaml ? config_file : nullptr, &g_cfg_K, g_cfg_W, g_cfg_H);
     g_process.store(true);
     g_batched.store(0);
     for (auto& r : g_realigned) r.store(0);
@@ -1191,6 +1212,7 @@ void stopSlamModule(void)
     if (g_queue) youth_queue_clear(g_queue);
     if (const youth_slam_map_hooks* mh = g_map_hooks.load()) mh->stop();
     if (const youth_slam_loop_hooks* lh = g_loop_hooks.load()) lh->stop();
+    if (const youth_slam_rectify_hooks* xh = g_rectify_hooks.load()) xh->stop();
     {
         std::lock_guard<std::mutex> sl(g_state_mu);
         g_running.store(false);
@@ -1366,6 +1388,8 @@ void youth_slam_set_map_hooks(const youth_slam_map_hooks* hooks) { g_map_hooks.s
 void youth_slam_set_loop_hooks(const youth_slam_loop_hooks* hooks) { g_loop_hooks.store(hooks); }
 
 void youth_slam_set_rgbd_hooks(const youth_slam_rgbd_hooks* hooks) { g_rgbd_hooks.store(hooks); }
+
+void youth_slam_set_rectify_hooks(const youth_slam_rectify_hooks* hooks) { g_rectify_hooks.store(hooks); }
 
 int youth_slam_rgbd_active(void) { return g_running.load() && g_rgbd.load() ? 1 : 0; }
 

@@ -142,11 +142,48 @@ static void texture_rgb(const double p[3], uint8_t rgb[3])
     rgb[2] = tex_channel(tex_bump((p[2] + 0.5 * p[1]) / 0.27), b4);
 }
 
+/* The lens model of youth_synth_render_distorted_rgb in fp64: the distorted
+ * normalised position of the ideal (x, y). */
+static void distort_xy(const youth_distortion* D, double x, double y, double* xd, double* yd)
+{
+    const double k1 = D->k1, k2 = D->k2, p1 = D->p1, p2 = D->p2, k3 = D->k3;
+    const double r2 = x * x + y * y;
+    const double rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
+    const double xy = x * y;
+    *xd = x * rad + ((2.0 * p1) * xy + p2 * (r2 + 2.0 * (x * x)));
+    *yd = y * rad + (p1 * (r2 + 2.0 * (y * y)) + (2.0 * p2) * xy);
+}
+
+/* Its inverse by 30 fixed-point steps from (xd, yd); 0 when the result does
+ * not map back to within 1e-9 of (xd, yd). */
+static int undistort_xy(const youth_distortion* D, double xd, double yd, double* xo, double* yo)
+{
+    const double k1 = D->k1, k2 = D->k2, p1 = D->p1, p2 = D->p2, k3 = D->k3;
+    double x = xd, y = yd;
+    for (int it = 0; it < 30; ++it) {
+        const double r2 = x * x + y * y;
+        const double rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
+        const double xy = x * y;
+        const double tx = (2.0 * p1) * xy + p2 * (r2 + 2.0 * (x * x));
+        const double ty = p1 * (r2 + 2.0 * (y * y)) + (2.0 * p2) * xy;
+        x = (xd - tx) / rad;
+        y = (yd - ty) / rad;
+    }
+    double fx, fy;
+    distort_xy(D, x, y, &fx, &fy);
+    *xo = x;
+    *yo = y;
+    return fabs(fx - xd) <= 1e-9 && fabs(fy - yd) <= 1e-9;
+}
+
 /* One frame: depth as youth_synth_render documents it and, when rgb is not
  * NULL, the texture at every ray's exact hit point (before noise, holes and
- * the range test; 0 where the ray hits nothing). */
+ * the range test; 0 where the ray hits nothing).  D not NULL: the ray of a
+ * pixel goes through the lens model's inverse; a pixel without one hits
+ * nothing. */
 static void render_frame(const double T_wc[16], int W, int H, const youth_intrinsics* K,
-                         uint64_t noise_seed, int flags, int16_t* depth, uint8_t* rgb)
+                         const youth_distortion* D, uint64_t noise_seed, int flags, int16_t* depth,
+                         uint8_t* rgb)
 {
     sphere_t sp[N_SPHERES];
     scene_spheres(sp);
@@ -155,13 +192,13 @@ static void render_frame(const double T_wc[16], int W, int H, const youth_intrin
     for (int v = 0; v < H; ++v) {
         for (int u = 0; u < W; ++u) {
             /* camera ray with z-component 1, so the hit parameter is Z */
-            const double dc[3] = {((double)u - K->cx) / K->fx, ((double)v - K->cy) / K->fy,
-                                  1.0};
+            double dc[3] = {((double)u - K->cx) / K->fx, ((double)v - K->cy) / K->fy, 1.0};
+            const int seen = !D || undistort_xy(D, dc[0], dc[1], &dc[0], &dc[1]);
             double dw[3];
             for (int i = 0; i < 3; ++i)
                 dw[i] = T_wc[i * 4 + 0] * dc[0] + T_wc[i * 4 + 1] * dc[1] +
                         T_wc[i * 4 + 2] * dc[2];
-            const double z = cast_ray(o, dw, sp);
+            const double z = seen ? cast_ray(o, dw, sp) : INFINITY;
             if (rgb) {
                 uint8_t* c = rgb + ((size_t)v * W + u) * 3;
                 c[0] = c[1] = c[2] = 0;
@@ -194,14 +231,21 @@ void youth_synth_render(const double T_wc[16], int W, int H,
                         const youth_intrinsics* K, uint64_t noise_seed,
                         int flags, int16_t* depth)
 {
-    render_frame(T_wc, W, H, K, noise_seed, flags, depth, NULL);
+    render_frame(T_wc, W, H, K, NULL, noise_seed, flags, depth, NULL);
 }
 
 void youth_synth_render_rgb(const double T_wc[16], int W, int H,
                             const youth_intrinsics* K, uint64_t noise_seed,
                             int flags, int16_t* depth, uint8_t* rgb)
 {
-    render_frame(T_wc, W, H, K, noise_seed, flags, depth, rgb);
+    render_frame(T_wc, W, H, K, NULL, noise_seed, flags, depth, rgb);
+}
+
+void youth_synth_render_distorted_rgb(const double T_wc[16], int W, int H,
+                                      const youth_intrinsics* K, const youth_distortion* D,
+                                      uint64_t noise_seed, int flags, int16_t* depth, uint8_t* rgb)
+{
+    render_frame(T_wc, W, H, K, D, noise_seed, flags, depth, rgb);
 }
 
 /* T = [R t; 0 1] from camera orientation angles and position. */
@@ -275,8 +319,8 @@ static void pair_frames(uint64_t seed, int W, int H, const youth_intrinsics* K, 
     mat4_mul(Twc0, T01, Twc1);
     const uint64_t seed_dst = splitmix64(&s);
     const uint64_t seed_src = splitmix64(&s);
-    render_frame(Twc0, W, H, K, seed_dst, flags, dst, dst_rgb);
-    render_frame(Twc1, W, H, K, seed_src, flags, src, src_rgb);
+    render_frame(Twc0, W, H, K, NULL, seed_dst, flags, dst, dst_rgb);
+    render_frame(Twc1, W, H, K, NULL, seed_src, flags, src, src_rgb);
     if (T_gt) memcpy(T_gt, T01, sizeof(T01));
 }
 
@@ -329,7 +373,7 @@ static void sequence_frames(uint64_t seed, int first_frame, int n, int W, int H,
         camera_pose(yaw, pitch, roll, pos, T);
         uint64_t s = seed ^ (0xD1B54A32D192ED03ull * (uint64_t)(k + 1));
         const uint64_t ns = splitmix64(&s);
-        render_frame(T, W, H, K, ns, flags, frames + (size_t)f * N,
+        render_frame(T, W, H, K, NULL, ns, flags, frames + (size_t)f * N,
                      rgb ? rgb + (size_t)f * N * 3 : NULL);
         if (T_wc) memcpy(T_wc + (size_t)f * 16, T, sizeof(T));
     }

@@ -140,6 +140,28 @@ def render_rgb(T_wc: np.ndarray, width: int, height: int, K=None, noise_seed: in
     return out, rgb
 
 
+def render_distorted_rgb(T_wc: np.ndarray, width: int, height: int, K, D, noise_seed: int = 0,
+                          flags: int = 0):
+    """render_rgb() through a lens with distortion D (a youth_rectify.Distortion
+    or k1, k2, p1, p2, k3) -> (depth, rgb); a pixel the lens model's inverse
+    does not reach is 0 in both."""
+    from youth_rectify import as_distortion
+
+    lib = load_library()
+    D = as_distortion(D)
+    lib.youth_synth_render_distorted_rgb.argtypes = [
+        POINTER(c_double), c_int, c_int, POINTER(Intrinsics), POINTER(type(D)), c_uint64, c_int,
+        POINTER(c_int16), POINTER(c_uint8)]
+    lib.youth_synth_render_distorted_rgb.restype = None
+    T = np.ascontiguousarray(T_wc, np.float64)
+    out = np.zeros((height, width), np.int16)
+    rgb = np.zeros((height, width, 3), np.uint8)
+    lib.youth_synth_render_distorted_rgb(_p(T, c_double), width, height, ctypes.byref(K),
+                                         ctypes.byref(D), noise_seed, flags, _p(out, c_int16),
+                                         _p(rgb, c_uint8))
+    return out, rgb
+
+
 def luma(rgb: np.ndarray) -> np.ndarray:
     """Y = (77 R + 150 G + 29 B + 128) >> 8, uint8."""
     c = np.asarray(rgb, np.uint8).astype(np.int32)

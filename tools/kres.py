@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel register use and spills of the HIP translation units
-(icp_kernels, rgbd_align, viewer_cloud, voxel_map, map_render, depth_filter) as hipcc reports them
+(icp_kernels, rgbd_align, viewer_cloud, voxel_map, map_render, depth_filter, rectify) as hipcc reports them
 (-Rpass-analysis=kernel-resource-usage): `python tools/kres.py [filter]`
 compiles each TU for gfx950 with the product flags (object discarded) and
 prints VGPRs / AGPRs / SGPRs / spills / LDS / occupancy per kernel
@@ -12,7 +12,7 @@ import sys
 ROOT = __file__.rsplit("/tools/", 1)[0]
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
 out = ""
-for tu in ("icp_kernels", "rgbd_align", "viewer_cloud", "voxel_map", "map_render", "depth_filter"):
+for tu in ("icp_kernels", "rgbd_align", "viewer_cloud", "voxel_map", "map_render", "depth_filter", "rectify"):
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
            "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", f"-I{ROOT}/include",
            f"-I{ROOT}/slam-rgbd_amd/csrc", "-c", f"{ROOT}/slam-rgbd_amd/csrc/{tu}.hip",
