@@ -323,6 +323,10 @@ youth_icp_ctx* youth_icp_create(int device, int W, int H, int max_frames,
                             "launches of this context are refused\n");
         const char* nqs = getenv("YOUTH_ICP_QUEUES");
         if (nqs && atoi(nqs) >= 1 && atoi(nqs) <= kMaxQueues) c->queues = atoi(nqs);
+        // A/B and test knob: k_icp's pixel loop without its phase priority
+        // (icp_kernels.hip "Phase priority")
+        const char* ipr = getenv("YOUTH_ICP_PRIO");
+        if (ipr && (*ipr == '0' || *ipr == '1') && !ipr[1]) c->issue_prio = *ipr - '0';
         const char* pxm = getenv("YOUTH_ICP_PREP_XCD_MAP");
         if (pxm && (*pxm == '1' || *pxm == '2')) c->prep_xcd_map = *pxm - '0';
         const char* cts = getenv("YOUTH_ICP_COOP_TILE_SRC");

@@ -152,6 +152,7 @@ struct youth_icp_ctx {
     youth_filter_params flt{8, 96};
     int16_t* d_raw = nullptr;        // [trk_raw_slots][N] raw frames of one launch, filtered into d_depth
     int queues = 0;                  // k_icp work queues (YOUTH_ICP_QUEUES=1..8; 0: by batch size)
+    int issue_prio = 1;              // k_icp's projection phase at wave priority 1 (YOUTH_ICP_PRIO=0: off)
     int share = 1;                   // contexts launching k_icp concurrently (set_concurrency)
     int prep_xcd_map = 0;             // YOUTH_ICP_PREP_XCD_MAP=1: k_prep tiles contiguous per XCD (slower)
     // pipelined tracking (youth_icp_track_submit / _collect): up to

@@ -631,14 +631,30 @@ __global__ void k_init(const double* __restrict__ T_init, int n, double* T64, fl
 // code (xform_project, match_accumulate), the wave reduce-scatter and the
 // fused solve's hand-off are icp_device.h's, shared with k_rgbd_reduce.
 
+// Phase priority of k_icp's pixel loop (kPhase with prio, wave-uniform:
+// IterState.prio, YOUTH_ICP_PRIO; k_reduce keeps the plain form).  The loop is
+// bound by VALU issue at four waves per SIMD, and the SIMD picks the wave to
+// issue from by priority, then age (MI355X_MICROARCH.md "Two waves per SIMD",
+// item 2).  A step is a projection phase (four back-projections and
+// projections, ending in the four record gathers and the depth prefetch) and
+// a match phase that consumes the records.  The wave runs its projection
+// phase at priority 1 and drops to 0 right after its last load is issued, so
+// a wave that has not yet asked for its records issues ahead of the match
+// phases of waves that already hold theirs, and its memory round trip runs
+// behind their arithmetic instead of after it: -2.5 % on k_icp at no VALU
+// instruction and no register (profiles/issue_order/).  Priority is 0 again
+// before the step's first wait for a record, so it is 0 wherever the loop is
+// left, at every barrier and at every poll of another workgroup's progress
+// after it: a raised wave never waits on the waves it outranks.
+
 // Accumulate source pixels [start, end) of one pair into acc (spec a7-a9).
-template <int kSp, bool kAssoc, bool kFast, bool kAligned>
+template <int kSp, bool kAssoc, bool kFast, bool kAligned, bool kPhase = false>
 __device__ __forceinline__ void accumulate_chunk(const int16_t* __restrict__ sD,
                                                  const float4* __restrict__ rec, int rec_bytes,
                                                  const float* __restrict__ T, int start, int end,
                                                  int W, int H, const Intr& K, const FastK& F,
                                                  float thr2, double* acc,
-                                                 int32_t* __restrict__ arow)
+                                                 int32_t* __restrict__ arow, bool prio = false)
 {
     // the pair's target records through a buffer descriptor (wave-uniform
     // base): a gather costs one 32-bit byte offset instead of 64-bit address
@@ -671,6 +687,8 @@ __device__ __forceinline__ void accumulate_chunk(const int16_t* __restrict__ sD,
                                                                        rdep, i * 2, 0, 0))
                                        : short4{};
     for (; i < end; i += kRedStep) {
+        // (s_setprio is a scalar instruction: the guard is an SGPR condition)
+        if (kPhase && prio) __builtin_amdgcn_s_setprio(1);
         const short4 d4 = kAligned ? dnext : load_depth4<kAligned>(sD, i, end);
         const int dd[4] = {d4.x, d4.y, d4.z, d4.w};
         float qx[4], qy[4], qz[4], fu[4], fv[4];
@@ -689,6 +707,8 @@ __device__ __forceinline__ void accumulate_chunk(const int16_t* __restrict__ sD,
             ++v0;
         }
         // four 16-byte fetches back to back, then the next step's depth
+        // (a gather issued behind its own projection, three quarters of the
+        // phase earlier for the first, measured 10 % slower: HISTORY.md)
         f4v t[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -700,6 +720,9 @@ __device__ __forceinline__ void accumulate_chunk(const int16_t* __restrict__ sD,
         if (kAligned)
             dnext = __builtin_bit_cast(
                 short4, __builtin_amdgcn_raw_buffer_load_b64(rdep, (i + kRedStep) * 2, 0, 0));
+        // every load of the step is issued: the match phase yields (a no-op
+        // at priority 0)
+        if (kPhase) __builtin_amdgcn_s_setprio(0);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             LaneMask okm;
@@ -949,6 +972,7 @@ struct IterState {
     int nq;               // work queues (1..kMaxQueues): heads at head[kQHeads + 32 q]
     int ident_first;      // every pose starts at identity: iteration 0 takes accumulate_chunk_ident
     int first;            // first iteration to run (1: k_prep_ident ran iteration 0 and set epoch = 1)
+    int prio;             // != 0: the pixel loop's projection phase at wave priority 1 (YOUTH_ICP_PRIO)
 };
 
 // One dequeue: from the workgroup's current queue q, moving on to the next
@@ -1070,6 +1094,10 @@ __device__ __forceinline__ int icp_claim(const IterState& is, int item, int tota
 // thread 0 dequeues and claims the next item -> barrier.
 // (Dequeuing ahead from wave 1 so that waves 1-3 skip the second barrier
 // measured no faster: DESIGN.md §5.)
+// Wave priority is raised in the pixel loop only (is.prio, accumulate_chunk)
+// and is 0 at every barrier here and in icp_claim's polls.  (Raising the
+// hand-off chain too, wave 0 from its publish to the ticket and the last
+// arriver through sum, solve and publish, measured -0.35 %: HISTORY.md.)
 template <int kSp, bool kFast, bool kAligned>
 __global__ __launch_bounds__(kRedThreads, 4) void k_icp(const int16_t* __restrict__ dsrc,
                                                     const float4* __restrict__ recs, size_t P,
@@ -1130,10 +1158,10 @@ __global__ __launch_bounds__(kRedThreads, 4) void k_icp(const int16_t* __restric
                     dsrc + (size_t)(pm.src0 + p) * N, recs + (size_t)(pm.tgt0 + p) * P,
                     (int)(P * sizeof(float4)), start, end, W, H, K, F, thr2, acc);
         } else {
-            accumulate_chunk<kSp, false, kFast, kAligned>(dsrc + (size_t)(pm.src0 + p) * N,
-                                                     recs + (size_t)(pm.tgt0 + p) * P,
-                                                     (int)(P * sizeof(float4)), T, start, end, W,
-                                                     H, K, F, thr2, acc, nullptr);
+            accumulate_chunk<kSp, false, kFast, kAligned, true>(
+                dsrc + (size_t)(pm.src0 + p) * N, recs + (size_t)(pm.tgt0 + p) * P,
+                (int)(P * sizeof(float4)), T, start, end, W, H, K, F, thr2, acc, nullptr,
+                is.prio != 0);
         }
         {
             double tot;
@@ -1220,10 +1248,12 @@ __global__ __launch_bounds__(kRedThreads, 4) void k_icp(const int16_t* __restric
 // identity pose (no T_init, exact reduction; run_iterations).  There every
 // source pixel matches the target record at its own index (icp_device.h
 // ident_accumulate), and k_prep holds that record in registers, and the
-// target's point in its LDS planes, when it stores it.  So the pass that is
-// bound by its 16 B/px store stream also loads the pair's source depth at
-// the pixel (2 B/px) and runs the gate, r, J and the 29 sums on its idle VALU,
-// and k_icp runs iterations 1 .. iters - 1 only.
+// target's point in its LDS planes, when it stores it.  So the prep pass also
+// loads the pair's source depth at the pixel (2 B/px) and runs the gate, r, J
+// and the 29 sums, and k_icp runs iterations 1 .. iters - 1 only.  With them
+// the pass is bound by VALU issue, not by its 16 B/px store stream (~186 VALU
+// instructions per pixel, the SIMDs' issue slots full by the counters: DESIGN.md
+// §5).
 //   * A UNIT is one wave (a 64-thread workgroup) on 64 adjacent columns and a
 //     band of `band` consecutive rows of one frame, lane l on column x0 + l:
 //     no LDS planes and no barrier.  The wave walks down its columns with the
@@ -2686,7 +2716,7 @@ int run_iterations(youth_icp_ctx* c, hipStream_t s, const int16_t* dsrc, int src
                            c->queues ? c->queues : (n_pairs >= 128 ? kMaxQueues : 1),
                            // no T_init: iteration 0 at the identity pose (exact sums only:
                            // the lane32 kernels have no such form)
-                           ident && !ident_prep, first};
+                           ident && !ident_prep, first, c->issue_prio};
         c->last_first_form = ident_prep ? 2 : ident ? 1 : 0;
         if (exported) *exported = d_T_out != nullptr;  // k_icp's final solves write d_T_out
         EventPair ep{};

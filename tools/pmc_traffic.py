@@ -70,7 +70,7 @@ def main():
     res = summarize(root)
     key = next(k for k in res if k.startswith("k_icp") or k.startswith("k_reduce"))
     r = res[key]
-    fetch = r["FETCH_SIZE"] * 1024.0
+    fetch = r.get("FETCH_SIZE", 0.0) * 1024.0   # 0: a root without the traffic passes (VALU account only)
     write = r.get("WRITE_SIZE", 0.0) * 1024.0
     px = pairs * W * H
     doc = {
@@ -144,8 +144,26 @@ def main():
             doc["k_prep_bytes_per_px"] = doc["k_prep_hbm_bytes"] / (pairs * W * H)
         pacc = valu_account(res[m], doc.get("simds", 1024), costs_path, root_dir)
         if pacc:
+            # the prep pass's issue fraction, the account k_icp has above:
+            # instructions by class x their measured issue cost over the
+            # SIMD-cycles of the launch; "other" (moves, selects, compares,
+            # DPP) priced at 4.3 cycles, and at 2.4 in the second figure
+            doc["k_prep_kernel"] = m
             doc["k_prep_valu_account"] = pacc
             doc["k_prep_valu_busy_frac"] = pacc["busy_frac"]
+            doc["k_prep_valu_busy_frac_other_at_2_4_cycles"] = pacc["busy_frac_other_at_2_4_cycles"]
+            pr = res[m]
+            pcyc = pr["GRBM_GUI_ACTIVE"] / N_XCD
+            doc["k_prep_valu_wave_instructions_per_launch"] = pr["SQ_INSTS_VALU"]
+            doc["k_prep_valu_lane_ops_per_px"] = pr["SQ_INSTS_VALU"] * 64 / px
+            doc["k_prep_valu_cycles_per_instruction"] = doc.get("simds", 1024) * pcyc / pr["SQ_INSTS_VALU"]
+            doc["k_prep_gpu_cycles_per_launch"] = pcyc
+            pd = [int(row["End_Timestamp"]) - int(row["Start_Timestamp"])
+                  for f in glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True)
+                  if "pmc_types" in f and "pmc_types2" not in f
+                  for row in csv.DictReader(open(f)) if m in row.get("Kernel_Name", "")]
+            if pd:
+                doc["k_prep_effective_clock_ghz"] = pcyc / (sum(pd) / len(pd))
     json.dump(doc, open(out, "w"), indent=1)
     print(json.dumps(doc, indent=1))
 

@@ -30,7 +30,9 @@ timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ
 timeout -k 10 300 rocprofv3 --pmc SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_MISC SQ_WAVE_CYCLES SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE --kernel-trace -T --output-format csv -d $OUT/pmc_active -o pmc \
     -- python3 bench.py $ARGS > $OUT/bench_active.log 2>&1
 python3 tools/pmc_summary.py $OUT > $OUT/pmc_summary.txt
-python3 tools/pmc_traffic.py $OUT $OUT/traffic.json ${PAIRS:-512} 640 480 10 > /dev/null
+# iterations a k_icp launch covers: 9 of the default run's 10 (k_prep_ident runs iteration 0);
+# KICP_ITERS=10 for a run that keeps every iteration in k_icp (T_init, YOUTH_ICP_NO_IDENT_FIRST=1)
+python3 tools/pmc_traffic.py $OUT $OUT/traffic.json ${PAIRS:-512} 640 480 ${KICP_ITERS:-9} > /dev/null
 KT=$(find $OUT/kt -name '*kernel_trace.csv' -print -quit)
 python3 tools/kt_summary.py $KT 5 > $OUT/kt_summary.txt
 cp "$(find $OUT/kt -name '*kernel_stats.csv' -print -quit)" $OUT/kernel_stats.csv
