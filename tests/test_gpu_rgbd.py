@@ -130,8 +130,10 @@ def test_lambda_zero_is_the_depth_only_align(pairs160):
     assert np.array_equal(stats[:, :, 3], cnt_icp) and not stats[:, :, 2].any()
 
 
-@pytest.mark.parametrize("W,H,fastdiv", [(97, 53, True), (160, 120, True), (160, 120, False)],
-                         ids=["97x53_unaligned", "160x120_aligned", "160x120_ieee_division"])
+@pytest.mark.parametrize("W,H,fastdiv", [(97, 53, True), (160, 120, True), (160, 120, False),
+                                         (97, 53, False)],
+                         ids=["97x53_unaligned", "160x120_aligned", "160x120_ieee_division",
+                              "97x53_unaligned_ieee_division"])
 def test_lambda_zero_equals_the_per_iteration_align_bit_for_bit(W, H, fastdiv, monkeypatch):
     """k_rgbd_reduce and k_reduce's fused solve run one text of a7-a9, of the
     wave sum and of the hand-off (csrc/icp_device.h), on the same chunks: at

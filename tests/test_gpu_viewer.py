@@ -29,6 +29,32 @@ def _frame(W, H, seed, holes=0.1, negative=True):
     return depth, rgb
 
 
+NAN_BITS = 0x7FC0BEEF          # one quiet-NaN pattern; no vertex holds a NaN
+GUARD = 64                     # floats after the last frame's list
+
+
+def guarded_vertices(n, N):
+    """The device vertex buffer of n frames of N pixels and GUARD floats more,
+    as int32 words all holding NAN_BITS."""
+    return torch.full((n * N * 6 + GUARD,), NAN_BITS, dtype=torch.int32, device="cuda")
+
+
+def check_guarded_vertices(words, counts, wants, N):
+    """words: guarded_vertices back on the host.  Every frame's list is the
+    expected one, bit for bit; the floats [count * 6, N * 6) behind it and the
+    guard behind the last frame still hold NAN_BITS."""
+    words = words.view(np.uint32)
+    n = len(wants)
+    assert words.shape == (n * N * 6 + GUARD,)
+    for f, want in enumerate(wants):
+        assert counts[f] == want.shape[0], f
+        frame = words[f * N * 6:(f + 1) * N * 6]
+        cnt = int(counts[f])
+        assert np.array_equal(frame[:cnt * 6].reshape(cnt, 6), _bits(want)), f
+        assert (frame[cnt * 6:] == NAN_BITS).all(), f
+    assert (words[n * N * 6:] == NAN_BITS).all()
+
+
 def test_cloud_640x480_synthetic_scene_bit_exact():
     src, _, _ = youth_synth.pairs(0, 1)
     depth = src[0]
@@ -90,7 +116,8 @@ def test_cloud_device_batch(offset, px, monkeypatch):
     c_all = torch.zeros(n * H * W * 3 + offset, dtype=torch.uint8, device="cuda")
     d_all[offset:] = torch.from_numpy(np.stack([f[0] for f in frames]).reshape(-1)).cuda()
     c_all[offset:] = torch.from_numpy(np.stack([f[1] for f in frames]).reshape(-1)).cuda()
-    verts = torch.zeros((n, H * W, 6), dtype=torch.float32, device="cuda")
+    guarded = guarded_vertices(n, H * W)
+    verts = guarded[:n * H * W * 6].view(torch.float32).view(n, H * W, 6)
     counts = torch.full((n,), -1, dtype=torch.int32, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
     with youth_viewer.CloudBuilder(W, H, max_frames=n) as cb:
@@ -99,10 +126,12 @@ def test_cloud_device_batch(offset, px, monkeypatch):
         torch.cuda.synchronize()
     counts = counts.cpu().numpy()
     verts = verts.cpu().numpy()
-    for f, (d, c) in enumerate(frames):
-        want = oracle.viewer_cloud(d, c)
+    wants = [oracle.viewer_cloud(d, c) for d, c in frames]
+    for f, want in enumerate(wants):
         assert counts[f] == want.shape[0]
         assert np.array_equal(_bits(verts[f, : counts[f]]), _bits(want))
+    # nothing was stored past a frame's list or past the batch
+    check_guarded_vertices(guarded.cpu().numpy(), counts, wants, H * W)
 
 
 def _pose(rng, big=False):
@@ -131,7 +160,8 @@ def test_cloud_world_frame_batch(offset):
     d_all[offset:] = torch.from_numpy(np.stack([f[0] for f in frames]).reshape(-1)).cuda()
     c_all[offset:] = torch.from_numpy(np.stack([f[1] for f in frames]).reshape(-1)).cuda()
     d_T = torch.from_numpy(T.reshape(n, 12)).cuda()
-    verts = torch.zeros((n, H * W, 6), dtype=torch.float32, device="cuda")
+    guarded = guarded_vertices(n, H * W)
+    verts = guarded[:n * H * W * 6].view(torch.float32).view(n, H * W, 6)
     counts = torch.full((n,), -1, dtype=torch.int32, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
     with youth_viewer.CloudBuilder(W, H, max_frames=n) as cb:
@@ -139,15 +169,22 @@ def test_cloud_world_frame_batch(offset):
                               d_T.data_ptr(), verts.data_ptr(), counts.data_ptr(), stream=stream)
         torch.cuda.synchronize()
         got = verts.cpu().numpy(), counts.cpu().numpy()
+        posed_words = guarded.cpu().numpy()
         cb.build_device_posed(d_all.data_ptr() + offset * 2, c_all.data_ptr() + offset, n, W, H,
                               0, verts.data_ptr(), counts.data_ptr(), stream=stream)
         torch.cuda.synchronize()
         cam = verts.cpu().numpy()
+        cam_words, cam_counts = guarded.cpu().numpy(), counts.cpu().numpy()
     for f, (d, c) in enumerate(frames):
         want = oracle.viewer_cloud(d, c, T_world=T[f])
         assert got[1][f] == want.shape[0]
         assert np.array_equal(_bits(got[0][f, : got[1][f]]), _bits(want))
         assert np.array_equal(_bits(cam[f, : got[1][f]]), _bits(oracle.viewer_cloud(d, c)))
+    # nothing was stored past a frame's list or past the batch, by either call
+    check_guarded_vertices(posed_words, got[1],
+                           [oracle.viewer_cloud(d, c, T_world=T[f]) for f, (d, c) in enumerate(frames)],
+                           H * W)
+    check_guarded_vertices(cam_words, cam_counts, [oracle.viewer_cloud(d, c) for d, c in frames], H * W)
 
 
 def test_cloud_rejects_bad_arguments():
