@@ -9,8 +9,9 @@
 // reduce-scatter (wave_reduce_scatter<kN>); the fused solve's hand-off
 // between a pair's workgroups (handoff_publish, handoff_sum); the a10 solve
 // and pose update.  One text of the spec's arithmetic and of the summation
-// order for both units.  The host units include it (through icp_host.h) for
-// the constants and structs alone.
+// order for both units.  The host units (icp_api.cpp, icp_batch.cpp,
+// icp_track.cpp; rgbd_api.cpp, rgbd_track.cpp) include it through icp_host.h
+// for the constants and structs alone.
 //
 // No __global__ function lives here: a kernel in a shared header would be
 // emitted again by every unit that includes it.

@@ -7,7 +7,8 @@
 //   icp_api.cpp      create / destroy, setters, device and stage-level entries
 //   icp_batch.cpp    the host batch and multi-GPU batch API
 //   icp_track.cpp    the pipelined tracker
-//   rgbd_align.hip   the RGB-D alignment, on this context
+//   rgbd_host.h      the RGB-D alignment's own interface, on this context:
+//                    rgbd_align.hip, rgbd_api.cpp, rgbd_track.cpp
 #ifndef YOUTH_ICP_HOST_H
 #define YOUTH_ICP_HOST_H
 
@@ -286,6 +287,9 @@ int launch_pull_frames(youth_icp_ctx* c, hipStream_t s, const int16_t* const* sr
 // icp_track.cpp: whether [p, p + bytes) lies inside one buffer of
 // youth_icp_host_alloc (page-locked: a kernel may read it in place).
 bool host_alloc_covers_bytes(const void* p, size_t bytes);
+// icp_track.cpp: a collect's wait for its frame: with poll, up to 2 ms of
+// hipEventQuery first; then hipEventSynchronize.
+hipError_t wait_event_polled(hipEvent_t ev, bool poll);
 // The self-test kernels (0 projdiv, 1 projquot, 2 normalize) on the null
 // stream; returns hipGetLastError().
 hipError_t launch_selftest(int which, unsigned long long n, unsigned long long seed,

@@ -2,6 +2,8 @@
 // youth_icp_track_*): frames submitted one at a time or in micro-batches, each
 // aligned to the frame before it, results collected in order; the depth filter
 // in front of it; the page-locked buffers it reads in place.  Host code only.
+// Two helpers at the tail serve rgbd_track.cpp as well (icp_host.h):
+// host_alloc_covers_bytes and wait_event_polled.
 
 #include <stdint.h>
 #include <stdio.h>
@@ -115,17 +117,7 @@ static bool trk_chain_fits(const youth_icp_ctx* c, int m)
 // hipMemcpyAsync, so a pageable buffer passed by mistake is copied by the
 // runtime instead of faulting the GPU.
 static std::mutex g_host_mu;
-static std::map<uintptr_t, size_t> g_host_bufs;  // base -> bytes
-
-static bool host_alloc_covers(const int16_t* p, size_t values)
-{
-    const uintptr_t a = (uintptr_t)p;
-    std::lock_guard<std::mutex> lk(g_host_mu);
-    auto it = g_host_bufs.upper_bound(a);
-    if (it == g_host_bufs.begin()) return false;
-    --it;
-    return a >= it->first && a + values * sizeof(int16_t) <= it->first + it->second;
-}
+static std::map<uintptr_t, size_t> g_host_bufs;  // base -> bytes (host_alloc_covers_bytes, below)
 
 // the SLAM module's event trace (slam_api.cpp, youth_slam_trace_enable):
 // steps inside a submission, YOUTH_SLAM_EV_SUBMIT_STEP.  Weak: a program
@@ -249,7 +241,8 @@ static int track_submit_frames(youth_icp_ctx* c, const int16_t* depth, int m,
     // the caller's frames are pulled in place only when youth_icp_host_alloc
     // made them (the staging buffers always are page-locked)
     bool pull = !c->trk_copy_sdma;
-    for (int i = 0; pull && frames && i < m; ++i) pull = host_alloc_covers(frames[i], N);
+    for (int i = 0; pull && frames && i < m; ++i)
+        pull = host_alloc_covers_bytes(frames[i], N * sizeof(int16_t));
     if (pull) {
         const int16_t* src[kCoopMaxChain];
         for (int i = 0; i < m; ++i) src[i] = frames ? frames[i] : c->trk[qi[i]].pinned;
@@ -424,29 +417,13 @@ void youth_icp_host_free(int16_t* p)
     (void)hipHostFree(p);
 }
 
-// A collect waits for its frame by polling the event for up to 2 ms before
-// the runtime's blocking wait: a sleeping wait's wake-up cost a backlogged
-// SLAM worker up to ~0.6 ms per micro-batch (profiles/r04/slamtrace_r4k.txt).
-// YOUTH_ICP_TRACK_WAIT=sync keeps the blocking wait only (A/B).
-static hipError_t track_wait(hipEvent_t ev)
+int youth_icp_track_collect(youth_icp_ctx* c, double* T_rel, int* has_ref)
 {
+    // YOUTH_ICP_TRACK_WAIT=sync keeps the blocking wait only (A/B)
     static const bool poll = [] {
         const char* e = getenv("YOUTH_ICP_TRACK_WAIT");
         return !(e && strcmp(e, "sync") == 0);
     }();
-    if (poll) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (;;) {
-            const hipError_t r = hipEventQuery(ev);
-            if (r != hipErrorNotReady) return r;
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-        }
-    }
-    return hipEventSynchronize(ev);
-}
-
-int youth_icp_track_collect(youth_icp_ctx* c, double* T_rel, int* has_ref)
-{
     if (!c || !T_rel) return g_icp_err.set(YOUTH_EINVAL, "track_collect: bad arguments");
     if (c->trk_n == 0) return g_icp_err.set(YOUTH_EINVAL, "track_collect: no frame in flight");
     int rc = bind_device(c);
@@ -454,7 +431,7 @@ int youth_icp_track_collect(youth_icp_ctx* c, double* T_rel, int* has_ref)
     auto& q = c->trk[c->trk_head];
     c->trk_head = (c->trk_head + 1) % c->trk_cap;
     --c->trk_n;
-    HIP_TRY(track_wait(q.ev));
+    HIP_TRY(wait_event_polled(q.ev, poll));
     if (has_ref) *has_ref = q.has_ref;
     if (!q.has_ref) {
         for (int i = 0; i < 16; ++i) T_rel[i] = (i % 5) == 0 ? 1.0 : 0.0;
@@ -675,8 +652,8 @@ void youth_icp_track_reset(youth_icp_ctx* c)
 
 namespace youth_icp {
 
-// host_alloc_covers for the RGB-D tracker's frames (rgbd_align.hip): depth and
-// colour alike lie in buffers of youth_icp_host_alloc, sized in bytes here
+// For this tracker's depth frames and the RGB-D tracker's depth and colour
+// frames (rgbd_track.cpp): all lie in buffers of youth_icp_host_alloc.
 bool host_alloc_covers_bytes(const void* p, size_t bytes)
 {
     const uintptr_t a = (uintptr_t)p;
@@ -685,6 +662,23 @@ bool host_alloc_covers_bytes(const void* p, size_t bytes)
     if (it == g_host_bufs.begin()) return false;
     --it;
     return a >= it->first && a + bytes <= it->first + it->second;
+}
+
+// A collect (here and in rgbd_track.cpp) waits for its frame by polling the
+// event for up to 2 ms before the runtime's blocking wait: a sleeping wait's
+// wake-up cost a backlogged SLAM worker up to ~0.6 ms per micro-batch
+// (profiles/r04/slamtrace_r4k.txt).  poll false: the blocking wait only.
+hipError_t wait_event_polled(hipEvent_t ev, bool poll)
+{
+    if (poll) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (;;) {
+            const hipError_t r = hipEventQuery(ev);
+            if (r != hipErrorNotReady) return r;
+            if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
+        }
+    }
+    return hipEventSynchronize(ev);
 }
 
 }  // namespace youth_icp

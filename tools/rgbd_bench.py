@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""The RGB-D alignment (csrc/rgbd_align.hip) by the numbers, run
+"""The RGB-D alignment (kernels csrc/rgbd_align.hip, host csrc/rgbd_api.cpp;
+DESIGN.md §13) by the numbers, run
 by hand (not part of bench.py).  One process, HIP events, the variants
 alternating within every round:
 

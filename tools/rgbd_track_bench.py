@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The streaming RGB-D tracker (csrc/rgbd_align.hip) by the
+"""The streaming RGB-D tracker (csrc/rgbd_track.cpp) by the
 numbers, run by hand (not part of bench.py).  One MI355X, 640x480, 10
 iterations, the variants alternating within every round:
 
