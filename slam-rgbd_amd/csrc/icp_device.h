@@ -315,7 +315,7 @@ __device__ __forceinline__ float4 prep_record(float px, float py, float pz, floa
     const float cy = az * bx - ax * bz;
     const float cz = ax * by - ay * bx;
     const float len2 = (cx * cx + cy * cy) + cz * cz;
-    const bool has_n = inner & (zmin != 0u) & (len2 > 0.0f);
+    bool has_n = inner & (zmin != 0u) & (len2 > 0.0f);
     const float len = sqrt_rn_mid(len2);
     const float r = proj_recip(len);
     float nx = norm_div(cx, len, r);
@@ -326,6 +326,11 @@ __device__ __forceinline__ float4 prep_record(float px, float py, float pz, floa
         nx = cx / l;
         ny = cy / l;
         nz = cz / l;
+        // |c|^2 overflowed (points of ~10^10 m under a corner camera): c /
+        // inf is (0, 0, 0), and a zero normal is no normal (spec a6 / a7:
+        // the oracle tests the stored normal).  A finite len2 > 0 leaves a
+        // component of at least |c| / sqrt(3), so only this branch needs the test
+        has_n = (nx != 0.0f) | (ny != 0.0f) | (nz != 0.0f);
     }
     // oriented so n.P <= 0
     if (((nx * px + ny * py) + nz * pz) > 0.0f) {
@@ -678,7 +683,11 @@ __device__ __forceinline__ void survey_project(const float* T, float sx, float s
     // unsigned compare on its bits (negative and NaN bit patterns lie
     // above 2^60's): every lane takes the fast quotient with den = P'_z;
     // a valid source whose P'_z is <= 0 or outside the range (never in
-    // practice) redoes it below as the IEEE division of the spec.  The
+    // practice: tests/test_gpu_icp_hostile.py puts whole frames at P'_z <= 0,
+    // which qpos rejects; P'_z in (0, 2^-60) or above 2^60 with the pixel
+    // still in the frame no test reaches, profiles/hostile/mutant.txt)
+    // redoes it below as the IEEE division of
+    // the spec.  The
     // other lanes' quotients may be inf / NaN; the mask drops them.
     const LaneMask sok = mask_gt(sz, 0.0f);
     const LaneMask dok = mask_ule(__float_as_uint(qz) - 0x21800000u, 0x5d800000u - 0x21800000u);

@@ -389,8 +389,13 @@ __device__ __forceinline__ void prep_tile(const int16_t* __restrict__ dep, float
         const int o = ly * kLW + lx;
         const float px = sX[o], py = sY[o], pz = sZ[o];
         if (X) {
-            X[i] = px;
-            X[P + i] = py;
+            // an invalid pixel's point is (+0, +0, +0) (spec a2): its x, y
+            // are (u - cx) 0 / fx, which is -0 left of and above the principal
+            // point under the IEEE division (the fast one's n l term happens
+            // to give +0 under the viewer's camera).  Only the stored planes
+            // show the sign; the records never read an invalid point's x, y
+            X[i] = pz > 0.0f ? px : 0.0f;
+            X[P + i] = pz > 0.0f ? py : 0.0f;
             X[2 * P + i] = pz;
         }
         // every lane forms the record from its LDS neighbours (the halo
